@@ -15,6 +15,11 @@ is how the server's batcher drives the engine.  Per-request latency = submit -> 
 Prints ONE JSON line on rank 0 (value = total requests/s over all ranks, computed from the
 max elapsed time over ranks).  Weights are random-init and inputs synthetic (no network).
 
+A plain run sets up, warms up, times ``--steps`` steps and prints the line.  ``--full`` adds the
+same-run stock-PyTorch engine (``--measure-eager``, ``vs_pytorch_eager_per_gpu``).
+``--dump-outputs DIR`` writes what the last timed step returned (top-5 probabilities and classes
+per request) as float32 ``DIR/*.npy``; weights and inputs are seeded, so two builds can be compared.
+
 Launch modes:
   * ``python bench.py --gpus N`` with no ``WORLD_SIZE`` in the environment: this process is a
     pure launcher (it touches neither the GPU nor ``torch.cuda``) and starts N rank processes of
@@ -104,11 +109,19 @@ def parse_args(argv=None):
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--serial", action="store_true", help="one compute stream (no concurrent in-flight batches)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the same-run stock-PyTorch "
+                         "engine (--measure-eager).  A plain run only sets up, warms up, times --steps "
+                         "steps and prints the result line")
     ap.add_argument("--measure-eager", type=int, default=int(os.environ.get("MLS_MEASURE_EAGER", 20)),
                     metavar="STEPS",
-                    help="after the timed run (which it does not touch), time STEPS batches of the "
-                         "stock-PyTorch (MIOpen/hipBLASLt) engine in the same process and report "
+                    help="with --full: after the timed run (which it does not touch), time STEPS batches "
+                         "of the stock-PyTorch (MIOpen/hipBLASLt) engine in the same process and report "
                          "vs_pytorch_eager_per_gpu -- BASELINE.md's config-2 bar; 0 = skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller "
+                         "(rank 0's per-request top-5 probabilities and class indices) as float32 "
+                         "DIR/<name>.npy; the weights (--seed) and the inputs are the same from run to run")
     ap.add_argument("--launch-timeout", type=float, default=1500.0,
                     help="launcher mode: bound on the whole N-rank job (s)")
     return ap.parse_args(argv)
@@ -235,16 +248,19 @@ def run_rank(args) -> int:
                     return k
 
     def run_steps(n, lat):
+        """Run ``n`` batches through the engine; returns what the last one submitted gave its caller."""
         pending = []
+        last = None
         nxt = engine.prepare(pool[0]) if prestage and n else None
         for i in range(n):
             t0 = time.perf_counter()
             if prestage:
-                pending.append(engine.launch_prepared(nxt))
+                last = engine.launch_prepared(nxt)
                 if i + 1 < n:
                     nxt = engine.prepare(pool[(i + 1) % len(pool)])
             else:
-                pending.append(engine.submit(pool[i % len(pool)]))
+                last = engine.submit(pool[i % len(pool)])
+            pending.append(last)
             host_s[0] += time.perf_counter() - t0
             if len(pending) >= args.inflight:
                 t = pending.pop(oldest_or_first_done(pending))
@@ -257,6 +273,7 @@ def run_rank(args) -> int:
             lat.append(time.perf_counter() - t.t_arrive)
             events.append((t.t_arrive, time.perf_counter(), getattr(t, "stamps", None),
                            getattr(t, "launch_ns", None)))
+        return last.wait() if last is not None else None
 
     phases = os.environ.get("MLS_BENCH_PHASES")  # diagnostics: wall-clock stamps of the phases
 
@@ -302,12 +319,18 @@ def run_rank(args) -> int:
     torch.cuda.synchronize(device)
     stamp("timed")
     t_start = time.perf_counter()
-    run_steps(args.steps, lat)
+    last_out = run_steps(args.steps, lat)
     torch.cuda.synchronize(device)
     mdist.barrier()
     elapsed = time.perf_counter() - t_start
     gc.enable()
     stamp("done")
+    if args.dump_outputs and info.rank == 0 and last_out is not None:
+        # the engine's return value for the last timed batch: (top-5 probabilities, top-5 classes),
+        # one row per request (a few hundred bytes; class indices < 1000 are exact in float32)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in zip(("top5_prob", "top5_index"), last_out):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(arr, dtype=np.float32))
     if tickets_log and info.rank == 0:
         with open(tickets_log, "a") as f:
             f.write(json.dumps({"steps": args.steps, "elapsed_ms": elapsed * 1e3,
@@ -336,7 +359,8 @@ def run_rank(args) -> int:
     total_req = world * args.batch * args.steps
     value = total_req / elapsed_max
     eager = None
-    if args.measure_eager > 0:  # stock-PyTorch engine, same process / box / protocol (not the flagship)
+    # --full: the stock-PyTorch engine, same process / protocol (not the flagship)
+    if args.full and args.measure_eager > 0:
         efwd = build_model("eager", device, args.batch, params)
         eeng = GpuEngine(efwd, device, (224, 224, 3), torch.uint8, buckets=[args.batch], inflight=args.inflight,
                          use_graphs=not args.no_graphs, name=f"eager.r{info.rank}", concurrent=not args.serial,

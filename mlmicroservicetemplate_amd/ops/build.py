@@ -52,7 +52,9 @@ def _digest(paths: List[str], extra: str = "") -> str:
     h = hashlib.sha256(extra.encode())
     for p in paths:
         with open(p, "rb") as f:
-            h.update(p.encode())
+            # the file's name, not its absolute path: a tree built in one directory and run from
+            # another (a copy, another mount point) must not recompile at its first import
+            h.update(os.path.basename(p).encode())
             h.update(f.read())
     return h.hexdigest()[:16]
 

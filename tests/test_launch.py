@@ -63,3 +63,17 @@ def test_bench_refuses_world_size_mismatch():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"],
                        env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode == 2 and "WORLD_SIZE=1" in r.stderr and r.stdout == ""
+
+
+def test_bench_plain_run_options():
+    """A plain run measures nothing but the headline figure: the same-run eager engine is behind
+    --full, and --dump-outputs is off unless a directory is given."""
+    sys.path.insert(0, ROOT)
+    try:
+        import bench
+    finally:
+        sys.path.remove(ROOT)
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.full is False and plain.dump_outputs is None and plain.steps == 7
+    full = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert full.full is True and full.dump_outputs == "out" and full.measure_eager > 0

@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd $R
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-timeout -k 10 400 python3 bench.py > $OUT/default.json 2> $OUT/default.err || { tail -20 $OUT/default.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $OUT/default.json 2> $OUT/default.err || { tail -20 $OUT/default.err; exit 1; }
 cut -c1-400 $OUT/default.json
 : > $OUT/s20.jsonl
 for r in 1 2 3 4 5; do

@@ -12,7 +12,7 @@ tail -1 $OUT/smoke.log
 for r in 1 2 3; do
   MLS_MEASURE_EAGER=0 timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 >> $OUT/s20.jsonl 2>> $OUT/s20.err || { tail -20 $OUT/s20.err; exit 1; }
 done
-timeout -k 10 400 python3 bench.py > $OUT/default.json 2> $OUT/default.err || { tail -20 $OUT/default.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $OUT/default.json 2> $OUT/default.err || { tail -20 $OUT/default.err; exit 1; }
 python3 -c "
 import json
 for l in open('$OUT/s20.jsonl'):
