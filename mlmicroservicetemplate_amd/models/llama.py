@@ -424,9 +424,17 @@ class LlamaTP:
 
     def __init__(self, params: Dict[str, torch.Tensor], cfg: LlamaConfig, tp: int = 1, rank: int = 0,
                  comm: Optional[TPComm] = None, backend: str = "reference", device="cpu", max_batch: int = 8,
-                 max_seq: int = 1024, top_k_max: int = 50, kv_pages: int = 0):
+                 max_seq: int = 1024, top_k_max: int = 50, kv_pages: int = 0, kv_dtype: str = "bf16"):
         """``kv_pages > 0``: paged KV cache -- per layer a pool of ``kv_pages`` pages of 64 rows
-        shared by all sequences (:class:`~.kv_pages.PageTable`), instead of ``max_batch x max_seq``."""
+        shared by all sequences (:class:`~.kv_pages.PageTable`), instead of ``max_batch x max_seq``.
+        ``kv_dtype="fp8"``: e4m3 KV rows with one fp32 scale per (row, KV head)
+        (``ops.reference.kv_quant_fp8``) -- 132 instead of 256 bytes per head row.  Fused backend: uint8
+        caches + scale tensors, written and read by ``ops.rope_kv_fp8_`` / ``ops.decode_attention_fp8``
+        (head-major layout, head_dim 128, Hq / Hkv in 1, 2, 4, 8 only); reference backend: the fp32
+        caches hold the round-tripped rows (the CPU oracle).  Prefill attention stays unquantised."""
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
+        self.kv_dtype = kv_dtype
         self.cfg = cfg
         self.sd = shard_dims(cfg, tp, rank)
         self.tp, self.rank = tp, rank
@@ -511,6 +519,25 @@ class LlamaTP:
         else:
             shape = (max_batch, self.sd.hkv, max_seq, D) if self.kv_hm else (max_batch, max_seq, self.sd.hkv, D)
         self.kv_hm_rows = 0 if not self.kv_hm else (self.page_rows if kv_pages > 0 else max_seq)
+        self.kv_fp8 = backend == "fused" and kv_dtype == "fp8"
+        self.k_scale: List[torch.Tensor] = []
+        self.v_scale: List[torch.Tensor] = []
+        if self.kv_fp8:
+            # the matrix-core decode kernel's own limits; no fallback to bf16 rows
+            G = self.sd.hq // max(self.sd.hkv, 1)
+            bad = [why for ok, why in (
+                (self.kv_hm, "the head-major cache layout (MLS_KV_HEAD_MAJOR=0 is set)"),
+                (D == 128, f"head_dim 128 (got {D})"),
+                (self.sd.hq % self.sd.hkv == 0 and G in (1, 2, 4, 8),
+                 f"Hq / Hkv in 1, 2, 4, 8 (got {self.sd.hq} / {self.sd.hkv})"),
+                (self.dec_chunk in (0, 64, 128), f"decode splits of 64 or 128 rows (MLS_DEC_CHUNK={self.dec_chunk})"),
+                (kv_pages > 0 or max_seq % 4 == 0, f"max_seq a multiple of 4 (got {max_seq})"),
+            ) if not ok]
+            if bad:
+                raise ValueError("kv_dtype='fp8' on the fused backend needs " + "; ".join(bad))
+            cdt = torch.uint8
+            self.k_scale = [torch.zeros(shape[:3], device=self.device, dtype=torch.float32) for _ in range(cfg.layers)]
+            self.v_scale = [torch.zeros_like(self.k_scale[0]) for _ in range(cfg.layers)]
         self.k_cache = [torch.zeros(shape, device=self.device, dtype=cdt) for _ in range(cfg.layers)]
         self.v_cache = [torch.zeros_like(self.k_cache[0]) for _ in range(cfg.layers)]
         self.cos, self.sin = R.rope_tables(max_seq, D, cfg.rope_theta, self.device)
@@ -586,13 +613,17 @@ class LlamaTP:
             valid = valid & (positions < lens.long()[b_of])
         rows = b_of if slots_b is None else slots_b.long()[b_of]  # batch row -> cache row
         bi, pi = rows[valid], positions[valid].long()
+        k_st, v_st = k[valid], v[valid]
+        if self.kv_dtype == "fp8":  # the cache holds what an e4m3 row + scale gives back (prefill stays unquantised)
+            k_st = R.kv_dequant_fp8(*R.kv_quant_fp8(k_st))
+            v_st = R.kv_dequant_fp8(*R.kv_quant_fp8(v_st))
         if self.pages is not None:  # paged: flat pool rows through the page table
             flat = self.pages.rows(bi, pi)
-            self.k_cache[i].view(-1, sd.hkv, D)[flat] = k[valid].to(self.k_cache[i].dtype)
-            self.v_cache[i].view(-1, sd.hkv, D)[flat] = v[valid].to(self.v_cache[i].dtype)
+            self.k_cache[i].view(-1, sd.hkv, D)[flat] = k_st.to(self.k_cache[i].dtype)
+            self.v_cache[i].view(-1, sd.hkv, D)[flat] = v_st.to(self.v_cache[i].dtype)
         else:
-            self.k_cache[i][bi, pi] = k[valid].to(self.k_cache[i].dtype)
-            self.v_cache[i][bi, pi] = v[valid].to(self.v_cache[i].dtype)
+            self.k_cache[i][bi, pi] = k_st.to(self.k_cache[i].dtype)
+            self.v_cache[i][bi, pi] = v_st.to(self.v_cache[i].dtype)
         if decode:
             qrow = q.reshape(B, sd.hq * D)
             if self.pages is not None:  # gather each sequence's pages back into [B, rows, hkv, D]
@@ -748,18 +779,33 @@ class LlamaTP:
             parts = None
             if decode:  # RoPE + KV append ride inside the decode-attention launch
                 kw = dict(workspace=self.dec_ws, counters=self.dec_cnt, positions=pos, cos=self.cos, sin=self.sin,
-                          max_len=self._dec_ctx, combine=not fuse_combine, head_major=self.kv_hm)
-                if self.pages is not None:
+                          max_len=self._dec_ctx, combine=not fuse_combine)
+                if self.kv_fp8:  # e4m3 cache: same partials, same consumers
+                    if self.pages is not None:
+                        a = ops.decode_attention_fp8(qkv, self.k_cache[i], self.v_cache[i], self.k_scale[i],
+                                                     self.v_scale[i], lens, sd.hq, sd.hkv, D, chunk=self.page_rows,
+                                                     page_table=self.pages.dev[:B], **kw)
+                    else:
+                        a = ops.decode_attention_fp8(qkv, self.k_cache[i][:B], self.v_cache[i][:B],
+                                                     self.k_scale[i][:B], self.v_scale[i][:B], lens, sd.hq, sd.hkv,
+                                                     D, chunk=dec_chunk, **kw)
+                elif self.pages is not None:
                     a = ops.decode_attention(qkv, self.k_cache[i], self.v_cache[i], lens, sd.hq, sd.hkv, D,
-                                             chunk=self.page_rows, page_table=self.pages.dev[:B], **kw)
+                                             chunk=self.page_rows, page_table=self.pages.dev[:B],
+                                             head_major=self.kv_hm, **kw)
                 else:
                     a = ops.decode_attention(qkv, self.k_cache[i][:B], self.v_cache[i][:B], lens, sd.hq, sd.hkv,
-                                             D, chunk=dec_chunk, **kw)
+                                             D, chunk=dec_chunk, head_major=self.kv_hm, **kw)
                 if fuse_combine:
                     a, parts = a
             else:
-                ops.rope_kv_(qkv, pos, self.cos, self.sin, sd.hq, sd.hkv, D, explicit_slots, self.k_cache[i],
-                             self.v_cache[i], lens=lens, seq=S, max_seq=self.max_seq, hm_rows=self.kv_hm_rows)
+                if self.kv_fp8:  # qkv keeps the unquantised bf16 K / V the flash attention below reads
+                    ops.rope_kv_fp8_(qkv, pos, self.cos, self.sin, sd.hq, sd.hkv, D, explicit_slots, self.k_cache[i],
+                                     self.v_cache[i], self.k_scale[i], self.v_scale[i], lens=lens, seq=S,
+                                     max_seq=self.max_seq, hm_rows=self.kv_hm_rows)
+                else:
+                    ops.rope_kv_(qkv, pos, self.cos, self.sin, sd.hq, sd.hkv, D, explicit_slots, self.k_cache[i],
+                                 self.v_cache[i], lens=lens, seq=S, max_seq=self.max_seq, hm_rows=self.kv_hm_rows)
                 a = ops.flash_attention(qkv, B, S, sd.hq, sd.hkv, D, kv_lens=lens, causal=True)
             if parts is not None:  # split-KV combine in the o-projection's prologue (one launch, not two)
                 o_w = p[f"l{i}.o"]
@@ -830,7 +876,9 @@ class LlamaTP:
         # plain cache: each half runs rope_kv_'s implicit slot mode (token t -> row (t // S) * max_seq
         # + pos) on a view of the caches starting at its first batch row -- no torch-side slot map
         # (the head-major layout groups hm_rows slots, so the offset must be a whole group)
-        implicit = explicit_slots is None and (not self.kv_hm_rows or (half * self.max_seq) % self.kv_hm_rows == 0)
+        # (the fp8 cache takes explicit slots: its scale tensors would need a second offset view)
+        implicit = (explicit_slots is None and not self.kv_fp8
+                    and (not self.kv_hm_rows or (half * self.max_seq) % self.kv_hm_rows == 0))
         if explicit_slots is None and not implicit:
             explicit_slots = ops.prefill_slots(pos, lens, B, S, max_seq=self.max_seq)
         slot_elems = sd.hkv * D  # cache elements per slot in either layout
@@ -850,6 +898,10 @@ class LlamaTP:
                     ops.rope_kv_(qkv, pos[lo:hi], self.cos, self.sin, sd.hq, sd.hkv, D, None,
                                  self.k_cache[i].reshape(-1)[off:], self.v_cache[i].reshape(-1)[off:],
                                  lens=lens[b0:b1], seq=S, max_seq=self.max_seq, hm_rows=self.kv_hm_rows)
+                elif self.kv_fp8:
+                    ops.rope_kv_fp8_(qkv, pos[lo:hi], self.cos, self.sin, sd.hq, sd.hkv, D, explicit_slots[lo:hi],
+                                     self.k_cache[i], self.v_cache[i], self.k_scale[i], self.v_scale[i],
+                                     lens=lens[b0:b1], seq=S, max_seq=self.max_seq, hm_rows=self.kv_hm_rows)
                 else:
                     ops.rope_kv_(qkv, pos[lo:hi], self.cos, self.sin, sd.hq, sd.hkv, D, explicit_slots[lo:hi],
                                  self.k_cache[i], self.v_cache[i], lens=lens[b0:b1], seq=S, max_seq=self.max_seq,

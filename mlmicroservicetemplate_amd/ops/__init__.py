@@ -97,6 +97,7 @@ from .vision import (  # noqa: F401
 from .transformer import (  # noqa: F401
     DecodePartials,
     decode_attention,
+    decode_attention_fp8,
     decode_pick,
     embed_layernorm,
     embed_layernorm_packed,
@@ -110,6 +111,7 @@ from .transformer import (  # noqa: F401
     rmsnorm,
     rope_,
     rope_kv_,
+    rope_kv_fp8_,
     skinny_packed_combine,
     skinny_packed_combine_ar,
 )

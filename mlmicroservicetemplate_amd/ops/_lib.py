@@ -91,6 +91,9 @@ _SIGS = {
     "mls_ar_destroy": [P],
     "mls_rope_kv": [P, P, P, P, L, I, I, I, I, P, P, P, P, I, I, L, I, I, P],
     "mls_kv_append": [P, I, I, I, P, P, P, L, I, I, I, P],
+    "mls_rope_kv_fp8": [P, P, P, P, L, I, I, I, I, P, P, P, P, P, P, I, I, L, I, I, P],
+    "mls_decode_attention_fp8": [P, P, P, P, P, P, P, P, P, I, I, I, P, P, P, P, I, I, I, I, I, I, I, F, P, I, I, I,
+                                 P],
     "mls_flash_attention": [P, P, P, P, I, I, I, I, I, I, I, I, I, P, I, F, P],
     "mls_flash_attention_rows": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P, I, F, P],
     "mls_skinny_gemm": [P, P, P, P, P, P, SZ, I, I, I, I, I, P],
@@ -137,12 +140,13 @@ def _bind(lib: ctypes.CDLL) -> None:
 
 
 DEBUG = os.environ.get("MLS_DEBUG", "0") == "1"
-DEBUG_TUS = ("attention", "norm_ops", "stem_pool", "conv3x3_halo")  # translation units with MLS_CHECK bounds
+DEBUG_TUS = ("attention", "norm_ops", "stem_pool", "conv3x3_halo", "kv_fp8")  # translation units with MLS_CHECK bounds
 DEBUG_CODES = {
     101: "rope/KV append: cache slot beyond the cache",
     102: "rope/KV append: position beyond the RoPE table",
     201: "decode attention: lens[b] exceeds the split grid (host context bound max_len too small)",
     202: "decode attention (rope mode): position outside the RoPE table or != lens - 1",
+    203: "decode attention (fp8 cache): page id outside the pool",
     301: "flash attention: kv_lens[b] > S",
 }
 

@@ -82,5 +82,28 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     return torch.stack(out)
 
 
+KV_FP8_MAX = 448.0          # largest finite e4m3fn value
+KV_FP8_AMAX_FLOOR = 2.0 ** -40  # keeps the scale of an all-zero row finite (and its inverse below fp32 max)
+
+
+def kv_quant_fp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The FP8 KV-cache rule, per head row ``x[..., D]`` (bf16-representable values):
+    ``scale = max(max|x|, 2^-40) / 448`` in fp32, ``q = e4m3fn_rne(x * (1 / scale))``.
+    Returns ``(uint8 [..., D], fp32 scale [...])``; every HIP writer matches this bit for bit."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    # tensor / tensor: true IEEE divisions on every device (a scalar divisor may become a multiply by
+    # its reciprocal, one ulp off the rule)
+    scale = torch.clamp(amax, min=KV_FP8_AMAX_FLOOR) / torch.full_like(amax, KV_FP8_MAX)
+    inv = torch.ones_like(scale) / scale
+    q = (xf * inv.unsqueeze(-1)).to(torch.float8_e4m3fn)
+    return q.view(torch.uint8), scale
+
+
+def kv_dequant_fp8(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """fp32 ``float(q) * scale`` of :func:`kv_quant_fp8`'s output."""
+    return q.view(torch.float8_e4m3fn).float() * scale.float().unsqueeze(-1)
+
+
 def gelu(x):
     return F.gelu(x)

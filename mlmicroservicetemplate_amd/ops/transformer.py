@@ -297,6 +297,142 @@ class DecodePartials:
         self.lens, self.n_q_heads, self.head_dim = lens, int(n_q_heads), int(head_dim)
 
 
+def _need_kv_fp8(k_cache, v_cache, k_scale, v_scale, n_kv_heads: int, head_dim: int, dev) -> None:
+    """The FP8 KV cache: head-major uint8 ``[blocks, Hkv, R, 128]`` and fp32 scales ``[blocks, Hkv, R]``."""
+    if head_dim != 128:
+        raise ValueError(f"fp8 KV cache: head_dim must be 128, got {head_dim}")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        _need(t, name, torch.uint8, dev)
+        if t.dim() != 4 or t.shape[1] != n_kv_heads or t.shape[3] != head_dim:
+            raise ValueError(f"{name}: the fp8 cache is head-major [blocks, Hkv={n_kv_heads}, rows, {head_dim}], "
+                             f"got {tuple(t.shape)}")
+    if k_cache.shape != v_cache.shape:
+        raise ValueError("k_cache and v_cache must have the same shape")
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        _need(t, name, torch.float32, dev)
+        if tuple(t.shape) != tuple(k_cache.shape[:3]):
+            raise ValueError(f"{name}: expected {tuple(k_cache.shape[:3])} (the cache's shape without its last "
+                             f"dimension), got {tuple(t.shape)}")
+
+
+def rope_kv_fp8_(qkv: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_q_heads: int,
+                 n_kv_heads: int, head_dim: int, slots: Optional[torch.Tensor], k_cache: torch.Tensor,
+                 v_cache: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                 lens: Optional[torch.Tensor] = None, seq: int = 1, max_seq: int = 0, hm_rows: int = 0):
+    """:func:`rope_kv_` writing an FP8 (e4m3) cache: RoPE on the Q and K heads in place in the bf16
+    ``qkv`` rows (bit-identical to :func:`rope_kv_`), then each token's K / V head rows quantised by
+    ``ops.reference.kv_quant_fp8``'s rule into cache slot ``slots[t]`` (or the derived slot) of the
+    head-major uint8 caches ``[blocks, Hkv, R, 128]`` and fp32 scales ``[blocks, Hkv, R]``;
+    ``hm_rows`` = R (default: the cache's)."""
+    dev = qkv.device
+    _need(qkv, "qkv", torch.bfloat16, dev)
+    _need(positions, "positions", torch.int32, dev)
+    _need_kv_fp8(k_cache, v_cache, k_scale, v_scale, n_kv_heads, head_dim, dev)
+    if slots is not None:
+        _need(slots, "slots", torch.int32, dev)
+    if lens is not None:
+        _need(lens, "lens", torch.int32, dev)
+    R = k_cache.shape[2]
+    hm_rows = int(hm_rows) or R
+    if hm_rows != R:
+        raise ValueError(f"hm_rows must be the cache's rows per block ({R}), got {hm_rows}")
+    if qkv.shape[-1] != (n_q_heads + 2 * n_kv_heads) * head_dim:
+        raise ValueError("qkv width does not match the heads")
+    T = positions.numel()
+    _need(cos, "cos", torch.float32, dev)
+    _need(sin, "sin", torch.float32, dev)
+    if cos.dim() != 2 or cos.shape[1] != head_dim // 2 or sin.shape != cos.shape:
+        raise ValueError("cos / sin must be [max_pos, D/2]")
+    if qkv.numel() < T * qkv.shape[-1] or (slots is not None and slots.numel() < T):
+        raise ValueError("qkv / slots hold fewer tokens than positions")
+    if slots is None and max_seq > 0 and (seq <= 0 or (lens is not None and lens.numel() * seq < T)):
+        raise ValueError("derived slots: lens must cover every sequence of seq tokens")
+    rc = lib().mls_rope_kv_fp8(qkv.data_ptr(), positions.data_ptr(), cos.data_ptr(), sin.data_ptr(), T, qkv.shape[-1],
+                               n_q_heads, n_kv_heads, head_dim, _ptr(slots), k_cache.data_ptr(), v_cache.data_ptr(),
+                               k_scale.data_ptr(), v_scale.data_ptr(), _ptr(lens), seq, max_seq,
+                               k_cache.shape[0] * R, cos.shape[0], hm_rows, stream_ptr(dev))
+    check(rc, "mls_rope_kv_fp8")
+    return qkv
+
+
+def decode_attention_fp8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: torch.Tensor,
+                         v_scale: torch.Tensor, lens: torch.Tensor, n_q_heads: int, n_kv_heads: int, head_dim: int, *,
+                         chunk: int = 64, scale: Optional[float] = None, workspace: Optional[torch.Tensor] = None,
+                         counters: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                         positions: Optional[torch.Tensor] = None, cos: Optional[torch.Tensor] = None,
+                         sin: Optional[torch.Tensor] = None, max_len: Optional[int] = None,
+                         page_table: Optional[torch.Tensor] = None, combine: bool = True):
+    """:func:`decode_attention` on an FP8 (e4m3) KV cache: head-major uint8 caches ``[B, Hkv, max_len,
+    128]`` (paged: ``[pages, Hkv, chunk, 128]``) with one fp32 scale per (row, KV head) in ``k_scale`` /
+    ``v_scale`` (the caches' shape without the last dimension).  The matrix-core kernel only:
+    D = 128, G = Hq / Hkv in {1, 2, 4, 8}, chunk 64 or 128 -- anything else raises ``ValueError``.
+    Rope mode quantises the new K / V row as :func:`rope_kv_fp8_` does and attends to the stored
+    (round-tripped) row, so the output is a function of the cache contents after the call.
+    Returns what :func:`decode_attention` returns (``combine=False``: ``(out, DecodePartials)``)."""
+    dev = q.device
+    if q.dtype != torch.bfloat16 or q.dim() != 2 or q.stride(1) != 1 or q.device != lens.device:
+        raise ValueError("q must be bf16 rows [B, >= Hq*D] with unit column stride, on the device of lens")
+    _need(lens, "lens", torch.int32, dev)
+    _need_kv_fp8(k_cache, v_cache, k_scale, v_scale, n_kv_heads, head_dim, dev)
+    if n_q_heads % n_kv_heads or n_q_heads // n_kv_heads not in (1, 2, 4, 8):
+        raise ValueError(f"fp8 KV cache: Hq / Hkv must be 1, 2, 4 or 8, got {n_q_heads} / {n_kv_heads}")
+    if chunk not in (64, 128):
+        raise ValueError(f"fp8 KV cache: chunk must be 64 or 128, got {chunk}")
+    B = lens.numel()
+    R = k_cache.shape[2]
+    if R % 4:
+        raise ValueError(f"fp8 KV cache: rows per block must be a multiple of 4, got {R}")
+    if q.shape[0] < B or q.shape[1] < n_q_heads * head_dim:
+        raise ValueError("q must be [B, >= Hq*D]")
+    if page_table is not None:
+        _need(page_table, "page_table", torch.int32, dev)
+        if page_table.dim() != 2 or page_table.shape[0] < B or R != chunk:
+            raise ValueError(f"paged fp8 decode: page_table [>= B, pages_per_seq], caches [pages, Hkv, chunk={chunk}, D]"
+                             f" (got pages of {R} rows)")
+        cap = page_table.shape[1] * chunk
+    else:
+        if k_cache.shape[0] < B:
+            raise ValueError("the cache holds fewer sequences than lens")
+        cap = R
+    max_len = cap if max_len is None else min(int(max_len), cap)
+    if (positions is None) != (cos is None) or (cos is None) != (sin is None):
+        raise ValueError("rope mode takes positions, cos and sin together")
+    if positions is not None:
+        _need(positions, "positions", torch.int32, dev)
+        _need(cos, "cos", torch.float32, dev)
+        _need(sin, "sin", torch.float32, dev)
+        if q.shape[1] < (n_q_heads + 2 * n_kv_heads) * head_dim:
+            raise ValueError("rope mode: q must be the fused QKV rows")
+        if positions.numel() < B or cos.dim() != 2 or cos.shape[1] != head_dim // 2 or sin.shape != cos.shape:
+            raise ValueError("rope mode: positions [B], cos / sin [max_pos, D/2]")
+    if out is not None:
+        _need(out, "out", torch.bfloat16, dev)
+        if out.dim() != 2 or out.shape[0] < B or out.shape[1] < n_q_heads * head_dim:
+            raise ValueError("out must be [>= B, >= Hq*D]")
+    nsplit = (max_len + chunk - 1) // chunk
+    need = B * n_q_heads * nsplit * (head_dim + 2)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=dev, dtype=torch.float32)
+    if counters is None or counters.numel() < B * n_kv_heads:
+        counters = torch.zeros(B * n_kv_heads, device=dev, dtype=torch.int32)
+    ws = workspace[: B * n_q_heads * nsplit * head_dim]
+    ws_ml = workspace[B * n_q_heads * nsplit * head_dim: need]
+    out = torch.empty(B, n_q_heads * head_dim, device=dev, dtype=torch.bfloat16) if out is None else out
+    scale = head_dim ** -0.5 if scale is None else scale
+    rc = lib().mls_decode_attention_fp8(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(),
+                                        v_scale.data_ptr(), out.data_ptr(), ws.data_ptr(), ws_ml.data_ptr(),
+                                        counters.data_ptr(), q.stride(0), out.stride(0), k_cache.shape[0],
+                                        lens.data_ptr(), _ptr(positions), _ptr(cos), _ptr(sin),
+                                        cos.shape[0] if cos is not None else 0, B, n_q_heads, n_kv_heads, head_dim,
+                                        max_len, chunk, float(scale), _ptr(page_table),
+                                        page_table.shape[1] if page_table is not None else 0, int(not combine), R,
+                                        stream_ptr(dev))
+    check(rc, "mls_decode_attention_fp8")
+    if not combine:
+        return out, DecodePartials(ws, ws_ml, nsplit, chunk, lens, n_q_heads, head_dim)
+    return out
+
+
 def skinny_packed_combine(attn_out: torch.Tensor, parts: DecodePartials, wp: torch.Tensor, N: int, *,
                           bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
                           variant: int = 9) -> torch.Tensor:

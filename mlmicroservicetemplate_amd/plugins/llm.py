@@ -57,13 +57,15 @@ class LlamaPlugin(ModelPlugin):
         source = llama.CheckpointSource(s.WEIGHTS, device=dev) if s.WEIGHTS else None
         params = llama.init_llama_shard(cfg, tp, ctx.rank, int(s.SEED), device=dev, source=source)
         max_batch, max_seq = int(s.MAX_BATCH) or 32, int(extra.get("max_seq", 2048))
-        kv_pages = self._kv_pages(extra.get("kv_pages", 0), cfg, tp, max_batch, max_seq, dev, backend)
+        kv_dtype = str(extra.get("kv_dtype", "bf16"))  # MODEL_CONFIG kv_dtype: bf16 | fp8 (e4m3 KV cache)
+        kv_pages = self._kv_pages(extra.get("kv_pages", 0), cfg, tp, max_batch, max_seq, dev, backend, kv_dtype)
         if tp > 1 and kv_pages:  # the scheduler replays rank 0's admissions: every pool must be equal
             from ..parallel import dist as mdist
 
             kv_pages = int(-mdist.max_over_ranks(-float(kv_pages)))
         self.model = llama.LlamaTP(params, cfg, tp=tp, rank=ctx.rank, comm=llama.TPComm(None, tp, device=dev), backend=backend,
-                                   device=dev, max_batch=max_batch, max_seq=max_seq, kv_pages=kv_pages)
+                                   device=dev, max_batch=max_batch, max_seq=max_seq, kv_pages=kv_pages,
+                                   kv_dtype=kv_dtype)
         self.tok = llama.LlamaTokenizer(cfg, extra.get("tokenizer_file"))
         self.cfg = cfg
         self.engine = None
@@ -73,10 +75,28 @@ class LlamaPlugin(ModelPlugin):
             self.engine = ContinuousLlama(self.model, max_queue=int(s.MAX_QUEUE), channel=self if tp > 1 else None)
             if ctx.rank == 0:
                 self.engine.start()
-        logger.info("llama ready: tp=%d rank=%d backend=%s device=%s", tp, ctx.rank, backend, dev)
+        logger.info("llama ready: tp=%d rank=%d backend=%s device=%s kv_dtype=%s kv_bytes_per_token=%d", tp, ctx.rank,
+                    backend, dev, kv_dtype, self.kv_page_bytes(cfg, tp, backend, kv_dtype) // 64)
 
     @staticmethod
-    def _kv_pages(spec, cfg, tp, max_batch, max_seq, dev, backend: str = "fused") -> int:
+    def kv_page_bytes(cfg, tp: int, backend: str = "fused", kv_dtype: str = "bf16") -> int:
+        """Bytes of one 64-row KV page over all layers of one rank, K and V: bf16 rows on the fused
+        backend, fp32 on the reference backend (which keeps dequantised rows, whatever ``kv_dtype``),
+        and with ``kv_dtype="fp8"`` on the fused backend one e4m3 byte per element plus one fp32
+        scale per (row, KV head)."""
+        from ..models.llama import shard_dims
+
+        hkv = shard_dims(cfg, tp, 0).hkv
+        if backend != "fused":
+            row = cfg.head_dim * 4
+        elif kv_dtype == "fp8":
+            row = cfg.head_dim + 4
+        else:
+            row = cfg.head_dim * 2
+        return cfg.layers * 2 * 64 * hkv * row
+
+    @staticmethod
+    def _kv_pages(spec, cfg, tp, max_batch, max_seq, dev, backend: str = "fused", kv_dtype: str = "bf16") -> int:
         """MODEL_CONFIG ``kv_pages``: 0 = per-slot caches (``max_batch x max_seq`` rows), N = a
         shared pool of N 64-row pages, ``auto`` = as many pages as half the free HBM holds, capped
         at what ``max_batch`` full-length sequences could use (+ the scratch page).  Under TP the
@@ -86,14 +106,16 @@ class LlamaPlugin(ModelPlugin):
         full = max_batch * -(-max_seq // 64) + 1
         if str(spec) != "auto":
             return int(spec)
-        from ..models.llama import shard_dims
-
-        elem = 2 if backend == "fused" else 4  # LlamaTP: bf16 caches when fused, fp32 for the reference backend
-        page_bytes = cfg.layers * 2 * 64 * shard_dims(cfg, tp, 0).hkv * cfg.head_dim * elem
+        page_bytes = LlamaPlugin.kv_page_bytes(cfg, tp, backend, kv_dtype)
         if torch.device(dev).type != "cuda":
             return full
         free, _total = torch.cuda.mem_get_info(torch.device(dev))
-        return max(2, min(full, int(free * 0.5) // page_bytes))
+        return LlamaPlugin.kv_pages_for(free, page_bytes, full)
+
+    @staticmethod
+    def kv_pages_for(free_bytes: int, page_bytes: int, full: int) -> int:
+        """``kv_pages: auto``: the pages half of ``free_bytes`` holds, at least 2, at most ``full``."""
+        return max(2, min(full, int(free_bytes * 0.5) // page_bytes))
 
     # ------------------------------------------------------------------ request path
     def prepare_generate(self, req: dict) -> Tuple[List[int], Any]:
