@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "chain_sched.h"
+
 typedef __bf16 bf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -156,10 +158,19 @@ MLS_DEV float block_max(float v, float* red) {
 // Bijective XCD-aware remap (cdna_hip_programming.md §5 "XCD swizzle must be bijective"):
 // blocks b, b+8, b+16 ... share an XCD; give each XCD a contiguous range of logical tiles so
 // neighbouring tiles (which share operand panels) hit the same L2.
-MLS_DEV int xcd_remap(int bid, int nwg) {
-  if (nwg <= 8) return bid;
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+// (the arithmetic lives in chain_sched.h, which also compiles for the host and is checked there)
+MLS_DEV int xcd_remap(int bid, int nwg) { return chain_logical_block(bid, nwg); }
+
+// CUs of the current device, for the grids of the persistent kernels (256 if the query fails)
+static inline int mls_num_cus() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+  }
+  return n;
 }
 
 MLS_DEV float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }

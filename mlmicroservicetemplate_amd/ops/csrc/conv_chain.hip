@@ -25,7 +25,7 @@
 //   * epilogue: t1 = relu(acc2 + b1) -> bf16 through LDS -> 16-B stores.
 // Numerics: y rounds once exactly as conv_gemm.hip's epilogue (acc + bias + res, ReLU, bf16); t1
 // accumulates the same K order in fp32.
-#include "common.h"
+#include "common.h"  // + chain_sched.h
 #include "fastdiv.h"
 
 namespace {
@@ -394,6 +394,484 @@ __global__ __launch_bounds__(512, OCC) void conv_chain_kernel(const ChainArgs a)
   }
 }
 
+// s_waitcnt vmcnt(n) for a wave-uniform n that is a constant wherever the loops unroll and a
+// two-way choice (residual or none, a block's first tile or a later one) elsewhere.  Anything above
+// the listed counts waits for everything, which is only ever stricter.
+MLS_DEV void vm_wait(int n) {
+#define MLS_VMW(k) \
+  case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
+  switch (n) {
+    MLS_VMW(1) MLS_VMW(2) MLS_VMW(3) MLS_VMW(4) MLS_VMW(5) MLS_VMW(6) MLS_VMW(7) MLS_VMW(8) MLS_VMW(9) MLS_VMW(10)
+    MLS_VMW(11) MLS_VMW(12) MLS_VMW(13) MLS_VMW(14) MLS_VMW(15) MLS_VMW(16) MLS_VMW(17) MLS_VMW(18) MLS_VMW(19)
+    MLS_VMW(20)
+    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+#undef MLS_VMW
+}
+
+// LDS accesses of the ring kernel's epilogues as inline asm.  hipcc's waitcnt pass treats an LDS-DMA
+// as a pending LDS write and puts s_waitcnt vmcnt(0) before every ds_write it can see (and before a
+// ds_read of the same address): written in C++, pass 1's in-place y write drains the whole ring in
+// every chunk, whatever the hand-placed counted wait allows (conv_chain_kernel above compiles that
+// way: its stage j + 1 has to land before chunk j's pass 1 ends).  These it does not see; a batch of
+// reads is issued, then lds_landed() ties each value to an lgkmcnt(0); the writes are retired by the
+// lgkmcnt(0) before the barrier that publishes them.
+MLS_DEV uint32_t lds_off(const void* p) { return (uint32_t)(uintptr_t)(LDS3 const char*)p; }
+// HAZARD: between lds_ld*_issue() and lds_landed() the compiler believes the register already holds
+// the value; a copy or spill of it placed there would read stale data.  Nothing orders that but
+// register allocation: a batch is issued and landed back to back with no other code between, and
+// every instantiation must keep 0 spills / 0 scratch (-Rpass-analysis=kernel-resource-usage; recheck
+// the .s when a batch grows).
+MLS_DEV uint2 lds_ld8_issue(uint32_t off) {  // the value is valid after lds_landed() on it
+  uint2 v;
+  asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"(off) : "memory");
+  return v;
+}
+MLS_DEV uint32_t lds_ld2_issue(uint32_t off) {
+  uint32_t v;
+  asm volatile("ds_read_u16 %0, %1" : "=v"(v) : "v"(off) : "memory");
+  return v;
+}
+template <typename T>
+MLS_DEV void lds_landed(T& v) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v)::"memory"); }
+MLS_DEV uint4 lds_ld16(uint32_t off) {
+  uint4 v;
+  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(off) : "memory");
+  return v;
+}
+MLS_DEV void lds_st8(uint32_t off, uint2 v) { asm volatile("ds_write_b64 %0, %1" ::"v"(off), "v"(v) : "memory"); }
+MLS_DEV void lds_st2(uint32_t off, bf16 h) {
+  const uint32_t v = __builtin_bit_cast(unsigned short, h);
+  asm volatile("ds_write_b16 %0, %1" ::"v"(off), "v"(v) : "memory");
+}
+
+// The same chain with more bytes in flight per CU: an S-deep ring (S - 1 stages in flight) and,
+// with PERS, a persistent block that walks the row tiles chain_sched.h gives it.
+//
+//   !PERS  one tile per block as above; a stage is {W3_j, W1_j, residual chunk j}.
+//   PERS   W3 and W1 are loaded into LDS once per block (NJ chunk images each, the layout of a
+//          stage's); a stage is the residual chunk alone (the y staging of the dual form, which has
+//          no residual); the A1 image is double-buffered and t1 has its own staging tile.  The ring
+//          runs on across tiles: at step (t, j) the stage of the step S - 1 later is issued, for the
+//          block's next tile once j + S - 1 >= NJ, the next tile's A1 first when that stage is its
+//          chunk 0.  Past the block's last tile the same loads are issued with every row out of
+//          range (they write nothing that is read), so the counts below hold on every tile.
+//
+// The counted wait.  vmcnt retires in issue order, so at the top of step g = (t, j) stage g has
+// landed once at most n(g) younger VMEM ops are outstanding.  A wave's order within step h is
+// [stage h + S - 1 (A1 of the next tile first)] [Y_ST y stores] [T_ST t1 stores after a tile's last
+// chunk]; stage g was issued in step g - S + 1, so the younger ops are
+//     the stages g + 1 .. g + S - 2 that exist:  n_st each (this wave's DMA pieces of one stage),
+//                                                + n_a1 if one of them is a tile's chunk 0 (PERS)
+//     the y stores of steps g - S + 1 .. g - 1:   Y_ST each; only j of them on a block's first tile
+//     the t1 stores of the previous tile (PERS):  T_ST if its last step is among those, j <= S - 2
+// !PERS: n(j) = max(0, min(S - 2, NJ - 1 - j)) * n_st + min(j, S - 1) * Y_ST   (S = 2: the kernel above)
+// PERS:  n(j) = (S - 2) * n_st + [j >= NJ - S + 2] * n_a1
+//               + (first tile ? min(j, S - 1) * Y_ST : (S - 1) * Y_ST + [j <= S - 2] * T_ST)
+// The DMA splits are strided over the waves (piece q = i * 8 + wave) and a piece type with fewer
+// than 8 pieces is issued by the first waves only, so n_st and n_a1 are per-wave values.
+template <int BM, int KS, int N1, int N2, int CW, int S, int OCC, bool SW, bool PERS>
+__global__ __launch_bounds__(512, OCC) void conv_chain_ring_kernel(const ChainArgs a, const int ntiles) {
+  constexpr int NW = 8, NT = 512, WM = 4, WN = 2;
+  constexpr int WTM = BM / WM, TM = WTM / 16;
+  constexpr int TN = CW / WN / 16;
+  constexpr int TN2 = N2 / WN / 16;
+  constexpr int CPR = CW / 8;
+  constexpr int RPP = 64 / CPR;
+  constexpr int NJ = N1 / CW;
+  constexpr int A1_BYTES = BM * KS * 128;
+  constexpr int W3_BYTES = CW * KS * 128;
+  constexpr int W1_BYTES = N2 * CW * 2;
+  constexpr int R_BYTES = BM * CW * 2;
+  constexpr int EPI_BYTES = BM * N2 * 2;
+  constexpr int STAGE = PERS ? R_BYTES : W3_BYTES + W1_BYTES + R_BYTES;
+  constexpr int OFF_W3 = (PERS ? 2 : 1) * A1_BYTES;         // PERS: resident W3, NJ chunk images
+  constexpr int OFF_W1 = OFF_W3 + (PERS ? NJ * W3_BYTES : 0);  // PERS: resident W1
+  constexpr int OFF_EPI = OFF_W1 + (PERS ? NJ * W1_BYTES : 0);  // PERS: t1 staging (!PERS: over the ring)
+  constexpr int OFF_RING = OFF_EPI + (PERS ? EPI_BYTES : 0);
+  constexpr int RING_END = OFF_RING + S * STAGE;
+  constexpr int LDS_BYTES = RING_END > EPI_BYTES ? RING_END : EPI_BYTES;
+  constexpr int A1_P = BM / 8 * KS, W3_P = CW / 8 * KS, W1_P = N2 / RPP, R_P = BM / RPP;  // 1-KiB DMA pieces
+  constexpr int Y_ST = BM * CPR / NT;
+  constexpr int T_ST = BM * N2 / 8 / NT;
+  static_assert(TM >= 1 && TN >= 1 && TN2 >= 1 && (CW == 64 || CW == 32), "tile");
+  static_assert(S >= 2 && S - 1 <= NJ && (!PERS || NJ % S == 0), "ring depth");
+  static_assert(Y_ST * NT == BM * CPR && T_ST * NT == BM * N2 / 8, "epilogue split");
+  static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+  __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wid / WN, wn = wid % WN;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int G = gridDim.x;
+  int tile = chain_first_tile(blockIdx.x, G);
+  if (tile >= ntiles) return;  // a forced grid larger than the tile count
+  int m0 = tile * BM;
+  const int K1 = a.Ka + a.Kb, KSA = a.Ka / 64;
+  const bool has_res = a.res != nullptr;
+
+  float b3v[SW ? 1 : NJ][TN], b1v[TN2];
+  if constexpr (!SW) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int jn = 0; jn < TN; ++jn) b3v[j][jn] = a.b3 ? a.b3[j * CW + wn * (CW / 2) + jn * 16 + fr] : 0.f;
+#pragma unroll
+    for (int jn = 0; jn < TN2; ++jn) b1v[jn] = a.b1 ? a.b1[wn * (N2 / 2) + jn * 16 + fr] : 0.f;
+  }
+
+  const int r8 = lane >> 3, lc = (lane & 7) ^ r8;
+  const int rq = lane / CPR, lq = (lane % CPR) ^ row_swz<CPR>(rq);
+
+  const rsrc_t a1r = make_rsrc(a.a1, a.a1_bytes);
+  const rsrc_t a2r = make_rsrc(a.a2, a.a2_bytes);
+  const rsrc_t w3r = make_rsrc(a.w3, a.w3_bytes);
+  const rsrc_t w1r = make_rsrc(a.w1, a.w1_bytes);
+  const rsrc_t rr = make_rsrc(a.res, a.res_bytes);
+  const rsrc_t yr = make_rsrc(a.y, a.y_bytes);
+  const rsrc_t tr = make_rsrc(a.t1, a.t1_bytes);
+
+  // this wave's pieces of a P-piece image: q = i * NW + wid < P
+  auto pieces = [&](int P) { return P / NW + (wid < P % NW ? 1 : 0); };
+  const int n_a1 = pieces(A1_P);
+  const int n_st = (PERS ? 0 : pieces(W3_P) + pieces(W1_P)) + (has_res ? pieces(R_P) : 0);
+
+  auto issue_a1 = [&](int mt, char* dstA) {
+#pragma unroll
+    for (int i = 0; i < (A1_P + NW - 1) / NW; ++i) {
+      const int q = i * NW + wid;
+      if (A1_P % NW != 0 && q >= A1_P) break;
+      const int s = q / (BM / 8), rb = q - s * (BM / 8);
+      const int m = mt + rb * 8 + r8;
+      char* dst = dstA + q * 1024;
+      if (s < KSA) {
+        glds16(a1r, dst, m < a.M ? (m * a.Ka + s * 64 + lc * 8) * 2 : OOB, 0);
+      } else {
+        int off = OOB;
+        if (m < a.M) {
+          const int b = fastdiv(m, a.fd_howo), rem = m - b * (a.Ho * a.Wo);
+          const int oh = fastdiv(rem, a.fd_wo), ow = rem - oh * a.Wo;
+          off = (((b * a.H2 + oh * a.stride2) * a.W2 + ow * a.stride2) * a.Kb + (s - KSA) * 64 + lc * 8) * 2;
+        }
+        glds16(a2r, dst, off, 0);
+      }
+    }
+  };
+  auto issue_w = [&](int j, char* sW3, char* sW1) {
+#pragma unroll
+    for (int i = 0; i < (W3_P + NW - 1) / NW; ++i) {
+      const int q = i * NW + wid;
+      if (W3_P % NW != 0 && q >= W3_P) break;
+      const int s = q / (CW / 8), rb = q - s * (CW / 8);
+      glds16(w3r, sW3 + q * 1024, ((j * CW + rb * 8 + r8) * K1 + s * 64 + lc * 8) * 2, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < (W1_P + NW - 1) / NW; ++i) {
+      const int q = i * NW + wid;
+      if (W1_P % NW != 0 && q >= W1_P) break;
+      glds16(w1r, sW1 + q * 1024, ((q * RPP + rq) * N1 + j * CW + lq * 8) * 2, 0);
+    }
+  };
+  auto issue_r = [&](int j, int mt, char* sR) {
+    if (!has_res) return;
+#pragma unroll
+    for (int i = 0; i < (R_P + NW - 1) / NW; ++i) {
+      const int q = i * NW + wid;
+      if (R_P % NW != 0 && q >= R_P) break;
+      const int m = mt + q * RPP + rq;
+      glds16(rr, sR + q * 1024, m < a.M ? (m * N1 + j * CW + lq * 8) * 2 : OOB, 0);
+    }
+  };
+  // chunk j's weight images and the ring slot's residual / y chunk
+  auto w3_at = [&](int j, int slot) { return smem + (PERS ? OFF_W3 + j * W3_BYTES : OFF_RING + slot * STAGE); };
+  auto w1_at = [&](int j, int slot) {
+    return smem + (PERS ? OFF_W1 + j * W1_BYTES : OFF_RING + slot * STAGE + W3_BYTES);
+  };
+  auto r_at = [&](int slot) { return smem + OFF_RING + slot * STAGE + (PERS ? 0 : W3_BYTES + W1_BYTES); };
+  auto issue_stage = [&](int j, int slot, int mt) {
+    if constexpr (!PERS) issue_w(j, w3_at(j, slot), w1_at(j, slot));
+    issue_r(j, mt, r_at(slot));
+  };
+
+  if constexpr (PERS) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) issue_w(j, w3_at(j, 0), w1_at(j, 0));
+  }
+  issue_a1(m0, smem);
+#pragma unroll
+  for (int s = 0; s < S - 1; ++s) issue_stage(s, s, m0);
+  if constexpr (PERS) {
+    // once per block: the weights, the first A1 and the first stages all landed (and the biases)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (!SW) {
+#pragma unroll
+      for (int jj = 0; jj < NJ; ++jj)
+#pragma unroll
+        for (int jn = 0; jn < TN; ++jn) asm volatile("" ::"v"(b3v[jj][jn]));
+#pragma unroll
+      for (int jn = 0; jn < TN2; ++jn) asm volatile("" ::"v"(b1v[jn]));
+    }
+  }
+
+  f32x4 acc2[TM][TN2];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int jn = 0; jn < TN2; ++jn) acc2[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  int abuf = 0;         // PERS: the A1 buffer of the current tile
+  bool first = true;    // PERS: the block's first tile (no older tile's stores in flight)
+  for (;;) {
+    int m0n = a.M;  // the block's next tile; none: every row out of range
+    if constexpr (PERS) {
+      const int next = chain_next_tile(tile, G);
+      if (next < ntiles) m0n = next * BM;
+    }
+    char* const sA1 = smem + abuf * A1_BYTES;
+
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      // ---- stage j landed (the count is derived above the kernel)
+      if constexpr (PERS) {
+        const int jm = j < S - 1 ? j : S - 1;
+        const int ahead = (S - 2) * n_st + (j >= NJ - S + 2 ? n_a1 : 0);
+        vm_wait(ahead + (first ? jm * Y_ST : (S - 1) * Y_ST + (j <= S - 2 ? T_ST : 0)));
+      } else {
+        const int left = NJ - 1 - j < S - 2 ? NJ - 1 - j : S - 2;
+        const int jm = j < S - 1 ? j : S - 1;
+        vm_wait(left * n_st + jm * Y_ST);
+        if (!SW && j == 0) {  // the biases are older still: pin their first use here
+#pragma unroll
+          for (int jj = 0; jj < NJ; ++jj)
+#pragma unroll
+            for (int jn = 0; jn < TN; ++jn) asm volatile("" ::"v"(b3v[jj][jn]));
+#pragma unroll
+          for (int jn = 0; jn < TN2; ++jn) asm volatile("" ::"v"(b1v[jn]));
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();  // every wave is done with step j - 1: its slot is free
+      {
+        const int jn = j + S - 1;  // (constants once the chunk loop is unrolled)
+        if (jn < NJ) {
+          issue_stage(jn, jn % S, m0);
+        } else if (PERS) {
+          if (jn == NJ) issue_a1(m0n, smem + (abuf ^ 1) * A1_BYTES);
+          issue_stage(jn - NJ, jn % S, m0n);
+        }
+      }
+      char* const sW3 = w3_at(j, j % S);
+      char* const sW1 = w1_at(j, j % S);
+      char* const sR = r_at(j % S);
+
+      // ---- GEMM1: acc1[BM x CW] = A1 . W3_j^T
+      f32x4 acc1[TM][TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int jn = 0; jn < TN; ++jn) acc1[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const uint4* A1s = reinterpret_cast<const uint4*>(sA1);
+      const uint4* W3s = reinterpret_cast<const uint4*>(sW3);
+#pragma unroll
+      for (int kk = 0; kk < 2 * KS; ++kk) {
+        const int s = kk >> 1, ch = fq + 4 * (kk & 1);
+        bf16x8 af[TM], bfv[TN];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          const int r = wm * WTM + i * 16 + fr;
+          af[i] = __builtin_bit_cast(bf16x8, A1s[s * BM * 8 + r * 8 + (ch ^ (r & 7))]);
+        }
+#pragma unroll
+        for (int jn = 0; jn < TN; ++jn) {
+          const int n = wn * (CW / 2) + jn * 16 + fr;
+          bfv[jn] = __builtin_bit_cast(bf16x8, W3s[s * CW * 8 + n * 8 + (ch ^ (n & 7))]);
+        }
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int jn = 0; jn < TN; ++jn)
+            acc1[i][jn] = SW ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfv[jn], af[i], acc1[i][jn], 0, 0, 0)
+                             : __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfv[jn], acc1[i][jn], 0, 0, 0);
+      }
+
+      // ---- pass 1: y = relu(acc1 + b3 (+ res)) -> bf16, in place over the residual chunk
+      auto y_at = [&](int row, int col) {  // LDS offset of y[row][col] in the slot's swizzled image
+        return lds_off(sR + row * (CW * 2) + (((col >> 3) ^ row_swz<CPR>(row)) << 4) + (col & 7) * 2);
+      };
+      if constexpr (SW) {
+        uint2 rv[TN][TM];
+        if (has_res) {
+#pragma unroll
+          for (int jn = 0; jn < TN; ++jn)
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+              rv[jn][i] = lds_ld8_issue(y_at(wm * WTM + i * 16 + fr, wn * (CW / 2) + jn * 16 + fq * 4));
+#pragma unroll
+          for (int jn = 0; jn < TN; ++jn)
+#pragma unroll
+            for (int i = 0; i < TM; ++i) lds_landed(rv[jn][i]);
+        }
+#pragma unroll
+        for (int jn = 0; jn < TN; ++jn) {
+          const int nt0 = wn * (CW / 2) + jn * 16, col = nt0 + fq * 4;  // col % 8 in {0, 4}: 8 B in one chunk
+          const f32x4 bb = bias4(a.b3, j * CW + nt0, fq);
+#pragma unroll
+          for (int i = 0; i < TM; ++i) {
+            const int row = wm * WTM + i * 16 + fr;
+            float rs[4] = {0.f, 0.f, 0.f, 0.f};
+            if (has_res) {
+              const bf16x4 r4 = __builtin_bit_cast(bf16x4, rv[jn][i]);
+#pragma unroll
+              for (int r = 0; r < 4; ++r) rs[r] = (float)r4[r];
+            }
+            bf16x4 q;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const float e = acc1[i][jn][r];  // through a named float (ext-vector element bit-cast hazard)
+              q[r] = (bf16)fmaxf(e + bb[r] + rs[r], 0.f);
+            }
+            lds_st8(y_at(row, col), __builtin_bit_cast(uint2, q));
+          }
+        }
+      } else {
+        uint32_t rv[TN][TM][4];
+        if (has_res) {
+#pragma unroll
+          for (int jn = 0; jn < TN; ++jn)
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                rv[jn][i][r] = lds_ld2_issue(y_at(wm * WTM + i * 16 + fq * 4 + r, wn * (CW / 2) + jn * 16 + fr));
+#pragma unroll
+          for (int jn = 0; jn < TN; ++jn)
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) lds_landed(rv[jn][i][r]);
+        }
+#pragma unroll
+        for (int jn = 0; jn < TN; ++jn) {
+          const int col = wn * (CW / 2) + jn * 16 + fr;
+          const float bb = b3v[j][jn];
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int row = wm * WTM + i * 16 + fq * 4 + r;
+              const float e = acc1[i][jn][r];  // through a named float (ext-vector element bit-cast hazard)
+              float v = e + bb;
+              if (has_res) v += (float)__builtin_bit_cast(bf16, (unsigned short)rv[jn][i][r]);
+              lds_st2(y_at(row, col), (bf16)fmaxf(v, 0.f));
+            }
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+
+      // ---- y chunk -> HBM, issued before GEMM2
+#pragma unroll
+      for (int it = 0; it < Y_ST; ++it) {
+        const int q = tid + it * NT;
+        const int row = q / CPR, c = q % CPR;
+        const uint4 v = lds_ld16(lds_off(sR + row * (CW * 2) + ((c ^ row_swz<CPR>(row)) << 4)));
+        const int m = m0 + row;
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), yr,
+                                               m < a.M ? (m * N1 + j * CW + c * 8) * 2 : OOB, 0, 0);
+      }
+
+      // ---- GEMM2: acc2[BM x N2] += y_j . W1_j^T
+      const uint4* Ys = reinterpret_cast<const uint4*>(sR);
+      const uint4* W1s = reinterpret_cast<const uint4*>(sW1);
+#pragma unroll
+      for (int kk = 0; kk < CW / 32; ++kk) {
+        const int ch = fq + 4 * kk;
+        bf16x8 af[TM], bfv[TN2];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          const int r = wm * WTM + i * 16 + fr;
+          af[i] = __builtin_bit_cast(bf16x8, Ys[r * CPR + (ch ^ row_swz<CPR>(r))]);
+        }
+#pragma unroll
+        for (int jn = 0; jn < TN2; ++jn) {
+          const int n = wn * (N2 / 2) + jn * 16 + fr;
+          bfv[jn] = __builtin_bit_cast(bf16x8, W1s[n * CPR + (ch ^ row_swz<CPR>(n))]);
+        }
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int jn = 0; jn < TN2; ++jn)
+            acc2[i][jn] = SW ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfv[jn], af[i], acc2[i][jn], 0, 0, 0)
+                             : __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfv[jn], acc2[i][jn], 0, 0, 0);
+      }
+    }
+
+    // ---- t1 = relu(acc2 + b1) -> bf16 tile in LDS -> 16-B stores
+    constexpr int TPR = N2 / 8;
+    bf16* to = reinterpret_cast<bf16*>(smem + (PERS ? OFF_EPI : 0));
+    if constexpr (!PERS) {  // the staging tile lies over the ring: every wave must be done reading it
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+    }
+    if constexpr (SW) {
+#pragma unroll
+      for (int jn = 0; jn < TN2; ++jn) {
+        const int nt0 = wn * (N2 / 2) + jn * 16, col = nt0 + fq * 4;
+        const f32x4 bb = bias4(a.b1, nt0, fq);
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          const int row = wm * WTM + i * 16 + fr;
+          bf16x4 q;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float e = acc2[i][jn][r];
+            q[r] = (bf16)fmaxf(e + bb[r], 0.f);
+          }
+          lds_st8(lds_off(to + row * N2 + ((((col >> 3) ^ (row & 7))) << 3) + (col & 7)), __builtin_bit_cast(uint2, q));
+        }
+      }
+    } else {
+#pragma unroll
+      for (int jn = 0; jn < TN2; ++jn) {
+        const int col = wn * (N2 / 2) + jn * 16 + fr;
+        const float bb = b1v[jn];
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = wm * WTM + i * 16 + fq * 4 + r;
+            const float e = acc2[i][jn][r];
+            lds_st2(lds_off(to + row * N2 + ((((col >> 3) ^ (row & 7))) << 3) + (col & 7)), (bf16)fmaxf(e + bb, 0.f));
+          }
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+#pragma unroll
+    for (int it = 0; it < T_ST; ++it) {
+      const int q = tid + it * NT;
+      const int row = q / TPR, c = q - (q / TPR) * TPR;
+      const uint4 v = lds_ld16(lds_off(to + row * N2 + ((c ^ (row & 7)) << 3)));
+      const int m = m0 + row;
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), tr,
+                                             m < a.M ? (m * a.N2 + c * 8) * 2 : OOB, 0, 0);
+    }
+    if constexpr (!PERS) break;
+    tile = chain_next_tile(tile, G);
+    if (tile >= ntiles) break;
+    m0 = m0n;
+    abuf ^= 1;
+    first = false;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int jn = 0; jn < TN2; ++jn) acc2[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  // the loads issued past the last tile target this block's LDS: retire them before it is released
+  if constexpr (PERS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
 // The ResNet-50 boundaries (BM = 128):          KS   N1   N2  CW
 //   layer1.0 (dual) -> layer1.1                  2   256   64  64
 //   layer1.1 -> layer1.2                         1   256   64  64
@@ -415,8 +893,50 @@ int launch_chain(const ChainArgs& a, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
+int g_chain_grid = 0;  // persistent form's block count (0 = one per CU; mls_chain_set_grid, tests)
+
+// The ring kernel's instantiations.                         BM  KS   N1   N2  CW  S   LDS
+//   layer1.0 (dual) -> layer1.1          PERS              64   2   256   64  64  2  152 KB
+//   layer2.1 -> 2.2, 2.2 -> 2.3                           128   2   512  128  64  2  128 KB
+//   layer2.3 -> layer3.0                                  128   2   512  256  32  3  128 KB
+// PERS: 64-row tiles (1568 at B = 32, 6.1 per block of a 256-block grid where 784 tiles of 128 rows
+// leave a 4-versus-3 imbalance); the grid is one block per CU, capped by the tile count.  The
+// single-slab layer1 boundaries (1, 256, 64) and (1, 256, 128) measured no faster in either form
+// (docs/PERF_NOTES.md) and stay with conv_chain_kernel under every variant.
+// Only the second row is a default.  The other two are level with 4 copies co-running, which is how
+// the engine normally runs, but faster alone (36.9 -> 29.0 us and 29.0 -> 27.5 us): they are kept
+// for one-batch-at-a-time serving (bench.py --serial, an engine with inflight = 1), which selects
+// them with MLS_CHAIN_VARIANT=2.
+template <int BM, int KS, int N1, int N2, int CW, int S, bool PERS>
+int launch_ring(const ChainArgs& a, hipStream_t st) {
+#ifdef MLS_CHAIN_SWAP
+  constexpr bool SW = MLS_CHAIN_SWAP;
+#else
+  constexpr bool SW = KS == 1;
+#endif
+  constexpr int LDS = PERS ? 2 * BM * KS * 128 + N1 * KS * 128 + N2 * N1 * 2 + BM * N2 * 2 + S * BM * CW * 2
+                            : BM * KS * 128 + S * (CW * KS * 128 + N2 * CW * 2 + BM * CW * 2);
+  constexpr int OCC = LDS <= 80 * 1024 ? 4 : 2;
+  const int ntiles = (a.M + BM - 1) / BM;
+  int grid = ntiles;
+  if (PERS) {
+    const int cus = mls_num_cus();
+    grid = g_chain_grid > 0 ? g_chain_grid : (ntiles < cus ? ntiles : cus);
+  }
+  hipLaunchKernelGGL((conv_chain_ring_kernel<BM, KS, N1, N2, CW, S, OCC, SW, PERS>), dim3((unsigned)grid), dim3(512), 0,
+                     st, a, ntiles);
+  return (int)hipGetLastError();
+}
+
 int g_chain_cw_l2 = 0;  // layer2 chunk width override (0 = default 64; mls_chain_set_l2_cw for A/B)
 int g_chain_bm_l2 = 128;  // layer2 boundaries' row tile (64: 392 blocks instead of 196 at B = 32)
+int g_chain_variant = 0;  // 0 = per-shape default, 1 = conv_chain_kernel, 2 = conv_chain_ring_kernel
+
+// Per-shape default (variant 0): the ring / persistent form where it measured faster with 4 copies
+// co-running (docs/PERF_NOTES.md, "conv_chain: deeper ring, persistent tiles").
+constexpr bool RING_L1_DUAL = false, RING_L2 = true, RING_L2_OUT = false;
+
+bool use_ring(bool shape_default) { return g_chain_variant == 2 || (g_chain_variant == 0 && shape_default); }
 
 }  // namespace
 
@@ -466,14 +986,21 @@ int mls_conv_chain(const void* a1, const void* a2, const void* w3, const float* 
   const hipStream_t st = (hipStream_t)stream;
   const int ks = (Ka + Kb) / 64;
   if (ks == 1 && N1 == 256 && N2 == 64) return launch_chain<1, 256, 64, 64>(a, st);
-  if (ks == 2 && N1 == 256 && N2 == 64) return launch_chain<2, 256, 64, 64>(a, st);
+  if (ks == 2 && N1 == 256 && N2 == 64)
+    return use_ring(RING_L1_DUAL) ? launch_ring<64, 2, 256, 64, 64, 2, true>(a, st)
+                                  : launch_chain<2, 256, 64, 64>(a, st);
   if (ks == 1 && N1 == 256 && N2 == 128) return launch_chain<1, 256, 128, 64>(a, st);
+  // the layer2 A/B overrides keep selecting conv_chain_kernel's instantiations under variant 0
+  const bool l2_override = g_chain_variant == 0 && (g_chain_bm_l2 == 64 || g_chain_cw_l2 != 0);
   if (ks == 2 && N1 == 512 && N2 == 128) {
+    if (!l2_override && use_ring(RING_L2)) return launch_ring<128, 2, 512, 128, 64, 2, false>(a, st);
     if (g_chain_bm_l2 == 64) return launch_chain<2, 512, 128, 64, 64>(a, st);
     return g_chain_cw_l2 == 32 ? launch_chain<2, 512, 128, 32>(a, st) : launch_chain<2, 512, 128, 64>(a, st);
   }
-  if (ks == 2 && N1 == 512 && N2 == 256)
+  if (ks == 2 && N1 == 512 && N2 == 256) {
+    if (!l2_override && use_ring(RING_L2_OUT)) return launch_ring<128, 2, 512, 256, 32, 3, false>(a, st);
     return g_chain_bm_l2 == 64 ? launch_chain<2, 512, 256, 64, 64>(a, st) : launch_chain<2, 512, 256, 32>(a, st);
+  }
   if (ks == 4 && N1 == 1024 && N2 == 256) return launch_chain<4, 1024, 256, 32>(a, st);
   return MLS_UNSUPPORTED;
 }
@@ -484,6 +1011,15 @@ void mls_chain_set_l2_cw(int cw) { g_chain_cw_l2 = (cw == 32 || cw == 64) ? cw :
 
 // A/B switch for the layer2 boundaries' row tile: 128 (default) or 64 (twice the blocks).
 void mls_chain_set_l2_bm(int bm) { g_chain_bm_l2 = bm == 64 ? 64 : 128; }
+
+
+// Which kernel a boundary runs: 0 = the per-shape default, 1 = conv_chain_kernel everywhere, 2 =
+// conv_chain_ring_kernel wherever it is instantiated (the dual layer1 boundary and layer2).
+void mls_chain_set_variant(int v) { g_chain_variant = (v == 1 || v == 2) ? v : 0; }
+
+// Test hook: the persistent form's block count (0 = automatic).  Any count is correct; blocks
+// beyond the tile count find no tile and leave.
+void mls_chain_set_grid(int g) { g_chain_grid = g > 0 ? g : 0; }
 
 }  // extern "C"
 

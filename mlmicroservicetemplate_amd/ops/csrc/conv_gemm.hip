@@ -901,22 +901,12 @@ void choose_cfg(int M, int N, int K, int& cfg, int& splitk) {
   while (tiles * splitk < 384 && K / (splitk * 2) >= 256 && splitk < 8) splitk *= 2;
 }
 
-int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 template <int MODE>
 void launch_persistent(int cfg, hipStream_t st, ConvArgs a) {
   set_fastdivs(a, cfg == 21 ? 64 : cfg == 22 ? 128 : 64);
   auto grid = [&](int bm, int bn, int per_cu) {
     const long T = (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn);
-    const long g = (long)num_cus() * per_cu;
+    const long g = (long)mls_num_cus() * per_cu;
     return dim3((unsigned)(T < g ? T : g));
   };
   switch (cfg) {

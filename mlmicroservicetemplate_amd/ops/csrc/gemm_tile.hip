@@ -1032,17 +1032,6 @@ GtCfg gt_cfg(int cfg) {
   }
 }
 
-int gt_num_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-        hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
 int gt_launch(const GemmTileArgs& g0, int cfg, int grid_cap, hipStream_t st) {
   const GtCfg c = gt_cfg(cfg);
   if (!c.bm) return MLS_BAD_ARG;
@@ -1052,7 +1041,7 @@ int gt_launch(const GemmTileArgs& g0, int cfg, int grid_cap, hipStream_t st) {
   // persistent grid: one resident wave of blocks (cfg 3 fits 2 per CU), each walking its tiles with
   // the LDS-DMA ring running ahead across tile boundaries
   const int per_cu = cfg == 3 ? 2 : 1;
-  int cap = grid_cap > 0 ? grid_cap : gt_num_cus() * per_cu;
+  int cap = grid_cap > 0 ? grid_cap : mls_num_cus() * per_cu;
   const int ntiles = tiles_m * g.tiles_n;
   // split-K: tile-kernel cfgs only; whole k-steps per split, room for every slab and counter
   const bool sk_ok = cfg <= 7 || cfg >= 13;
