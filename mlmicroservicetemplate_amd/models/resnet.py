@@ -36,6 +36,9 @@ STAGES: Tuple[Tuple[int, int, int, int], ...] = (
 IMAGENET_MEAN = (0.485 * 255, 0.456 * 255, 0.406 * 255)
 IMAGENET_STD = (0.229 * 255, 0.224 * 255, 0.225 * 255)
 NUM_CLASSES = 1000
+# (Kb, N1, N2) of the boundaries whose conv2 runs inside the chain kernel by default: the shapes of
+# ops.CHAIN_CONV2_SHAPES that measured a gain with 4 batches co-running (docs/PERF_NOTES.md)
+CHAIN_CONV2_DEFAULT = ((64, 256, 64), (0, 256, 64))
 
 
 @dataclass
@@ -329,6 +332,15 @@ class ResNet50Fused:
         self.chain = os.environ.get("MLS_CHAIN", "1") != "0"
         # block names whose conv3 is NOT chained (A/B: MLS_CHAIN_SKIP=layer1.2,layer2.1)
         self.chain_skip: set = {b for b in os.environ.get("MLS_CHAIN_SKIP", "").split(",") if b}
+        # ... with the block's 3x3 conv2 computed in the same kernel (ops.conv3x3_chain: t2 never goes
+        # to HBM, one launch less per block) at layer1.0 -> 1.1 and layer1.1 -> 1.2.  MLS_CHAIN_CONV2=0
+        # restores the two launches (conv2, then the chain); =2 also fuses layer1.2 -> layer2.0, which
+        # is instantiated and tested but measured level co-running (docs/PERF_NOTES.md);
+        # MLS_CHAIN_CONV2_SKIP=layer1.0,layer1.1 keeps the two launches per block (A/B)
+        mode = os.environ.get("MLS_CHAIN_CONV2", "1")
+        self.chain_conv2 = mode != "0"
+        self.chain_conv2_shapes = ops.CHAIN_CONV2_SHAPES if mode == "2" else CHAIN_CONV2_DEFAULT
+        self.chain_conv2_skip: set = {b for b in os.environ.get("MLS_CHAIN_CONV2_SKIP", "").split(",") if b}
         # layer3 boundaries (K 256, N1 1024, N2 256): instantiated and tested, off by default --
         # interleaved A/B 51.3k vs 52.2k req/s with them (profiles/r2_chain_v2_ab.jsonl)
         self.chain_l3 = os.environ.get("MLS_CHAIN_L3", "0") == "1"
@@ -433,6 +445,16 @@ class ResNet50Fused:
             return False  # layer3: 49 tiles re-reading 1 MB of weights each -- measured slower (-3 %)
         return c1.k == 1 and c1.stride == 1 and shape in self.ops.CHAIN_SHAPES
 
+    def _conv2_fused(self, p: str, nxt: str, dual: bool, t1: torch.Tensor) -> bool:
+        """Compute block ``p``'s conv2 inside its (chained) boundary kernel (ops.conv3x3_chain)?"""
+        if not self.chain_conv2 or p in self.chain_conv2_skip:
+            return False
+        c2, c3 = self.specs[p + ".conv2"], self.specs[p + ".conv3"]
+        kb = self.specs[p + ".down"].cin if dual else 0
+        shape = (kb, c3.cout, self.specs[nxt + ".conv1"].cout)
+        return (c2.k == 3 and c2.stride == 1 and c2.pad == 1 and c2.cin == 64 and c2.cout == 64
+                and shape in self.chain_conv2_shapes and t1.shape[2] <= self.ops.CHAIN_CONV2_MAX_W)
+
     def forward(self, images_u8_nhwc: torch.Tensor) -> torch.Tensor:
         """uint8 ``[B,H,W,3]`` on device -> bf16 logits ``[B, num_classes]``."""
         ops = self.ops
@@ -488,9 +510,23 @@ class ResNet50Fused:
         for idx, (si, bi) in enumerate(blocks):
             p = f"layer{si + 1}.{bi}"
             nxt = f"layer{blocks[idx + 1][0] + 1}.{blocks[idx + 1][1]}" if idx + 1 < len(blocks) else None
-            t2 = self._conv(t1, p + ".conv2", ops.ACT_RELU)
             dual = bi == 0 and self.fuse_down
-            if nxt is not None and self._chained(p, nxt, dual):
+            chained = nxt is not None and self._chained(p, nxt, dual)
+            if chained and self._conv2_fused(p, nxt, dual, t1):
+                # conv2, conv3 (+ residual / downsample) and the next block's conv1 in one kernel
+                w1n, b1n = self.w[nxt + ".conv1"], self.b[nxt + ".conv1"]
+                w1n = w1n.reshape(w1n.shape[0], -1)
+                w2, b2 = self.w[p + ".conv2"], self.b[p + ".conv2"]
+                if dual:
+                    x, t1 = ops.conv3x3_chain(t1, w2, b2, self.dual_w[p], self.dual_b[p], w1n, b1n, a2=x,
+                                              stride2=self.specs[p + ".down"].stride)
+                else:
+                    w3 = self.w[p + ".conv3"]
+                    x, t1 = ops.conv3x3_chain(t1, w2, b2, w3.reshape(w3.shape[0], -1), self.b[p + ".conv3"], w1n,
+                                              b1n, residual=x)
+                continue
+            t2 = self._conv(t1, p + ".conv2", ops.ACT_RELU)
+            if chained:
                 # this block's conv3 (+ residual / downsample) and the next block's conv1 in one
                 # kernel: the block output goes to HBM once and is never read back
                 w1n, b1n = self.w[nxt + ".conv1"], self.b[nxt + ".conv1"]

@@ -73,6 +73,8 @@ from .vision import (  # noqa: F401
     CFG_HALO_N32,
     CFG_HALO_XL,
     CFG_PIPE,
+    CHAIN_CONV2_MAX_W,
+    CHAIN_CONV2_SHAPES,
     CHAIN_SHAPES,
     HALO_CFGS,
     PIPE_CFGS,
@@ -85,6 +87,7 @@ from .vision import (  # noqa: F401
     conv2d_pool,
     conv3x3_halo,
     conv3x3_halo_geometry,
+    conv3x3_chain,
     conv3x3_pipe,
     conv3x3_pipe_geometry,
     fc_head,

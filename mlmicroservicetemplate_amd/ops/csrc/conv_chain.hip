@@ -23,6 +23,9 @@
 //       y chunk -> HBM with 16-B buffer stores
 //       GEMM2  acc2[BM x N2] += y_j . W1_j^T   (the y chunk in LDS is exactly GEMM2's K-slab j)
 //   * epilogue: t1 = relu(acc2 + b1) -> bf16 through LDS -> 16-B stores.
+//   * C2 (mls_conv_chain_conv2, the layer1 boundaries): the A1 tile's first slab is not loaded but
+//     computed, t2 = relu(conv3x3(t1_in, W2) + b2) -- the bottleneck's conv2 -- from a strip of t1_in
+//     pixels and a ring of tap weights staged over the chunk ring before GEMM1 needs it.
 // Numerics: y rounds once exactly as conv_gemm.hip's epilogue (acc + bias + res, ReLU, bf16); t1
 // accumulates the same K order in fp32.
 #include "common.h"  // + chain_sched.h
@@ -37,6 +40,13 @@ MLS_DEV void glds16(rsrc_t r, char* lds, int voff, int soff) {
 }
 
 typedef unsigned int u32x4v __attribute__((__vector_size__(16)));
+
+// LDS reads the waitcnt pass does not see (defined, with the why and the hazard, above
+// conv_chain_ring_kernel); conv_chain_kernel's conv2 producer reads its tap ring through them
+MLS_DEV uint32_t lds_off(const void* p);
+MLS_DEV u32x4v lds_ld16_issue(uint32_t off);
+template <typename T>
+MLS_DEV void lds_landed(T& v);
 
 // SW (template parameter): MFMA operand order.  true: D = W . A^T, so a lane's 4 accumulators are
 // 4 consecutive output channels of one row -- pass 1 reads the residual and writes y as one 8-B
@@ -70,6 +80,11 @@ struct ChainArgs {
   int Ho, Wo, H2, W2, stride2;  // dual geometry (M = B * Ho * Wo)
   FastDiv fd_howo, fd_wo;       // Ho * Wo, Wo (fastdiv.h)
   uint32_t a1_bytes, a2_bytes, w3_bytes, res_bytes, y_bytes, w1_bytes, t1_bytes;
+  // conv2 producer (C2): a1 is not read; slab 0 of the A1 image is relu(conv3x3(t1in, w2) + b2)
+  const bf16* t1in;  // [B][Ho][Wo][64]
+  const bf16* w2;    // [64][3][3][64]
+  const float* b2;   // [64]
+  uint32_t t1in_bytes, w2_bytes;
 };
 
 // 16-B chunk swizzle of an LDS image row: 128-B rows (8 chunks): chunk ^ (r & 7); 64-B rows (4
@@ -88,7 +103,7 @@ MLS_DEV int row_swz(int r) {
 // LDS-DMA: a plain global load consumed beside in-flight DMA makes hipcc wait vmcnt(0) and drain
 // the ring (cdna_hip_programming.md §5, "Projection GEMM" item 4(b)).  OCC = waves per SIMD the
 // register allocation must allow: 4 where the LDS footprint lets two blocks share a CU (<= 80 KB).
-template <int BM, int KS, int N1, int N2, int CW, int OCC, bool SW>
+template <int BM, int KS, int N1, int N2, int CW, int OCC, bool SW, bool C2 = false>
 __global__ __launch_bounds__(512, OCC) void conv_chain_kernel(const ChainArgs a) {
   constexpr int NW = 8, NT = 512, WM = 4, WN = 2;
   constexpr int WTM = BM / WM, TM = WTM / 16;  // GEMM1 / GEMM2 wave rows
@@ -105,6 +120,8 @@ __global__ __launch_bounds__(512, OCC) void conv_chain_kernel(const ChainArgs a)
   constexpr int RING = A1_BYTES + 2 * STAGE;
   constexpr int LDS_BYTES = RING > EPI_BYTES ? RING : EPI_BYTES;
   constexpr int A1_PW = BM / 8 * KS / NW;  // 1-KiB DMA pieces per wave
+  constexpr int A1_S0 = C2 ? 1 : 0;        // first A1 slab that is loaded (C2: slab 0 is computed)
+  constexpr int A1_PWL = BM / 8 * (KS - A1_S0) / NW;
   constexpr int W3_PW = CW / 8 * KS / NW;
   constexpr int W1_PW = N2 / RPP / NW;
   constexpr int R_PW = BM / RPP / NW;
@@ -155,8 +172,8 @@ __global__ __launch_bounds__(512, OCC) void conv_chain_kernel(const ChainArgs a)
 
   // ---- A1 tile: slab s, row block rb; wave w issues pieces q = w * A1_PW + i
 #pragma unroll
-  for (int i = 0; i < A1_PW; ++i) {
-    const int q = wid * A1_PW + i;
+  for (int i = 0; i < A1_PWL; ++i) {
+    const int q = A1_S0 * (BM / 8) + wid * A1_PWL + i;
     const int s = q / (BM / 8), rb = q - s * (BM / 8);
     const int m = m0 + rb * 8 + r8;
     char* dst = sA1 + q * 1024;
@@ -197,6 +214,135 @@ __global__ __launch_bounds__(512, OCC) void conv_chain_kernel(const ChainArgs a)
       }
     }
   };
+
+  if constexpr (C2) {
+    // ---- conv2 producer: A1 slab 0 = t2 = relu(conv3x3(t1in, W2) + b2) of the tile's BM pixels,
+    // rounded to bf16 where the separate conv2 kernel rounds it; t2 never goes to memory.
+    //   strip  the t1in pixels [m0 - (Wo + 1), m0 + BM + (Wo + 1)) of the flattened [M][64] tensor,
+    //          strip row i = pixel m0 - (Wo + 1) + i (128-B rows, the A1 chunk swizzle by row & 7):
+    //          tap (dy, dx) of tile row r is strip row r + (Wo + 1) + dy * Wo + dx.  A tap outside
+    //          the image is masked to zero; a tap inside it is a pixel of the same image, so it is
+    //          in [0, M) and inside the strip.
+    //   taps   W2[:, t, :] ([64][64], 8 KB: one 1-KiB DMA piece per wave) through a 4-slot ring, 3
+    //          taps in flight, counted vmcnt + raw s_barrier per tap.
+    // Both alias the ring (strip: stage 0, taps: stage 1), which is idle until GEMM1, so the LDS
+    // footprint is the unfused kernel's.  The a2 slabs of the dual form and the strip are issued
+    // before the taps: older, so every counted wait below covers them.
+    constexpr int TAPS = 9, TSLOTS = 4, TAHEAD = 3, SROWS = 256, TNP = 64 / WN / 16;
+    static_assert(BM == 128 && STAGE >= SROWS * 128 && STAGE >= TSLOTS * 8192, "strip / tap ring alias one stage each");
+    char* const sS = stage_base(0);
+    char* const sT = stage_base(1);
+    const rsrc_t t1r = make_rsrc(a.t1in, a.t1in_bytes);
+    const rsrc_t w2r = make_rsrc(a.w2, a.w2_bytes);
+    const int halo = a.Wo + 1;  // host: 2 * halo + BM <= SROWS
+#pragma unroll
+    for (int i = 0; i < SROWS / 8 / NW; ++i) {
+      const int q = wid * (SROWS / 8 / NW) + i;
+      const int sr = q * 8 + r8, p = m0 - halo + sr;
+      glds16(t1r, sS + q * 1024, (p >= 0 && p < a.M && sr < BM + 2 * halo) ? (p * 64 + lc * 8) * 2 : OOB, 0);
+    }
+    auto issue_tap = [&](int t) {  // rows n = wid * 8 + r8 of tap t
+      glds16(w2r, sT + (t % TSLOTS) * 8192 + wid * 1024, (((wid * 8 + r8) * TAPS + t) * 64 + lc * 8) * 2, 0);
+    };
+#pragma unroll
+    for (int t = 0; t < TAHEAD; ++t) issue_tap(t);
+
+    // bit t of okm[i]: tap t of this lane's row i lies inside the image
+    int okm[TM];
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const int m = m0 + wm * WTM + i * 16 + fr;
+      okm[i] = 0;
+      if (m < a.M) {
+        const int b = fastdiv(m, a.fd_howo), rem = m - b * (a.Ho * a.Wo);
+        const int oh = fastdiv(rem, a.fd_wo), ow = rem - oh * a.Wo;
+#pragma unroll
+        for (int t = 0; t < TAPS; ++t)
+          if ((unsigned)(oh + t / 3 - 1) < (unsigned)a.Ho && (unsigned)(ow + t % 3 - 1) < (unsigned)a.Wo)
+            okm[i] |= 1 << t;
+      }
+    }
+
+    f32x4 accp[TM][TNP];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int jn = 0; jn < TNP; ++jn) accp[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < TAPS; ++t) {
+      // tap t landed: the younger ops are the taps t + 1 .. t + TAHEAD - 1 that exist
+      if (t + 2 < TAPS) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+      else if (t + 1 < TAPS) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();  // every wave is done with tap t - 1: its slot is free
+      if (t + TAHEAD < TAPS) issue_tap(t + TAHEAD);
+      const int shift = halo + (t / 3 - 1) * a.Wo + (t % 3 - 1);
+      // asm reads: written in C++, hipcc drains the tap ring (vmcnt(0)) before the first ds_read
+      // after every issue_tap.  One batch per tap, issued and landed back to back.
+      const uint32_t oS = lds_off(sS), oT = lds_off(sT + (t % TSLOTS) * 8192);
+      u32x4v av[2][TM], bv[2][TNP];
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int ch = fq + 4 * kk;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          const int r = wm * WTM + i * 16 + fr + shift;
+          av[kk][i] = lds_ld16_issue(oS + (r * 8 + (ch ^ (r & 7))) * 16);
+        }
+#pragma unroll
+        for (int jn = 0; jn < TNP; ++jn) {
+          const int n = wn * 32 + jn * 16 + fr;
+          bv[kk][jn] = lds_ld16_issue(oT + (n * 8 + (ch ^ (n & 7))) * 16);
+        }
+      }
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) lds_landed(av[kk][i]);
+#pragma unroll
+        for (int jn = 0; jn < TNP; ++jn) lds_landed(bv[kk][jn]);
+      }
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        bf16x8 af[TM], bfv[TNP];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          u32x4v v = av[kk][i];
+          if (!((okm[i] >> t) & 1)) v = u32x4v{0u, 0u, 0u, 0u};
+          af[i] = __builtin_bit_cast(bf16x8, v);
+        }
+#pragma unroll
+        for (int jn = 0; jn < TNP; ++jn) bfv[jn] = __builtin_bit_cast(bf16x8, bv[kk][jn]);
+        // D = W . A^T: a lane's 4 accumulators are 4 consecutive channels of tile row fr
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int jn = 0; jn < TNP; ++jn)
+            accp[i][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfv[jn], af[i], accp[i][jn], 0, 0, 0);
+      }
+    }
+    // every DMA has landed (vmcnt(0) above), so the plain stores below cost no extra wait
+#pragma unroll
+    for (int jn = 0; jn < TNP; ++jn) {
+      const int nt0 = wn * 32 + jn * 16, col = nt0 + fq * 4;
+      const f32x4 bb = bias4(a.b2, nt0, fq);
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const int row = wm * WTM + i * 16 + fr;
+        bf16x4 q;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float e = accp[i][jn][r];
+          q[r] = (bf16)fmaxf(e + bb[r], 0.f);
+        }
+        *reinterpret_cast<uint2*>(sA1 + row * 128 + (((col >> 3) ^ (row & 7)) << 4) + (col & 7) * 2) =
+            __builtin_bit_cast(uint2, q);
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // every wave is done with the strip and the taps: the ring is free
+  }
   issue(0, 0);
 
   f32x4 acc2[TM][TN2];
@@ -434,6 +580,11 @@ MLS_DEV uint32_t lds_ld2_issue(uint32_t off) {
 }
 template <typename T>
 MLS_DEV void lds_landed(T& v) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v)::"memory"); }
+MLS_DEV u32x4v lds_ld16_issue(uint32_t off) {
+  u32x4v v;
+  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(off) : "memory");
+  return v;
+}
 MLS_DEV uint4 lds_ld16(uint32_t off) {
   uint4 v;
   asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(off) : "memory");
@@ -879,7 +1030,7 @@ __global__ __launch_bounds__(512, OCC) void conv_chain_ring_kernel(const ChainAr
 //   layer2.1 -> 2.2, 2.2 -> 2.3                  2   512  128  64 (or 32: 80 KB, two blocks per CU)
 //   layer2.3 -> layer3.0                         2   512  256  32
 //   layer3.1 -> 3.2 ... layer3.4 -> 3.5          4  1024  256  32
-template <int KS, int N1, int N2, int CW, int BM = 128>
+template <int KS, int N1, int N2, int CW, int BM = 128, bool C2 = false>
 int launch_chain(const ChainArgs& a, hipStream_t st) {
   constexpr int LDS = BM * KS * 128 + 2 * (CW * KS * 128 + N2 * CW * 2 + BM * CW * 2);
   constexpr int OCC = LDS <= 80 * 1024 ? 4 : 2;
@@ -888,7 +1039,7 @@ int launch_chain(const ChainArgs& a, hipStream_t st) {
 #else
   constexpr bool SW = KS == 1;
 #endif
-  hipLaunchKernelGGL((conv_chain_kernel<BM, KS, N1, N2, CW, OCC, SW>), dim3((unsigned)((a.M + BM - 1) / BM)),
+  hipLaunchKernelGGL((conv_chain_kernel<BM, KS, N1, N2, CW, OCC, SW, C2>), dim3((unsigned)((a.M + BM - 1) / BM)),
                      dim3(512), 0, st, a);
   return (int)hipGetLastError();
 }
@@ -1002,6 +1153,60 @@ int mls_conv_chain(const void* a1, const void* a2, const void* w3, const float* 
     return g_chain_bm_l2 == 64 ? launch_chain<2, 512, 256, 64, 64>(a, st) : launch_chain<2, 512, 256, 32>(a, st);
   }
   if (ks == 4 && N1 == 1024 && N2 == 256) return launch_chain<4, 1024, 256, 32>(a, st);
+  return MLS_UNSUPPORTED;
+}
+
+// mls_conv_chain with the bottleneck's conv2 in the same kernel:
+//   t2 = relu(conv3x3(t1_in, w2) + b2)   (stride 1, pad 1; never written to memory)
+//   y  = relu(conv1x1([t2 | a2 strided]) + b3 (+ res)); t1 = relu(conv1x1(y, w1) + b1).
+// t1_in [B][H][W][64], w2 [64][3][3][64] (the packed conv weight), b2 [64] or null; the rest as
+// mls_conv_chain with a1 = t2 (Ka = 64, Ho = H, Wo = W).  (KS, N1, N2) one of the layer1 boundaries
+// (1, 256, 64), (2, 256, 64), (1, 256, 128) and W <= 63 (the tile's pixel strip with its halo of
+// W + 1 on both sides is staged as 256 LDS rows); anything else MLS_UNSUPPORTED.
+int mls_conv_chain_conv2(const void* t1_in, const void* w2, const float* b2, const void* a2, const void* w3,
+                         const float* b3, const void* res, void* y, const void* w1, const float* b1, void* t1, int B,
+                         int H, int W, int Ka, int H2, int W2, int Kb, int stride2, int N1, int N2, void* stream) {
+  if (B <= 0 || H <= 0 || W <= 0 || Ka <= 0 || Kb < 0 || Kb % 64 || N1 <= 0 || N1 % 64 || N2 <= 0) return MLS_BAD_ARG;
+  if (Kb > 0 && (stride2 < 1 || (H - 1) * stride2 >= H2 || (W - 1) * stride2 >= W2 || res)) return MLS_BAD_ARG;
+  if (Ka != 64 || 2 * (W + 1) + 128 > 256) return MLS_UNSUPPORTED;
+  ChainArgs a{};
+  a.t1in = (const bf16*)t1_in;
+  a.w2 = (const bf16*)w2;
+  a.b2 = b2;
+  a.a2 = (const bf16*)a2;
+  a.w3 = (const bf16*)w3;
+  a.b3 = b3;
+  a.res = (const bf16*)res;
+  a.y = (bf16*)y;
+  a.w1 = (const bf16*)w1;
+  a.b1 = b1;
+  a.t1 = (bf16*)t1;
+  a.Ka = Ka;
+  a.Kb = Kb;
+  a.N1 = N1;
+  a.N2 = N2;
+  a.Ho = H, a.Wo = W, a.H2 = H2, a.W2 = W2, a.stride2 = stride2;
+  a.fd_howo = fastdiv_make((uint32_t)(H * W));
+  a.fd_wo = fastdiv_make((uint32_t)W);
+  const long M = (long)B * H * W;
+  const long sizes[7] = {M * Ka * 2, (long)B * H2 * W2 * Kb * 2, (long)N1 * (Ka + Kb) * 2, res ? M * N1 * 2 : 0,
+                         M * N1 * 2, (long)N2 * N1 * 2, M * N2 * 2};
+  for (long s : sizes)
+    if (s >= 0x7fffffffL) return MLS_UNSUPPORTED;
+  a.M = (int)M;
+  a.t1in_bytes = (uint32_t)sizes[0];
+  a.a2_bytes = (uint32_t)sizes[1];
+  a.w3_bytes = (uint32_t)sizes[2];
+  a.res_bytes = (uint32_t)sizes[3];
+  a.y_bytes = (uint32_t)sizes[4];
+  a.w1_bytes = (uint32_t)sizes[5];
+  a.t1_bytes = (uint32_t)sizes[6];
+  a.w2_bytes = 64 * 9 * 64 * 2;
+  const hipStream_t st = (hipStream_t)stream;
+  const int ks = (Ka + Kb) / 64;
+  if (ks == 1 && N1 == 256 && N2 == 64) return launch_chain<1, 256, 64, 64, 128, true>(a, st);
+  if (ks == 2 && N1 == 256 && N2 == 64) return launch_chain<2, 256, 64, 64, 128, true>(a, st);
+  if (ks == 1 && N1 == 256 && N2 == 128) return launch_chain<1, 256, 128, 64, 128, true>(a, st);
   return MLS_UNSUPPORTED;
 }
 

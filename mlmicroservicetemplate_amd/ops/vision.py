@@ -197,6 +197,60 @@ def conv1x1_chain(a1: torch.Tensor, w3: torch.Tensor, b3: Optional[torch.Tensor]
     return y, t1
 
 
+# (Kb of the dual operand, N1, N2) the conv2-fused chain is instantiated for: the layer1 boundaries
+CHAIN_CONV2_SHAPES = ((0, 256, 64), (64, 256, 64), (0, 256, 128))
+CHAIN_CONV2_MAX_W = 63  # the tile's pixel strip with its halo (128 + 2 * (W + 1) rows) is 256 LDS rows
+
+
+def conv3x3_chain(t1_in: torch.Tensor, w2: torch.Tensor, b2: Optional[torch.Tensor], w3: torch.Tensor,
+                  b3: Optional[torch.Tensor], w1: torch.Tensor, b1: Optional[torch.Tensor], *,
+                  residual: Optional[torch.Tensor] = None, a2: Optional[torch.Tensor] = None, stride2: int = 1,
+                  y_out: Optional[torch.Tensor] = None, t1_out: Optional[torch.Tensor] = None):
+    """A bottleneck's 3x3 conv2, its conv3 (+ residual / + downsample) and the next block's conv1 in
+    one kernel (csrc/conv_chain.hip, the C2 form):
+    ``t2 = relu(conv3x3(t1_in, w2) + b2)`` (stride 1, pad 1; rounded to bf16, never written to HBM),
+    then ``conv1x1_chain(t2, w3, b3, w1, b1, ...)``.  Returns ``(y, t1)``.
+    ``t1_in`` is ``[B,H,W,64]``, ``w2`` the packed ``[64,3,3,64]`` weight.  Supported
+    (Kb, N1, N2): CHAIN_CONV2_SHAPES with W <= CHAIN_CONV2_MAX_W -- the ResNet-50 layer1 boundaries."""
+    dev = t1_in.device
+    for name, t in (("t1_in", t1_in), ("w2", w2), ("w3", w3), ("w1", w1)):
+        _need(t, name, torch.bfloat16, dev)
+    B, H, W, C = t1_in.shape
+    N1, N2 = w3.shape[0], w1.shape[0]
+    if C != 64 or tuple(w2.shape) != (64, 3, 3, 64):
+        raise ValueError("conv3x3_chain: t1_in must be [B,H,W,64] and w2 [64,3,3,64]")
+    Ka = 64
+    if a2 is not None:
+        _need(a2, "a2", torch.bfloat16, dev)
+        if residual is not None:
+            raise ValueError("conv3x3_chain: the dual form has no residual")
+        B2, H2, W2, Kb = a2.shape
+        if B2 != B or conv_out_hw(H2, W2, 1, stride2, 0) != (H, W):
+            raise ValueError("conv3x3_chain: a2 does not match t1_in's grid at stride2")
+    else:
+        H2 = W2 = Kb = 0
+    if w3.reshape(N1, -1).shape[1] != Ka + Kb or w1.reshape(N2, -1).shape[1] != N1:
+        raise ValueError("conv3x3_chain: weight shapes do not chain")
+    if (Kb, N1, N2) not in CHAIN_CONV2_SHAPES or W > CHAIN_CONV2_MAX_W:
+        raise ValueError(f"conv3x3_chain: unsupported shape (Kb {Kb}, N1 {N1}, N2 {N2}, W {W})")
+    for name, t, n in (("b2", b2, 64), ("b3", b3, N1), ("b1", b1, N2)):
+        if t is not None:
+            _need(t, name, torch.float32, dev)
+            if t.numel() != n:
+                raise ValueError(f"{name} must have {n} elements")
+    if residual is not None:
+        _need(residual, "residual", torch.bfloat16, dev)
+        if tuple(residual.shape) != (B, H, W, N1):
+            raise ValueError("residual shape mismatch")
+    y = torch.empty(B, H, W, N1, device=dev, dtype=torch.bfloat16) if y_out is None else y_out
+    t1 = torch.empty(B, H, W, N2, device=dev, dtype=torch.bfloat16) if t1_out is None else t1_out
+    rc = lib().mls_conv_chain_conv2(t1_in.data_ptr(), w2.data_ptr(), _ptr(b2), _ptr(a2), w3.data_ptr(), _ptr(b3),
+                                    _ptr(residual), y.data_ptr(), w1.data_ptr(), _ptr(b1), t1.data_ptr(), B, H, W,
+                                    Ka, H2, W2, Kb, stride2, N1, N2, stream_ptr(dev))
+    check(rc, "mls_conv_chain_conv2")
+    return y, t1
+
+
 _MEAN_STD_CACHE = {}
 
 
