@@ -598,14 +598,16 @@ class LlamaTP:
 
     # ---------------------------------------------------------------- reference backend
     def _ref_layer(self, i: int, x: torch.Tensor, B: int, S: int, positions: torch.Tensor, lens: torch.Tensor,
-                   slots_b: torch.Tensor, decode: bool) -> torch.Tensor:
+                   slots_b: torch.Tensor, decode: bool, past: Optional[torch.Tensor] = None) -> torch.Tensor:
         cfg, sd, p = self.cfg, self.sd, self.p
         D = cfg.head_dim
         xn = R.layernorm(x, p[f"l{i}.attn_norm"], None, eps=cfg.eps, rms=True)[0]
         qkv = xn @ p[f"l{i}.qkv"].float().T
         T = qkv.shape[0]
-        q = R.rope(qkv[:, : sd.hq * D].view(T, sd.hq, D), positions, self.cos, self.sin)
-        k = R.rope(qkv[:, sd.hq * D: (sd.hq + sd.hkv) * D].view(T, sd.hkv, D), positions, self.cos, self.sin)
+        # chunked prefill: a padding row's position may lie past the RoPE table (it is never stored)
+        rpos = positions if past is None else positions.clamp(max=self.max_seq - 1)
+        q = R.rope(qkv[:, : sd.hq * D].view(T, sd.hq, D), rpos, self.cos, self.sin)
+        k = R.rope(qkv[:, sd.hq * D: (sd.hq + sd.hkv) * D].view(T, sd.hkv, D), rpos, self.cos, self.sin)
         v = qkv[:, (sd.hq + sd.hkv) * D:].view(T, sd.hkv, D)
         b_of = torch.arange(B, device=x.device).repeat_interleave(T // B)
         valid = positions < self.max_seq
@@ -634,7 +636,12 @@ class LlamaTP:
                 a = R.decode_attention(qrow, self.k_cache[i][:B], self.v_cache[i][:B], lens, sd.hq, sd.hkv, D)
         else:
             qkv_r = torch.cat([q.reshape(T, -1), k.reshape(T, -1), v.reshape(T, -1)], dim=1)
-            a = R.attention(qkv_r, B, S, sd.hq, sd.hkv, D, kv_lens=lens, causal=True)
+            if past is not None:  # chunked prefill: the chunk attends to the cache rows just written
+                table = self.pages.device_table() if self.pages is not None else None
+                a = R.attention_ctx(qkv_r, self.k_cache[i], self.v_cache[i], past, lens, B, S, sd.hq, sd.hkv, D,
+                                    slot_ids=slots_b, page_table=table)
+            else:
+                a = R.attention(qkv_r, B, S, sd.hq, sd.hkv, D, kv_lens=lens, causal=True)
         o = self.comm.all_reduce_(a @ p[f"l{i}.o"].float().T)
         x = x + o
         xn = R.layernorm(x, p[f"l{i}.mlp_norm"], None, eps=cfg.eps, rms=True)[0]
@@ -643,20 +650,23 @@ class LlamaTP:
         return x + d
 
     def _ref_forward(self, ids: torch.Tensor, positions: torch.Tensor, lens: torch.Tensor, B: int, S: int,
-                     decode: bool, k: int, slot_ids: Optional[torch.Tensor] = None):
+                     decode: bool, k: int, slot_ids: Optional[torch.Tensor] = None,
+                     past: Optional[torch.Tensor] = None):
         x = self._embed(ids.reshape(-1))
         for i in range(self.cfg.layers):
-            x = self._ref_layer(i, x, B, S, positions.reshape(-1), lens, slot_ids, decode)
+            x = self._ref_layer(i, x, B, S, positions.reshape(-1), lens, slot_ids, decode, past)
         xn = R.layernorm(x, self.p["final_norm"], None, eps=self.cfg.eps, rms=True)[0]
         if not decode:
-            last = (torch.arange(B, device=x.device) * S + lens.long() - 1)
+            n = lens.long() if past is None else lens.long() - past.long()  # valid rows of this forward
+            last = (torch.arange(B, device=x.device) * S + n - 1)
             xn = xn[last]
         logits = xn @ self.p["lm_head"].float().T
         return self._local_topk(logits, k)
 
     # ---------------------------------------------------------------- fused backend
     def _fused_forward(self, ids: torch.Tensor, positions: torch.Tensor, lens: torch.Tensor, B: int, S: int,
-                       decode: bool, k: int, slot_ids: Optional[torch.Tensor] = None):
+                       decode: bool, k: int, slot_ids: Optional[torch.Tensor] = None,
+                       past: Optional[torch.Tensor] = None):
         """Native-kernel forward.  The RMSNorm gains are folded into the following projections, so
         for decode-shaped token counts (<= 16) each pre-norm + residual add rides inside the skinny
         GEMM (``ops.gemm_rmsnorm``: 7 launches per layer); larger counts run a gain-free RMSNorm and
@@ -667,7 +677,8 @@ class LlamaTP:
         fuse = B * S <= 16
         pos = positions.reshape(-1)
         explicit_slots = None
-        if (slot_ids is not None or self.pages is not None) and not decode:
+        sid = None
+        if (slot_ids is not None or self.pages is not None or past is not None) and not decode:
             # prefill into arbitrary cache rows (continuous batching) / through the page table: one
             # native launch (ops.prefill_slots), -1 past each sequence's length
             sid = None if slot_ids is None else slot_ids.to(torch.int32)
@@ -676,6 +687,8 @@ class LlamaTP:
                                                    page_rows=self.pages.page_rows)
             else:
                 explicit_slots = ops.prefill_slots(pos, lens, B, S, sid, max_seq=self.max_seq)
+        if past is not None:  # a padding row's position may lie past the RoPE table (its slot is -1 already)
+            pos = pos.clamp(max=self.max_seq - 1)
         # decode split size: 64 rows measured best from batch 1 to 32, at TP = 1 and on an emulated
         # TP = 8 rank (one KV head).  A single 256-row split per KV head (no combine launch) was
         # 1.6 % slower at batch 1, and one 8-wave block walking a whole <= 1024 context in passes
@@ -770,7 +783,7 @@ class LlamaTP:
                              residual_out=None if d is None else x, eps=eps)
             return ops.linear(xn, w, act=act, workspace=ws), x
 
-        overlap = (not decode and self.tp > 1 and B >= 2 and T >= 64 and self.tp_overlap
+        overlap = (not decode and past is None and self.tp > 1 and B >= 2 and T >= 64 and self.tp_overlap
                    and not torch.cuda.is_current_stream_capturing())
         if overlap:
             r, delta = self._prefill_overlapped(r, pos, lens, B, S, explicit_slots, pre_norm, linear)
@@ -806,7 +819,12 @@ class LlamaTP:
                 else:
                     ops.rope_kv_(qkv, pos, self.cos, self.sin, sd.hq, sd.hkv, D, explicit_slots, self.k_cache[i],
                                  self.v_cache[i], lens=lens, seq=S, max_seq=self.max_seq, hm_rows=self.kv_hm_rows)
-                a = ops.flash_attention(qkv, B, S, sd.hq, sd.hkv, D, kv_lens=lens, causal=True)
+                if past is not None:  # chunked prefill: the chunk's queries against the cache rows just written
+                    a = ops.flash_attention_ctx(qkv, self.k_cache[i], self.v_cache[i], past, lens, B, S, sd.hq, sd.hkv,
+                                                D, slot_ids=sid,
+                                                page_table=self.pages.dev if self.pages is not None else None)
+                else:
+                    a = ops.flash_attention(qkv, B, S, sd.hq, sd.hkv, D, kv_lens=lens, causal=True)
             if parts is not None:  # split-KV combine in the o-projection's prologue (one launch, not two)
                 o_w = p[f"l{i}.o"]
                 if ar_fuse:  # ... and the all-reduce in its epilogue
@@ -841,10 +859,11 @@ class LlamaTP:
             gu, r = pre_norm(r, f"l{i}.gate_up", o, act=ops.ACT_SILU_MUL)
             delta = row_parallel(gu, f"l{i}.down")
         if not decode:  # each sequence's last valid token (one native gather of r and delta)
+            rows = lens if past is None else lens - past  # valid rows of this forward (on the device)
             if delta is None:
-                r = ops.last_rows(r, lens, B, S)
+                r = ops.last_rows(r, rows, B, S)
             else:
-                r, delta = ops.last_rows(r, lens, B, S, delta)
+                r, delta = ops.last_rows(r, rows, B, S, delta)
         if B <= 4 and "lm_head" in self.fp8 and B * r.shape[1] * 2 <= 65536:
             q, sc = self.fp8["lm_head"]
             logits = ops.skinny_fp8(r, q, sc, p["lm_head"].shape[0], delta=delta, norm=True, eps=eps)
@@ -918,13 +937,35 @@ class LlamaTP:
         return r, torch.cat(dlt)
 
     # ---------------------------------------------------------------- public
+    def check_prefill_chunk(self) -> None:
+        """Chunked prefill (``step(past=...)``) reads its context from the KV cache: raises
+        ``ValueError`` for the configurations it does not serve (nothing falls back to one shot)."""
+        if self.kv_dtype == "fp8":
+            raise ValueError("chunked prefill is not available with kv_dtype='fp8': one-shot prefill attends the "
+                             "unquantised rows, a chunk reading e4m3 context would change the numerics")
+        if self.backend == "fused":
+            if not self.kv_hm:
+                raise ValueError("chunked prefill on the fused backend needs the head-major KV cache "
+                                 "(MLS_KV_HEAD_MAJOR=0 is set)")
+            if self.cfg.head_dim != 128:
+                raise ValueError(f"chunked prefill on the fused backend needs head_dim 128 (got {self.cfg.head_dim})")
+
     @torch.no_grad()
     def step(self, ids: torch.Tensor, positions: torch.Tensor, lens: torch.Tensor, decode: bool, k: int,
-             slot_ids: Optional[torch.Tensor] = None):
+             slot_ids: Optional[torch.Tensor] = None, past: Optional[torch.Tensor] = None):
         """One forward.  ``slot_ids`` (prefill only): cache row of each batch row (default: the
-        batch row itself) -- how continuous batching prefills new requests into free slots."""
+        batch row itself) -- how continuous batching prefills new requests into free slots.
+        ``past`` (prefill only, int32 ``[B]``): rows of each sequence already in the cache -- this
+        forward is the chunk at ``positions`` ``past[b] + i`` (absolute), ``lens`` the absolute end
+        after it; its attention reads the cache (``ops.flash_attention_ctx``) and the returned
+        candidates are those of row ``lens[b] - past[b] - 1``."""
         B, S = ids.shape
         ids, positions, lens = ids.contiguous(), positions.contiguous(), lens.contiguous()
+        if past is not None:
+            if decode:
+                raise ValueError("past is a prefill argument")
+            self.check_prefill_chunk()
+            past = past.to(self.device).to(torch.int32).contiguous()
         if self.pages is not None and not (self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
             self.pages.device_table()
         if slot_ids is not None:
@@ -932,8 +973,54 @@ class LlamaTP:
         with tracing.range("llama.decode" if decode else "llama.prefill"):
             if self.backend == "fused":
                 return self._fused_forward(ids.to(torch.int32), positions.to(torch.int32), lens.to(torch.int32), B,
-                                           S, decode, k, slot_ids)
-            return self._ref_forward(ids, positions, lens, B, S, decode, k, slot_ids)
+                                           S, decode, k, slot_ids, past)
+            return self._ref_forward(ids, positions, lens, B, S, decode, k, slot_ids, past)
+
+    @torch.no_grad()
+    def prefill_chunked(self, ids: torch.Tensor, lens: torch.Tensor, chunk: int, k: int,
+                        slot_ids: Optional[torch.Tensor] = None):
+        """Prefill the prompt batch ``ids [B, S]`` (right-padded, ``lens [B]``) in chunks of ``chunk``
+        positions: chunk c is one ``step(past=c * chunk)`` over the rows whose prompt has not ended
+        (the others drop out), as wide as the longest of them needs.  Returns ``(vals, idx)``
+        ``[B, k]`` -- each row's candidates from the chunk that holds its last prompt token."""
+        chunk = int(chunk)
+        if chunk <= 0:
+            raise ValueError(f"chunk must be positive, got {chunk}")
+        self.check_prefill_chunk()
+        B, S = ids.shape
+        dev = self.device
+        lens_h = [int(x) for x in lens.detach().to("cpu").tolist()]
+        if len(lens_h) != B or min(lens_h) < 1 or max(lens_h) > min(S, self.max_seq):
+            raise ValueError(f"lens must be in [1, {min(S, self.max_seq)}] for each of the {B} sequences")
+        ids = ids.to(dev)
+        vals = idx = None
+        for s0 in range(0, max(lens_h), chunk):
+            rows = [b for b in range(B) if lens_h[b] > s0]
+            w = min(chunk, max(lens_h[b] for b in rows) - s0)
+            rt = torch.tensor(rows, dtype=torch.long, device=dev)
+            ends = torch.tensor([min(lens_h[b], s0 + w) for b in rows], dtype=torch.int32, device=dev)
+            past = torch.full((len(rows),), s0, dtype=torch.int32, device=dev)
+            pos = (s0 + torch.arange(w, dtype=torch.int32, device=dev)).unsqueeze(0).expand(len(rows), w).contiguous()
+            sid = rt.to(torch.int32) if slot_ids is None else slot_ids.to(dev)[rt].to(torch.int32)
+            v, i = self.step(ids[rt, s0: s0 + w], pos, ends, decode=False, k=k, slot_ids=sid, past=past)
+            if vals is None:
+                vals = torch.zeros((B, *v.shape[1:]), dtype=v.dtype, device=v.device)
+                idx = torch.zeros((B, *i.shape[1:]), dtype=i.dtype, device=i.device)
+            fin = [j for j, b in enumerate(rows) if lens_h[b] <= s0 + w]  # rows whose prompt ends in this chunk
+            if fin:
+                src = torch.tensor(fin, dtype=torch.long, device=v.device)
+                dst = torch.tensor([rows[j] for j in fin], dtype=torch.long, device=v.device)
+                vals[dst] = v[src]
+                idx[dst] = i[src]
+        return vals, idx
+
+    def _prefill(self, ids: torch.Tensor, lens: torch.Tensor, k: int, prefill_chunk: int):
+        """generate()'s prompt forward: one shot, or in chunks of ``prefill_chunk`` positions."""
+        if prefill_chunk > 0:
+            return self.prefill_chunked(ids, lens, prefill_chunk, k)
+        B, S = ids.shape
+        pos = torch.arange(S, device=self.device, dtype=torch.int32).unsqueeze(0).expand(B, S).contiguous()
+        return self.step(ids, pos, lens, decode=False, k=k)
 
     def gather_candidates(self, vals: torch.Tensor, idx: torch.Tensor):
         """X4 all-gather of every rank's local top-k -> ``[B, tp*k]`` values / ids (host tensors)."""
@@ -1032,9 +1119,16 @@ class LlamaTP:
             self._dec_ctx = None
 
     @torch.no_grad()
-    def generate(self, ids: torch.Tensor, lens: torch.Tensor, gp: GenParams) -> torch.Tensor:
-        """ids int ``[B, S]`` (right-padded), lens ``[B]`` -> generated ``[B, max_new_tokens]``."""
+    def generate(self, ids: torch.Tensor, lens: torch.Tensor, gp: GenParams, prefill_chunk: int = 0) -> torch.Tensor:
+        """ids int ``[B, S]`` (right-padded), lens ``[B]`` -> generated ``[B, max_new_tokens]``.
+        ``prefill_chunk = N > 0``: the prompts are prefilled N positions at a time
+        (:meth:`prefill_chunked`) instead of in one forward."""
         B, S = ids.shape
+        prefill_chunk = int(prefill_chunk)
+        if prefill_chunk < 0:
+            raise ValueError(f"prefill_chunk must be >= 0, got {prefill_chunk}")
+        if prefill_chunk:
+            self.check_prefill_chunk()
         if B > self.max_batch or S + gp.max_new_tokens > self.max_seq:
             raise ValueError("batch / sequence exceed the KV cache")
         lens_host = lens.detach().to("cpu")
@@ -1045,15 +1139,14 @@ class LlamaTP:
         lens = lens.to(dev).to(torch.int32)
         k = max(1, min(gp.top_k, self.top_k_max))
         if self._device_loop_ok(B, k):
-            return self._generate_device(ids, lens, gp, k)
+            return self._generate_device(ids, lens, gp, k, prefill_chunk)
         assigned = 0
         try:
             if self.pages is not None:  # batch row b = slot b, pages for the prompt + the generation budget
                 for b in range(B):
                     self.pages.assign(b, S + gp.max_new_tokens)
                     assigned = b + 1
-            pos = torch.arange(S, device=dev, dtype=torch.int32).unsqueeze(0).expand(B, S).contiguous()
-            vals, idx = self.step(ids, pos, lens, decode=False, k=k)
+            vals, idx = self._prefill(ids, lens, k, prefill_chunk)
             out = []
             tok = self._sample_rows(vals, idx, gp, 0)
             out.append(tok)
@@ -1252,7 +1345,8 @@ class LlamaTP:
             self._dev_graphs.clear()
             raise TPCommError("a tensor-parallel peer missed a one-shot collective; falling back to RCCL")
 
-    def _generate_device(self, ids: torch.Tensor, lens: torch.Tensor, gp: GenParams, k: int) -> torch.Tensor:
+    def _generate_device(self, ids: torch.Tensor, lens: torch.Tensor, gp: GenParams, k: int,
+                         prefill_chunk: int = 0) -> torch.Tensor:
         """generate() with every decode step a graph replay that also merges the ranks' candidates
         and picks the next token on device (X4 + P4): no host round trip until the end (and the
         comm-health check every ``health_every`` steps)."""
@@ -1269,8 +1363,7 @@ class LlamaTP:
                 for b in range(B):
                     self.pages.assign(b, S + gp.max_new_tokens)
                     assigned = b + 1
-            posp = torch.arange(S, device=dev, dtype=torch.int32).unsqueeze(0).expand(B, S).contiguous()
-            vals, idx = self.step(ids, posp, lens, decode=False, k=k)
+            vals, idx = self._prefill(ids, lens, k, prefill_chunk)
             cv, ci = self._gather_dev(vals, idx)
             pos.copy_(lens - 1)  # the pick advances them to (lens, lens + 1): the first decode position
             lens_s.copy_(lens)

@@ -15,6 +15,15 @@ With a paged KV cache (``LlamaTP(kv_pages=...)``) a request is admitted only whi
 holds its prompt + ``max_new_tokens`` rows (FIFO: the head of the queue waits for pages rather
 than being overtaken), and its pages return to the pool when it retires.
 
+Chunked prefill (``ContinuousLlama(prefill_chunk=N)``, opt-in): step 1 becomes "every sequence whose
+prompt is not yet in the cache advances by at most N positions" -- one batched
+``LlamaTP.step(..., past=rows done)`` whose attention reads the rows already written -- and a
+sequence joins step 2 in the iteration whose chunk holds its last prompt token, so decoding slots
+are never held for more than one chunk.  A slot that is still prefilling is not idle for step 2: its
+dummy decode row goes to its first unwritten row (``pos = rows done``), which the next chunk
+overwrites, never to row 0 of its live prompt.  The chunk plan is a function of the slots alone, so
+TP followers replaying rank 0's admissions compute the same chunks.
+
 Each sequence samples with its own parameters and the same seeded rule as a batch-of-one
 ``LlamaTP.generate`` (``pick_token``), so results do not depend on what else is in flight.
 
@@ -90,13 +99,23 @@ class _Seq:
     slot: int = -1
     out: List[int] = field(default_factory=list)
     cur: int = 0  # position of the next token to feed
+    done: int = 0  # chunked prefill: prompt rows already in the cache (== len(ids): decoding)
     t_submit: float = field(default_factory=time.perf_counter)
 
 
 class ContinuousLlama:
     def __init__(self, model: LlamaTP, max_queue: int = 4096,
                  broadcast: Optional[Callable[[Optional[List[_Seq]]], Optional[List[_Seq]]]] = None,
-                 channel=None):
+                 channel=None, prefill_chunk: int = 0):
+        """``prefill_chunk = N > 0`` (chunked prefill): an admitted prompt advances by at most N
+        positions per iteration, batched over all prefilling slots, and the decoding slots get their
+        step in the same iteration -- a long prompt no longer holds every decoding sequence for its
+        whole prefill.  0: each iteration prefills its admissions in one forward."""
+        self.prefill_chunk = int(prefill_chunk)
+        if self.prefill_chunk < 0:
+            raise ValueError(f"prefill_chunk must be >= 0, got {prefill_chunk}")
+        if self.prefill_chunk:
+            model.check_prefill_chunk()  # ValueError: fp8 KV cache, row-major cache, head_dim != 128
         self.m = model
         self.B = model.max_batch
         self.max_queue = max_queue
@@ -168,7 +187,8 @@ class ContinuousLlama:
 
     def stats(self) -> dict:
         d = {"active": sum(s is not None for s in self.slots), "queued": len(self._pending),
-             "iterations": self.iterations, "tokens": self.tokens, "slots": self.B}
+             "iterations": self.iterations, "tokens": self.tokens, "slots": self.B,
+             "prefilling": sum(s is not None and s.done < len(s.ids) for s in self.slots) if self.prefill_chunk else 0}
         if self.m.pages is not None:
             d["kv_pages_free"] = self.m.pages.free_pages
             d["kv_pages"] = self.m.pages.num_pages
@@ -370,9 +390,175 @@ class ContinuousLlama:
         """Admit, decode one step, retire.  Returns the retired sequences (slots already freed);
         :meth:`run_iteration` resolves their futures once the comm-health check has passed."""
         self.dev_mode = self._dev_ok()
+        if self.prefill_chunk:
+            return self._iteration_dev_chunked(admit) if self.dev_mode else self._iteration_host_chunked(admit)
         if self.dev_mode:
             return self._iteration_dev(admit)
         return self._iteration_host(admit)
+
+    # ---------------------------------------------------------------- chunked prefill (prefill_chunk > 0)
+    def _chunk_plan(self):
+        """This iteration's prefill chunk: the prefilling sequences in slot order and the chunk's
+        width -- a pure function of the slots, so every TP rank replaying rank 0's admissions
+        computes the same chunk (the headers carry nothing about it)."""
+        pre = [s for s in self.slots if s is not None and s.done < len(s.ids)]
+        w = min(self.prefill_chunk, max((len(s.ids) - s.done for s in pre), default=0))
+        return pre, w
+
+    def _chunk_inputs(self, pre: List[_Seq], w: int):
+        """Host tensors of the chunk: ids ``[n, w]`` (zero-padded) and, per row, slot / rows done /
+        absolute end after the chunk."""
+        ids = torch.zeros(len(pre), w, dtype=torch.int32)
+        for j, s in enumerate(pre):
+            part = s.ids[s.done: s.done + w]
+            ids[j, : len(part)] = torch.tensor(part, dtype=torch.int32)
+        meta = [[s.slot, s.done, min(len(s.ids), s.done + w)] for s in pre]
+        return ids, meta
+
+    @torch.no_grad()
+    def _iteration_host_chunked(self, admit: List[_Seq]) -> List[_Seq]:
+        m = self.m
+        dev = m.device
+        done: List[_Seq] = []
+        for seq in admit:
+            self.slots[seq.slot] = seq
+            seq.done = 0
+            if m.pages is not None:  # every rank assigns the same pages (same calls, same order)
+                m.pages.assign(seq.slot, len(seq.ids) + seq.gp.max_new_tokens)
+        pre, w = self._chunk_plan()
+        if pre:
+            ids, meta = self._chunk_inputs(pre, w)
+            mt = torch.tensor(meta, dtype=torch.int32, device=dev)
+            slot_ids, past, lens = mt[:, 0].contiguous(), mt[:, 1].contiguous(), mt[:, 2].contiguous()
+            pos = past.unsqueeze(1) + torch.arange(w, dtype=torch.int32, device=dev).unsqueeze(0)
+            k = max(1, min(max(s.gp.top_k for s in pre), m.top_k_max))
+            vals, idx = m.step(ids.to(dev), pos, lens, decode=False, k=k, slot_ids=slot_ids, past=past)
+            cv, ci = m.gather_candidates(vals, idx)
+            fin = [(j, s) for j, s in enumerate(pre) if s.done + w >= len(s.ids)]  # the chunk holds their last token
+            for (j, s), t in zip(fin, self._pick_rows(cv, ci, [(j, s.gp, 0) for j, s in fin])):
+                s.out.append(t)
+                s.cur = len(s.ids)
+            for s in pre:
+                s.done = min(len(s.ids), s.done + w)
+            self.tokens += len(fin)
+            done += self._retire()
+        active = [s for s in self.slots if s is not None and s.done >= len(s.ids)]
+        if active:
+            # a slot still prefilling decodes its dummy token into its first unwritten row (the next
+            # chunk overwrites it; prompt + max_new_tokens <= max_seq keeps it in bounds) -- row 0, the
+            # idle slots' dummy row, already holds its prompt
+            tok_l, cur_l = [0] * self.B, [0] * self.B
+            for s in self.slots:
+                if s is not None:
+                    tok_l[s.slot] = s.out[-1] if s.done >= len(s.ids) else 0
+                    cur_l[s.slot] = s.cur if s.done >= len(s.ids) else s.done
+            tok = torch.tensor(tok_l, dtype=torch.int32)
+            cur = torch.tensor(cur_l, dtype=torch.int32)
+            k = max(1, min(max(s.gp.top_k for s in active), m.top_k_max))
+            max_ctx = max(cur_l) + 1  # covers the prefilling slots' lens = rows done + 1 too
+            vals, idx = m.decode_step(tok.to(dev), cur.to(dev), k, max_ctx=max_ctx)
+            cv, ci = m.gather_candidates(vals, idx)
+            picks = self._pick_rows(cv, ci, [(s.slot, s.gp, len(s.out)) for s in active])
+            for s, t in zip(active, picks):
+                s.out.append(t)
+                s.cur += 1
+            self.tokens += len(active)
+            done += self._retire()
+        self.iterations += 1
+        return done
+
+    @torch.no_grad()
+    def _iteration_dev_chunked(self, admit: List[_Seq]) -> List[_Seq]:
+        m = self.m
+        dev = m.device
+        st = m.serve_state(self.B)
+        ops = m.ops
+        for seq in admit:
+            self.slots[seq.slot] = seq
+            seq.done = 0
+            if m.pages is not None:
+                m.pages.assign(seq.slot, len(seq.ids) + seq.gp.max_new_tokens)
+        pre, w = self._chunk_plan()
+        fin: List[_Seq] = []
+        if pre:
+            ids, meta = self._chunk_inputs(pre, w)
+            fin_j = [j for j, s in enumerate(pre) if s.done + w >= len(s.ids)]
+            fin = [pre[j] for j in fin_j]
+            # one H2D of the chunk and of the slots' state after it: a sequence whose prompt ends here
+            # becomes active at (pos, lens) = (len - 1, len), which the pick advances; one still
+            # prefilling stays inactive with its dummy decode row at its first unwritten row
+            # (pos = rows done, lens = rows done + 1)
+            for row, s in zip(meta, pre):
+                last = row[2] >= len(s.ids)
+                row += [row[2] - 1 if last else row[2], row[2] if last else row[2] + 1, int(last), s.gp.top_k, s.gp.seed]
+            mt = torch.tensor(meta, dtype=torch.int64).to(dev, non_blocking=True)
+            temps = torch.tensor([s.gp.temperature for s in pre], dtype=torch.float32).to(dev, non_blocking=True)
+            slot_ids = mt[:, 0].to(torch.int32)
+            past = mt[:, 1].to(torch.int32)
+            lens = mt[:, 2].to(torch.int32)
+            pos = past.unsqueeze(1) + torch.arange(w, dtype=torch.int32, device=dev).unsqueeze(0)
+            k = max(1, min(max(s.gp.top_k for s in pre), m.top_k_max))
+            vals, idx = m.step(ids.to(dev), pos, lens, decode=False, k=k, slot_ids=slot_ids, past=past)
+            sl = mt[:, 0]
+            st["pos"][sl] = mt[:, 3].to(torch.int32)
+            st["lens"][sl] = mt[:, 4].to(torch.int32)
+            st["active"][sl] = mt[:, 5].to(torch.int32)
+            st["step"][sl] = 0
+            st["topk"][sl] = mt[:, 6].to(torch.int32)
+            st["seed"][sl] = mt[:, 7]
+            st["temp"][sl] = temps
+            if fin:
+                cv, ci = m._gather_dev(vals, idx)
+                fj = torch.tensor(fin_j, dtype=torch.int64).to(dev, non_blocking=True)
+                ops.decode_pick(cv[:, fj].contiguous(), ci[:, fj].contiguous(), st["tok"], st["pos"], st["lens"],
+                                st["step"], topk=st["topk"], temp=st["temp"], seed=st["seed"],
+                                rows=slot_ids[fj].contiguous(), emit=st["E"][0])
+            for s in pre:
+                s.done = min(len(s.ids), s.done + w)
+            for s in fin:
+                s.cur = len(s.ids)
+        active = [s for s in self.slots if s is not None and s.done >= len(s.ids)]
+        carry = self._carry and m.tp > 1
+        if active:
+            k = max(1, min(max(s.gp.top_k for s in active), m.top_k_max))
+            # the bound covers the prefilling slots' dummy rows (lens = rows done + 1) too
+            max_ctx = max(s.cur if s.done >= len(s.ids) else s.done for s in self.slots if s is not None) + 1
+            g = m.serve_graph(self.B, k, m.ctx_bucket(max_ctx))
+            if m.pages is not None:
+                m.pages.device_table()  # the graph reads the table buffer in place
+            if carry and self.leader:
+                self._plan_next(st)  # the next iteration's header rides this step's gather
+            g.replay()
+        done: List[_Seq] = []
+        if fin or active:
+            E_all = st["E_all"].cpu()  # the iteration's one device -> host copy
+            self.host_reads += 1
+            E = E_all[: 2 * self.B].view(2, self.B)
+            e0, e1 = E[0].tolist(), E[1].tolist()
+            if active and carry:
+                c = E_all[2 * self.B:].tolist()
+                ok = c[3] == ctl_check(self.iterations, c[0], c[1], c[2]) and c[0] in (OP_STOP, OP_ITER)
+                self._carry_check = (not ok) or c[4] != 0 or c[1] > 0  # as _iteration_dev
+                self._ctl_bad = None if ok else c[:4]
+                self._next_hdr = (c[0], c[1], c[2]) if ok else None
+            new = {id(s) for s in fin}
+            for s in fin:
+                s.out.append(int(e0[s.slot]))
+                self.tokens += 1
+            for s in active:
+                if id(s) in new and (len(s.out) >= s.gp.max_new_tokens or s.out[-1] in self.eos):
+                    continue  # finished on its prefill token: the decode pick is discarded
+                s.out.append(int(e1[s.slot]))
+                s.cur += 1
+                self.tokens += 1
+            done = self._retire()
+            if done:
+                idx_t = torch.tensor([q.slot for q in done], dtype=torch.int64).to(dev, non_blocking=True)
+                st["active"][idx_t] = 0
+                st["pos"][idx_t] = 0
+                st["lens"][idx_t] = 1
+        self.iterations += 1
+        return done
 
     @torch.no_grad()
     def _iteration_dev(self, admit: List[_Seq]) -> List[_Seq]:
@@ -524,7 +710,7 @@ class ContinuousLlama:
         """Free the slots of finished sequences (their futures are resolved by run_iteration)."""
         done = []
         for i, s in enumerate(self.slots):
-            if s is None:
+            if s is None or (self.prefill_chunk and s.done < len(s.ids)):  # still prefilling: nothing to retire
                 continue
             if len(s.out) >= s.gp.max_new_tokens or (s.out and s.out[-1] in self.eos):
                 self.slots[i] = None

@@ -82,6 +82,41 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     return torch.stack(out)
 
 
+def attention_ctx(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, past: torch.Tensor,
+                  lens: torch.Tensor, B: int, S: int, Hq: int, Hkv: int, D: int,
+                  slot_ids: Optional[torch.Tensor] = None, page_table: Optional[torch.Tensor] = None,
+                  scale: Optional[float] = None, head_major: bool = False) -> torch.Tensor:
+    """Chunked-prefill attention against the KV cache (the oracle of ``ops.flash_attention_ctx``):
+    query ``i`` of batch row ``b`` (``i < lens[b] - past[b]``, read from the chunk's RoPE'd fused
+    ``qkv [B*S, (Hq+2Hkv)*D]``) sits at position ``past[b] + i`` and attends to cache rows
+    ``0 .. past[b] + i`` of slot ``slot_ids[b]`` (``b`` when None).  Caches ``[slots, rows, Hkv, D]``
+    (``head_major``: ``[slots, Hkv, rows, D]``), or page pools of the same two layouts addressed
+    through ``page_table [slots, pages_per_seq]``.  Returns fp32 ``[B*S, Hq*D]``; rows at or past a
+    row's valid length are zero."""
+    scale = D ** -0.5 if scale is None else scale
+    q = qkv[:, : Hq * D].float().view(B, S, Hq, D)
+    out = torch.zeros(B, S, Hq, D, dtype=torch.float32, device=qkv.device)
+    rep = Hq // Hkv
+    for b in range(B):
+        P, L = int(past[b]), int(lens[b])
+        n = min(L - P, S)
+        if n <= 0:
+            continue
+        slot = b if slot_ids is None else int(slot_ids[b])
+        kv = []
+        for c in (k_cache, v_cache):  # this slot's rows [rows, Hkv, D], through the table when paged
+            blk = c[page_table[slot].long()] if page_table is not None else c[slot: slot + 1]
+            if head_major:
+                blk = blk.transpose(1, 2)
+            kv.append(blk.reshape(-1, Hkv, D)[:L].float().repeat_interleave(rep, dim=1))
+        s = torch.einsum("qhd,lhd->hql", q[b, :n], kv[0]) * scale
+        pos = P + torch.arange(n, device=qkv.device)
+        hidden = torch.arange(L, device=qkv.device).view(1, L) > pos.view(n, 1)
+        p = torch.softmax(s.masked_fill(hidden.unsqueeze(0), float("-inf")), dim=-1)
+        out[b, :n] = torch.einsum("hql,lhd->qhd", p, kv[1])
+    return out.reshape(B * S, Hq * D)
+
+
 KV_FP8_MAX = 448.0          # largest finite e4m3fn value
 KV_FP8_AMAX_FLOOR = 2.0 ** -40  # keeps the scale of an all-zero row finite (and its inverse below fp32 max)
 

@@ -225,6 +225,71 @@ def flash_attention_rows(q: torch.Tensor, kv: torch.Tensor, batch: int, seq: int
     return out
 
 
+def flash_attention_ctx(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, past: torch.Tensor,
+                        lens: torch.Tensor, batch: int, seq: int, n_q_heads: int, n_kv_heads: int, head_dim: int, *,
+                        slot_ids: Optional[torch.Tensor] = None, page_table: Optional[torch.Tensor] = None,
+                        scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Chunked-prefill attention: a chunk of ``seq`` new queries per batch row against the KV cache.
+    Query ``i`` of row ``b`` (``i < lens[b] - past[b]``) sits at position ``past[b] + i`` and attends to
+    cache rows ``0 .. past[b] + i`` of slot ``slot_ids[b]`` (``b`` when None).  Q is read in place from
+    the chunk's fused, RoPE'd ``qkv [B*S, (Hq+2Hkv)*D]``; K / V come only from the cache, so the chunk's
+    own rows must have been appended first (:func:`rope_kv_`).  ``past`` / ``lens`` (the absolute end
+    after this chunk, as :func:`prefill_slots` takes it) / ``slot_ids`` are int32 ``[B]`` on the device;
+    nothing is read on the host (capturable).  Head-major bf16 caches only, D = 128:
+    ``[slots, Hkv, max_seq, D]``, or page pools ``[pages, Hkv, 64, D]`` through ``page_table
+    [slots, pages_per_seq]``.  Returns ``[B*S, Hq*D]``; rows at or past a row's valid length are
+    unspecified."""
+    dev = qkv.device
+    _need(qkv, "qkv", torch.bfloat16, dev)
+    _need(k_cache, "k_cache", torch.bfloat16, dev)
+    _need(v_cache, "v_cache", torch.bfloat16, dev)
+    _need(past, "past", torch.int32, dev)
+    _need(lens, "lens", torch.int32, dev)
+    if batch <= 0 or seq <= 0 or n_kv_heads <= 0 or n_q_heads % n_kv_heads:
+        raise ValueError("batch, seq > 0 and Hq a multiple of Hkv")
+    if head_dim != 128:
+        raise ValueError(f"flash_attention_ctx: head_dim must be 128, got {head_dim}")
+    W = (n_q_heads + 2 * n_kv_heads) * head_dim
+    if qkv.dim() != 2 or tuple(qkv.shape) != (batch * seq, W):
+        raise ValueError("qkv shape does not match batch/seq/heads")
+    if past.numel() != batch or lens.numel() != batch:
+        raise ValueError(f"past and lens must have {batch} elements")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
+        raise ValueError("k_cache and v_cache must be 4-d and of the same shape")
+    if k_cache.shape[1] != n_kv_heads or k_cache.shape[3] != head_dim:
+        raise ValueError(f"flash_attention_ctx reads head-major caches [blocks, Hkv={n_kv_heads}, rows, {head_dim}] "
+                         f"only (a row-major cache is not supported), got {tuple(k_cache.shape)}")
+    blocks, rows = k_cache.shape[0], k_cache.shape[2]
+    if slot_ids is not None:
+        _need(slot_ids, "slot_ids", torch.int32, dev)
+        if slot_ids.numel() != batch:
+            raise ValueError(f"slot_ids must have {batch} elements")
+    if page_table is not None:
+        _need(page_table, "page_table", torch.int32, dev)
+        if page_table.dim() != 2:
+            raise ValueError("page_table must be [slots, pages_per_seq]")
+        if rows != 64:
+            raise ValueError(f"paged flash_attention_ctx: pages of 64 rows (one K/V tile), got {rows}")
+        slots, pps = page_table.shape
+    else:
+        slots, pps = blocks, 0
+    if slot_ids is None and batch > slots:
+        raise ValueError("the cache holds fewer slots than the batch")
+    if out is not None:
+        _need(out, "out", torch.bfloat16, dev)
+        if out.dim() != 2 or out.shape[0] < batch * seq or out.shape[1] != n_q_heads * head_dim:
+            raise ValueError("out must be [B*S, Hq*D]")
+    else:
+        out = torch.empty(batch * seq, n_q_heads * head_dim, device=dev, dtype=torch.bfloat16)
+    scale = head_dim ** -0.5 if scale is None else scale
+    rc = lib().mls_flash_attention_ctx(qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), W,
+                                       out.stride(0), past.data_ptr(), lens.data_ptr(), _ptr(slot_ids),
+                                       _ptr(page_table), pps, slots, batch, seq, n_q_heads, n_kv_heads, head_dim,
+                                       blocks, rows, float(scale), stream_ptr(dev))
+    check(rc, "mls_flash_attention_ctx")
+    return out
+
+
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, lens: torch.Tensor,
                      n_q_heads: int, n_kv_heads: int, head_dim: int, *, chunk: int = 64,
                      scale: Optional[float] = None, workspace: Optional[torch.Tensor] = None,

@@ -36,6 +36,7 @@ class LlamaPlugin(ModelPlugin):
         self.tok = None
         self.ctx = None
         self.comm_dev = None
+        self.prefill_chunk = 0
         self._lock = threading.Lock()
 
     def init(self, ctx: PluginContext) -> None:
@@ -58,6 +59,13 @@ class LlamaPlugin(ModelPlugin):
         params = llama.init_llama_shard(cfg, tp, ctx.rank, int(s.SEED), device=dev, source=source)
         max_batch, max_seq = int(s.MAX_BATCH) or 32, int(extra.get("max_seq", 2048))
         kv_dtype = str(extra.get("kv_dtype", "bf16"))  # MODEL_CONFIG kv_dtype: bf16 | fp8 (e4m3 KV cache)
+        # MODEL_CONFIG prefill_chunk: N > 0 = chunked prefill, N prompt positions per serving iteration
+        self.prefill_chunk = int(extra.get("prefill_chunk", 0) or 0)
+        if self.prefill_chunk < 0:
+            raise ValueError(f"prefill_chunk must be >= 0, got {self.prefill_chunk}")
+        if self.prefill_chunk and kv_dtype == "fp8":  # LlamaTP.check_prefill_chunk's rule
+            raise ValueError("prefill_chunk is not available with kv_dtype: fp8 (a chunk would attend e4m3 context "
+                             "rows where one-shot prefill attends unquantised ones)")
         kv_pages = self._kv_pages(extra.get("kv_pages", 0), cfg, tp, max_batch, max_seq, dev, backend, kv_dtype)
         if tp > 1 and kv_pages:  # the scheduler replays rank 0's admissions: every pool must be equal
             from ..parallel import dist as mdist
@@ -72,7 +80,8 @@ class LlamaPlugin(ModelPlugin):
         if bool(getattr(s, "CONTINUOUS_BATCHING", True)):
             from ..models.llama_serving import ContinuousLlama
 
-            self.engine = ContinuousLlama(self.model, max_queue=int(s.MAX_QUEUE), channel=self if tp > 1 else None)
+            self.engine = ContinuousLlama(self.model, max_queue=int(s.MAX_QUEUE), channel=self if tp > 1 else None,
+                                          prefill_chunk=self.prefill_chunk)
             if ctx.rank == 0:
                 self.engine.start()
         logger.info("llama ready: tp=%d rank=%d backend=%s device=%s kv_dtype=%s kv_bytes_per_token=%d", tp, ctx.rank,
@@ -204,7 +213,7 @@ class LlamaPlugin(ModelPlugin):
         lens = torch.tensor([len(t) for t in ids_l], dtype=torch.int32)
         with self._lock:
             self._broadcast_cmd(OP_GENERATE, ids, lens, gp)
-            out = self.model.generate(ids, lens, gp)
+            out = self.model.generate(ids, lens, gp, prefill_chunk=self.prefill_chunk)
         return out.cpu().tolist()
 
     # ---- the continuous engine's TP control channel (models/llama_serving.py ContinuousLlama):
@@ -319,7 +328,8 @@ class LlamaPlugin(ModelPlugin):
             lens = torch.zeros(B, dtype=torch.int32, device=self.comm_dev)
             dist.broadcast(ids, src=0)
             dist.broadcast(lens, src=0)
-            self.model.generate(ids, lens, GenParams(mnt, topk, temp / 1000.0, seed))
+            self.model.generate(ids, lens, GenParams(mnt, topk, temp / 1000.0, seed),
+                                prefill_chunk=self.prefill_chunk)
 
     def close(self) -> None:
         if self.engine is not None and self.ctx.rank == 0:

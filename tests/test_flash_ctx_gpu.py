@@ -1,0 +1,317 @@
+"""Chunked-prefill attention on the GPU (ops/csrc/flash_ctx.hip, ``ops.flash_attention_ctx``): a chunk
+of queries at positions ``[past, past + n)`` against the KV cache, per-slot and paged, vs the fp32 oracle
+``ops.reference.attention_ctx`` on the same bf16 cache contents; and the fused ``LlamaTP`` /
+``ContinuousLlama`` running their prompts in chunks vs in one shot.
+
+Tolerances: 2e-2 of the largest output magnitude for the kernel (the bound ``test_flash_attention`` holds
+the kernel it derives from to: P is rounded to bf16 before the PV product), 3e-2 for the model's top-k
+values against the reference backend (``test_e2e_gpu.py``'s bound for the Llama cut)."""
+import pytest
+import torch
+
+from mlmicroservicetemplate_amd.ops import reference as R
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+D = 128
+MAX_SEQ = 333  # not a multiple of the 64-key tile: the last tile of a slot ends inside its rows
+PASTS = [0, 1, 63, 64, 65, 200]  # ragged within one batch; 200 + 130 <= MAX_SEQ
+
+
+def rel(a, b):
+    return ((a.float() - b.float()).abs().max() / (b.float().abs().max() + 1e-6)).item()
+
+
+@pytest.fixture(scope="module")
+def ops():
+    from mlmicroservicetemplate_amd import ops as o
+
+    o.lib()
+    return o
+
+
+def _valid_counts(S):
+    """Valid queries per batch row: full chunks and chunks that end inside a tile."""
+    return [S, max(1, S - 1), max(1, S // 2), S, max(1, S - 7), S]
+
+
+def _case(Hq, Hkv, S, seed=0):
+    """qkv of the chunk (its K / V columns poisoned: the kernel reads K / V from the cache only), a
+    per-slot head-major cache and the same rows in a shuffled page pool; everything a launch must not
+    read (unused slots, rows >= lens, the tail of a slot's last page) is NaN."""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    B = len(PASTS)
+    past = torch.tensor(PASTS, dtype=torch.int32, device=DEV)
+    n = torch.tensor(_valid_counts(S), dtype=torch.int32, device=DEV)
+    lens = past + n
+    qkv = torch.randn(B * S, (Hq + 2 * Hkv) * D, device=DEV, generator=g).to(torch.bfloat16)
+    qkv[:, Hq * D:] = float("nan")
+    n_slots = B + 3
+    slot_ids = torch.tensor([7, 2, 8, 0, 5, 3], dtype=torch.int32, device=DEV)  # slots 1, 4, 6 unused
+    kc = torch.full((n_slots, Hkv, MAX_SEQ, D), float("nan"), device=DEV, dtype=torch.bfloat16)
+    vc = torch.full_like(kc, float("nan"))
+    for b in range(B):
+        L, s = int(lens[b]), int(slot_ids[b])
+        kc[s, :, :L] = torch.randn(Hkv, L, D, device=DEV, generator=g).to(torch.bfloat16)
+        vc[s, :, :L] = torch.randn(Hkv, L, D, device=DEV, generator=g).to(torch.bfloat16)
+    pps = -(-MAX_SEQ // 64)
+    pages = n_slots * pps + 1
+    table = (1 + torch.randperm(pages - 1, device=DEV, generator=g)).view(n_slots, pps).to(torch.int32)
+    kp = torch.full((pages, Hkv, 64, D), float("nan"), device=DEV, dtype=torch.bfloat16)
+    vp = torch.full_like(kp, float("nan"))
+    for s in range(n_slots):
+        for j in range(pps):
+            r0, r1 = j * 64, min(MAX_SEQ, j * 64 + 64)
+            kp[int(table[s, j]), :, : r1 - r0] = kc[s, :, r0:r1]
+            vp[int(table[s, j]), :, : r1 - r0] = vc[s, :, r0:r1]
+    return dict(B=B, S=S, past=past, n=n, lens=lens, qkv=qkv, slot_ids=slot_ids, kc=kc, vc=vc, table=table, kp=kp,
+                vp=vp)
+
+
+def _valid(out, c):
+    """The valid rows of every batch row, concatenated (the others are unspecified)."""
+    o = out.view(c["B"], c["S"], -1)
+    return torch.cat([o[b, : int(c["n"][b])] for b in range(c["B"])])
+
+
+@pytest.mark.parametrize("S", [1, 16, 63, 64, 65, 130])
+@pytest.mark.parametrize("Hq,Hkv", [(4, 1), (8, 2)])
+def test_kernel_vs_oracle_per_slot_and_paged(ops, Hq, Hkv, S):
+    c = _case(Hq, Hkv, S)
+    ref = R.attention_ctx(c["qkv"], c["kc"], c["vc"], c["past"], c["lens"], c["B"], S, Hq, Hkv, D,
+                          slot_ids=c["slot_ids"], head_major=True)
+    ref_p = R.attention_ctx(c["qkv"], c["kp"], c["vp"], c["past"], c["lens"], c["B"], S, Hq, Hkv, D,
+                            slot_ids=c["slot_ids"], page_table=c["table"], head_major=True)
+    assert torch.equal(ref, ref_p)  # the two cache images hold the same rows
+    out = ops.flash_attention_ctx(c["qkv"], c["kc"], c["vc"], c["past"], c["lens"], c["B"], S, Hq, Hkv, D,
+                                  slot_ids=c["slot_ids"])
+    out_p = ops.flash_attention_ctx(c["qkv"], c["kp"], c["vp"], c["past"], c["lens"], c["B"], S, Hq, Hkv, D,
+                                    slot_ids=c["slot_ids"], page_table=c["table"])
+    torch.cuda.synchronize()
+    got, got_p, want = _valid(out, c), _valid(out_p, c), _valid(ref, c)
+    assert torch.isfinite(got.float()).all()  # no poisoned row or column was read
+    err = rel(got, want)
+    print(f"Hq={Hq} Hkv={Hkv} S={S}: rel {err:.4f}")
+    assert err < 2e-2
+    # paged == per-slot bit for bit: the same tiles in the same order, only the addressing differs
+    assert torch.equal(got_p, got)
+
+
+def test_default_slots_and_out(ops):
+    """slot_ids=None: batch row b reads slot b; ``out=`` is written in place."""
+    Hq, Hkv, S, B = 4, 1, 65, 2
+    g = torch.Generator(device=DEV).manual_seed(1)
+    qkv = torch.randn(B * S, (Hq + 2 * Hkv) * D, device=DEV, generator=g).to(torch.bfloat16)
+    kc = torch.randn(B, Hkv, 200, D, device=DEV, generator=g).to(torch.bfloat16)
+    vc = torch.randn(B, Hkv, 200, D, device=DEV, generator=g).to(torch.bfloat16)
+    past = torch.tensor([100, 3], dtype=torch.int32, device=DEV)
+    lens = torch.tensor([165, 40], dtype=torch.int32, device=DEV)
+    out = torch.full((B * S, Hq * D), float("nan"), device=DEV, dtype=torch.bfloat16)
+    ret = ops.flash_attention_ctx(qkv, kc, vc, past, lens, B, S, Hq, Hkv, D, out=out)
+    assert ret.data_ptr() == out.data_ptr()
+    ref = R.attention_ctx(qkv, kc, vc, past, lens, B, S, Hq, Hkv, D, head_major=True)
+    c = dict(B=B, S=S, n=lens - past)
+    assert rel(_valid(out, c), _valid(ref, c)) < 2e-2
+
+
+@pytest.mark.parametrize("Hq,Hkv", [(4, 1), (8, 2)])
+def test_past_zero_matches_flash_attention(ops, Hq, Hkv):
+    """past = 0 with the chunk's own K / V rows in the cache == the one-shot prefill kernel on the same qkv."""
+    B, S = 3, 130
+    g = torch.Generator(device=DEV).manual_seed(2)
+    qkv = torch.randn(B * S, (Hq + 2 * Hkv) * D, device=DEV, generator=g).to(torch.bfloat16)
+    lens = torch.tensor([130, 77, 1], dtype=torch.int32, device=DEV)
+    _q, k, v = R.split_qkv(qkv, Hq, Hkv, D)
+    kc = torch.zeros(B, Hkv, 192, D, device=DEV, dtype=torch.bfloat16)
+    vc = torch.zeros_like(kc)
+    kc[:, :, :S] = k.view(B, S, Hkv, D).transpose(1, 2)
+    vc[:, :, :S] = v.view(B, S, Hkv, D).transpose(1, 2)
+    one = ops.flash_attention(qkv, B, S, Hq, Hkv, D, kv_lens=lens, causal=True)
+    ctx = ops.flash_attention_ctx(qkv, kc, vc, torch.zeros(B, dtype=torch.int32, device=DEV), lens, B, S, Hq, Hkv, D)
+    c = dict(B=B, S=S, n=lens)
+    assert rel(_valid(ctx, c), _valid(one, c)) < 2e-2
+
+
+def test_bad_geometry_is_refused(ops):
+    Hq, Hkv, S, B = 4, 2, 16, 1
+    qkv = torch.zeros(B * S, (Hq + 2 * Hkv) * D, device=DEV, dtype=torch.bfloat16)
+    past = torch.zeros(B, dtype=torch.int32, device=DEV)
+    lens = torch.full((B,), S, dtype=torch.int32, device=DEV)
+    hm = torch.zeros(2, Hkv, 64, D, device=DEV, dtype=torch.bfloat16)
+    ops.flash_attention_ctx(qkv, hm, hm, past, lens, B, S, Hq, Hkv, D)  # the supported layout launches
+    rm = torch.zeros(2, 64, Hkv, D, device=DEV, dtype=torch.bfloat16)  # row-major [slots, rows, Hkv, D]
+    with pytest.raises(ValueError, match="head-major"):
+        ops.flash_attention_ctx(qkv, rm, rm, past, lens, B, S, Hq, Hkv, D)
+    q64 = torch.zeros(B * S, (Hq + 2 * Hkv) * 64, device=DEV, dtype=torch.bfloat16)
+    c64 = torch.zeros(2, Hkv, 64, 64, device=DEV, dtype=torch.bfloat16)
+    with pytest.raises(ValueError, match="head_dim"):
+        ops.flash_attention_ctx(q64, c64, c64, past, lens, B, S, Hq, Hkv, 64)
+    p32 = torch.zeros(4, Hkv, 32, D, device=DEV, dtype=torch.bfloat16)  # pages of 32 rows
+    table = torch.tensor([[1, 2]], dtype=torch.int32, device=DEV)
+    with pytest.raises(ValueError, match="64 rows"):
+        ops.flash_attention_ctx(qkv, p32, p32, past, lens, B, S, Hq, Hkv, D, page_table=table)
+    with pytest.raises(TypeError):
+        ops.flash_attention_ctx(qkv, hm, hm, past.long(), lens, B, S, Hq, Hkv, D)
+    # the host entry refuses the same geometries itself (nothing is launched)
+    lib = ops.lib()
+    out = torch.zeros(B * S, Hq * D, device=DEV, dtype=torch.bfloat16)
+    W = qkv.shape[1]
+
+    def entry(cache, pt, pps, d, hm_rows):
+        return lib.mls_flash_attention_ctx(qkv.data_ptr(), cache.data_ptr(), cache.data_ptr(), out.data_ptr(), W,
+                                           out.stride(0), past.data_ptr(), lens.data_ptr(), None, pt, pps,
+                                           1 if pt else cache.shape[0], B, S, Hq, Hkv, d, cache.shape[0], hm_rows, 1.0,
+                                           ops.stream_ptr(torch.device(DEV)))
+
+    UNSUPPORTED, BAD_ARG = 1002, 1001
+    assert entry(rm, None, 0, D, 0) == UNSUPPORTED           # row-major cache
+    assert entry(c64, None, 0, 64, 64) == UNSUPPORTED        # D = 64
+    assert entry(p32, table.data_ptr(), 2, D, 32) == UNSUPPORTED  # page rows != 64
+    assert lib.mls_flash_attention_ctx(qkv.data_ptr(), hm.data_ptr(), hm.data_ptr(), out.data_ptr(), W + 4,
+                                       out.stride(0), past.data_ptr(), lens.data_ptr(), None, None, 0, 2, B, S, Hq,
+                                       Hkv, D, 2, 64, 1.0, ops.stream_ptr(torch.device(DEV))) == BAD_ARG  # misaligned stride
+
+
+# ------------------------------------------------------------------ the fused model
+CFG128 = dict(vocab=2048, layers=2, hidden=512, heads=8, kv_heads=2, head_dim=128, intermediate=1024)
+
+
+@pytest.fixture(scope="module")
+def tiny():
+    from mlmicroservicetemplate_amd.models.llama import init_llama_shard, tiny_config
+
+    cfg = tiny_config(**CFG128)
+    return cfg, init_llama_shard(cfg, 1, 0, seed=5, device=DEV)
+
+
+def _prompts():
+    ids = torch.randint(3, 2000, (3, 150), generator=torch.Generator().manual_seed(2)).to(torch.int32).to(DEV)
+    return ids, torch.tensor([150, 131, 17], dtype=torch.int32, device=DEV)  # 3 chunks of 64; rows drop out
+
+
+def _llama(tiny, backend, kv_pages=0):
+    from mlmicroservicetemplate_amd.models.llama import LlamaTP
+
+    cfg, p = tiny
+    return LlamaTP(p, cfg, backend=backend, device=DEV, max_batch=4, max_seq=512, kv_pages=kv_pages)
+
+
+@pytest.mark.parametrize("kv_pages", [0, 24])
+def test_fused_chunked_step_vs_reference_backend(tiny, kv_pages):
+    ids, lens = _prompts()
+    B, S = ids.shape
+    ref, fus = _llama(tiny, "reference", kv_pages), _llama(tiny, "fused", kv_pages)
+    if kv_pages:
+        for m in (ref, fus):
+            for b in range(B):
+                m.pages.assign(b, 256)
+    pos = torch.arange(S, device=DEV, dtype=torch.int32).unsqueeze(0).expand(B, S).contiguous()
+    rv, ri = ref.step(ids, pos, lens, decode=False, k=8)  # one shot, fp32
+    fv, fi = fus.prefill_chunked(ids, lens, 64, 8)
+    err = rel(fv, rv)
+    print(f"kv_pages={kv_pages}: chunked fused vs one-shot reference top-k values rel {err:.4f}")
+    assert err <= 3e-2
+    gap = (rv[:, 0] - rv[:, 1]) / rv.abs().max()
+    assert torch.equal(fi[:, 0][gap > 1e-2], ri[:, 0][gap > 1e-2])
+
+
+@pytest.mark.parametrize("kv_pages", [0, 24])
+def test_fused_generate_chunked_same_tokens(tiny, kv_pages):
+    from mlmicroservicetemplate_amd.models.llama import GenParams
+
+    ids, lens = _prompts()
+    gp = GenParams(max_new_tokens=8)
+    a = _llama(tiny, "fused", kv_pages).generate(ids, lens, gp)
+    b = _llama(tiny, "fused", kv_pages).generate(ids, lens, gp)
+    assert torch.equal(a, b)  # the unchunked fused run is reproducible: a difference below is the chunking's
+    c = _llama(tiny, "fused", kv_pages).generate(ids, lens, gp, prefill_chunk=64)
+    assert torch.equal(c.cpu(), a.cpu())
+
+
+def _requests():
+    g = torch.Generator().manual_seed(5)
+    mk = lambda n: torch.randint(3, 2000, (n,), generator=g).tolist()  # noqa: E731
+    from mlmicroservicetemplate_amd.models.llama import GenParams
+
+    return [(mk(400), GenParams(max_new_tokens=6)),  # 7 chunks of 64
+            (mk(9), GenParams(max_new_tokens=5)),
+            (mk(70), GenParams(max_new_tokens=4)),   # two chunks itself
+            (mk(3), GenParams(max_new_tokens=7))]
+
+
+def _drive(eng, reqs, dev_mode, trace):
+    """``ContinuousLlama._loop`` step by step: the long request first, the short ones after its second
+    iteration (mid-prefill when chunked), so both engines see the same admission schedule."""
+    eng._want_dev = dev_mode
+    futs = [eng.submit(*reqs[0])]
+
+    def it():
+        eng.run_iteration(eng._leader_admissions())
+        trace.append(dict(eng.stats(), done=[f.done() for f in futs]))
+
+    it()
+    it()
+    futs += [eng.submit(ids, gp) for ids, gp in reqs[1:]]
+    for _ in range(100):
+        if all(f.done() for f in futs):
+            break
+        it()
+    return [f.result(timeout=0) for f in futs]
+
+
+@pytest.mark.parametrize("dev_mode", [True, False])
+@pytest.mark.parametrize("kv_pages", [0, 24])
+def test_fused_serving_chunked_same_tokens(tiny, kv_pages, dev_mode):
+    from mlmicroservicetemplate_amd.models.llama_serving import ContinuousLlama
+
+    reqs = _requests()
+    e0 = ContinuousLlama(_llama(tiny, "fused", kv_pages))
+    want = _drive(e0, reqs, dev_mode, [])
+    again = _drive(ContinuousLlama(_llama(tiny, "fused", kv_pages)), reqs, dev_mode, [])
+    assert again == want  # the unchunked run is reproducible
+    eng = ContinuousLlama(_llama(tiny, "fused", kv_pages), prefill_chunk=64)
+    trace = []
+    got = _drive(eng, reqs, dev_mode, trace)
+    assert eng.dev_mode == dev_mode and e0.dev_mode == dev_mode
+    assert got == want
+    # short requests decoded (one finished) while the long prompt was still prefilling
+    mid = [t for t in trace if t["prefilling"] >= 1]
+    assert len(mid) >= 3 and any(any(t["done"][1:]) for t in mid)
+    st = eng.stats()
+    assert st["active"] == 0 and st["prefilling"] == 0
+    if kv_pages:
+        assert st["kv_pages_free"] == kv_pages - 1
+
+
+def test_fused_refusals(tiny, monkeypatch):
+    from mlmicroservicetemplate_amd.models.llama import GenParams, LlamaTP
+    from mlmicroservicetemplate_amd.models.llama_serving import ContinuousLlama
+
+    cfg, p = tiny
+    ids, lens = _prompts()
+    m8 = LlamaTP(p, cfg, backend="fused", device=DEV, max_batch=4, max_seq=256, kv_dtype="fp8")
+    with pytest.raises(ValueError, match="fp8"):
+        m8.generate(ids, lens, GenParams(2), prefill_chunk=64)
+    with pytest.raises(ValueError, match="fp8"):
+        ContinuousLlama(m8, prefill_chunk=64)
+    monkeypatch.setenv("MLS_KV_HEAD_MAJOR", "0")
+    rm = LlamaTP(p, cfg, backend="fused", device=DEV, max_batch=4, max_seq=256)
+    with pytest.raises(ValueError, match="head-major"):
+        rm.generate(ids, lens, GenParams(2), prefill_chunk=64)
+
+
+def test_debug_build_reports_ctx_bounds():
+    """The -DMLS_DEBUG build reports lens past a slot's rows, past > lens, a slot outside the cache and a
+    page id outside the pool as NativeError (tests/flash_ctx_debug_probe.py, in a child process as
+    test_debug_build_gpu.py runs its probe: the library variant is chosen at import)."""
+    import os
+    import subprocess
+    import sys
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    root = os.path.dirname(here)
+    env = dict(os.environ, MLS_DEBUG="1", HIP_LAUNCH_BLOCKING="1",
+               PYTHONPATH=os.pathsep.join([root, os.environ.get("PYTHONPATH", "")]))
+    r = subprocess.run([sys.executable, os.path.join(here, "flash_ctx_debug_probe.py")], cwd=root, env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "FLASH-CTX-DEBUG-OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
