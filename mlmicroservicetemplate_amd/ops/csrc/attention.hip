@@ -23,12 +23,12 @@
 //     ("flash-decoding"): grid (splits, Hkv, B); each wave walks keys with 16-B loads, one key
 //     row per D/8 lanes, all G = Hq/Hkv query heads of the KV head at once (GQA: every K/V byte
 //     is read once for the G heads); partial (m, l, O) per split, then a combine kernel.
+//
+// The flash tile's constants and v2 tile body and the cache-type-independent parts of the matrix-core
+// decode kernel are in attn_tiles.h, shared with flash_ctx.hip and kv_fp8.hip.
 #include <cstdlib>
 
-#include "common.h"
-
-typedef short short4v __attribute__((ext_vector_type(4)));
-#define LDS_AS __attribute__((address_space(3)))
+#include "attn_tiles.h"
 
 namespace {
 
@@ -47,18 +47,12 @@ struct AttnArgs {
   uint32_t q_bytes, k_bytes, v_bytes;
 };
 
-MLS_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
 template <int D, int NW = 4>
 __global__ __launch_bounds__(64 * NW) void flash_fwd_kernel(const AttnArgs a) {
+  using T = FlashTile<D>;
   constexpr int NT = 64 * NW;            // threads; NW waves x 16 query rows
-  constexpr int BQ = 16 * NW, BKV = 64;
-  constexpr int CPR = D / 8;             // 16-B chunks per row
-  constexpr int KK = D / 32;             // k-steps of the S^T MFMA
-  constexpr int DT = D / 16;             // 16-wide d tiles of O
-  constexpr int VST = D * 2 + 32;        // padded V row stride (bytes)
-  constexpr int K_BYTES = BKV * D * 2;
-  constexpr int V_BYTES = BKV * VST;
+  constexpr int BQ = 16 * NW, BKV = T::BKV, CPR = T::CPR, KK = T::KK, DT = T::DT, VST = T::VST;
+  constexpr int K_BYTES = T::K_BYTES, V_BYTES = T::V_BYTES;
   __shared__ __attribute__((aligned(16))) char smem[K_BYTES + V_BYTES];
   char* Ks = smem;
   char* Vs = smem + K_BYTES;
@@ -100,8 +94,7 @@ __global__ __launch_bounds__(64 * NW) void flash_fwd_kernel(const AttnArgs a) {
   // K / V tiles (zero rows past L via OOB loads) are register double-buffered: tile kt + 1's loads
   // are issued right after tile kt is in LDS and land while tile kt's MFMAs run (one global
   // round trip per kernel instead of one per tile: BERT S=128 has 2 tiles, Llama S=512 has 8)
-  constexpr int NI = (BKV * CPR) / NT;
-  static_assert(NI * NT == BKV * CPR, "tile chunks split evenly over the block");
+  constexpr int NI = T::ni(NT);
   uint4 kreg[NI], vreg[NI];
   auto load_into = [&](int kt, uint4 (&kd)[NI], uint4 (&vd)[NI]) {
 #pragma unroll
@@ -213,7 +206,6 @@ __global__ __launch_bounds__(64 * NW) void flash_fwd_kernel(const AttnArgs a) {
         const int colb = (16 * dt + 4 * pp) * 2;
         const short4v r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS short4v*)(Vs + row0 * VST + colb));
         const short4v r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS short4v*)(Vs + row1 * VST + colb));
-        typedef short short8v __attribute__((ext_vector_type(8)));
         const short8v vv = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
         acc_o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, __builtin_bit_cast(bf16x8, vv), acc_o[dt], 0, 0, 0);
       }
@@ -256,35 +248,17 @@ __global__ __launch_bounds__(64 * NW) void flash_fwd_kernel(const AttnArgs a) {
   }
 }
 
-// flash_fwd2_kernel<D>: the prefill kernel with the O accumulator transposed and the per-score VALU cut
-// (Llama prefill, D = 128: the v1 loop issued ~450 VALU + ~170 SALU per wave per 64-key tile against
-// 32 MFMAs -- 193 TFLOP/s at B = 8 x 512, profiles/r6_flash_llama_probe.txt).  Same tiling, loads and
-// LDS layouts as flash_fwd_kernel; per tile and wave:
-//   * O^T += V^T P^T: the PV MFMA with its operands swapped (the V fragment read by ds_read_tr16 is the
-//     A operand's layout as well), so the accumulator holds O[q = lane column][d rows] and the softmax
-//     rescale / final 1 / l are lane-local -- no cross-lane shuffles of alpha or 1 / l;
-//   * the row sum l stays a per-lane partial over the lane's own keys (combined once, at the end);
-//   * scores stay unscaled: the row max is taken raw, one FMA per score forms x * scale - m;
-//     -1e30 instead of -inf for the running max removes every "no key yet" select;
-//   * the key-range / causal mask runs only on the tiles that need it (wave-uniform branch), where
-//     16-key sub-tiles wholly above the diagonal also skip their MFMAs;
-//   * tile load offsets are computed once and advanced by one add per tile.
-// One tile body with wave-uniform branches, 158 VGPRs: 3 waves per SIMD.  (Full and edge tiles as
-// two straight-line copies of the body took 196 VGPRs -- 2 waves per SIMD -- and measured 71-73 vs
-// 62 us at B = 8 x 512: profiles/r6_flash_v2_vs_v1.jsonl.)
+// flash_fwd2_kernel<D>: the prefill kernel on the v2 tile body (Flash2Tile of attn_tiles.h, where the
+// design and its VGPR budget are described).  Same tiling, loads and LDS layouts as flash_fwd_kernel;
+// tile load offsets are computed once and advanced by one add per tile.
 template <int D, int NW = 4>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 3) void flash_fwd2_kernel(const AttnArgs a) {
+  using T = FlashTile<D>;
   constexpr int NT = 64 * NW;
-  constexpr int BQ = 16 * NW, BKV = 64;
-  constexpr int CPR = D / 8;
-  constexpr int KK = D / 32;
-  constexpr int DT = D / 16;
-  constexpr int VST = D * 2 + 32;
-  constexpr int K_BYTES = BKV * D * 2;
-  constexpr int V_BYTES = BKV * VST;
-  __shared__ __attribute__((aligned(16))) char smem[K_BYTES + V_BYTES];
+  constexpr int BQ = 16 * NW, BKV = T::BKV, CPR = T::CPR;
+  __shared__ __attribute__((aligned(16))) char smem[T::K_BYTES + T::V_BYTES];
   char* Ks = smem;
-  char* Vs = smem + K_BYTES;
+  char* Vs = smem + T::K_BYTES;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, fr = lane & 15;
@@ -300,29 +274,26 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 3) void flash_fwd2_kernel(co
   const rsrc_t kr = make_rsrc(a.k, a.k_bytes);
   const rsrc_t vr = make_rsrc(a.v, a.v_bytes);
 
-  bf16x8 qf[KK];  // Q^T fragments (B operand of S^T = K Q^T): Q[q = qw + fr][d = 32kk + 8g .. +7]
+  bf16x8 qf[T::KK];  // Q^T fragments (B operand of S^T = K Q^T): Q[q = qw + fr][d = 32kk + 8g .. +7]
   {
     const int q = qw + fr;
 #pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
+    for (int kk = 0; kk < T::KK; ++kk) {
       const int off = q < a.q_rows ? (int)(((tokq + q) * a.q_stride + (long)h * D + 32 * kk + 8 * g) * 2) : OOB;
       qf[kk] = __builtin_bit_cast(bf16x8, bload16(qr, off));
     }
   }
 
-  f32x4 acc_o[DT];  // acc_o[dt][j] = O[q = qw + fr][d = 16dt + 4g + j] (unnormalised)
+  f32x4 acc_o[T::DT];
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt) acc_o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const float c = a.scale_log2;
-  float m_run = -1e30f;  // running max of the scaled scores of query fr (log2 units)
-  float l_run = 0.f;     // this lane's partial of the row sum (its own keys only)
+  for (int dt = 0; dt < T::DT; ++dt) acc_o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m_run = -1e30f, l_run = 0.f;
 
   int kv_end = L;
   if (a.causal) kv_end = min(kv_end, q0 + BQ);
   const int ntiles = (kv_end + BKV - 1) / BKV;
 
-  constexpr int NI = (BKV * CPR) / NT;
-  static_assert(NI * NT == BKV * CPR, "tile chunks split evenly over the block");
+  constexpr int NI = T::ni(NT);
   int krow[NI], koff[NI], voff[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
@@ -343,82 +314,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 3) void flash_fwd2_kernel(co
       vd[i] = bload16(vr, ok ? voff[i] + kt * vstep : OOB);
     }
   };
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  auto tile_body = [&](int kv0, bool EDGE) {
-    f32x4 s[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      // a causal sub-tile wholly above the wave's diagonal: no MFMAs (masked to -inf below)
-      if (EDGE && a.causal && kv0 + 16 * t > qw + 15) continue;
-      const int row = 16 * t + fr;
-#pragma unroll
-      for (int kk = 0; kk < KK; ++kk) {
-        const int ch = 4 * kk + g;
-        const bf16x8 kf = __builtin_bit_cast(
-            bf16x8, *reinterpret_cast<const uint4*>(Ks + row * (D * 2) + ((ch ^ (row & (CPR - 1))) * 16)));
-        s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], s[t], 0, 0, 0);
-      }
-    }
-    if (EDGE) {
-      const int qabs = qw + fr;
-      const int lim = a.causal ? min(L - 1, qabs) : L - 1;  // last visible key of this query
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (kv0 + 16 * t + 4 * g + j > lim) s[t][j] = -INFINITY;
-    }
-    float mt = fmaxf(fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3])),
-                     fmaxf(fmaxf(s[1][0], s[1][1]), fmaxf(s[1][2], s[1][3])));
-    mt = fmaxf(mt, fmaxf(fmaxf(fmaxf(s[2][0], s[2][1]), fmaxf(s[2][2], s[2][3])),
-                         fmaxf(fmaxf(s[3][0], s[3][1]), fmaxf(s[3][2], s[3][3]))));
-    mt = fmaxf(mt, xor16_f(mt));
-    mt = fmaxf(mt, xor32_f(mt));
-    const float m_new = fmaxf(m_run, mt * c);  // -inf * c stays -inf; m_run >= -1e30
-    const float alpha = fast_exp2(m_run - m_new);
-    m_run = m_new;
-    // x * scale - m as packed FMAs (v_pk_fma_f32), two scores per instruction
-    const f32x2 c2 = {c, c}, nm2 = {-m_new, -m_new};
-    f32x2 ls2 = {0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj) {
-        f32x2 x = {s[t][2 * jj], s[t][2 * jj + 1]};
-        x = __builtin_elementwise_fma(x, c2, nm2);
-        const f32x2 p = {fast_exp2(x[0]), fast_exp2(x[1])};  // masked: exp2(-inf) = 0
-        s[t][2 * jj] = p[0];
-        s[t][2 * jj + 1] = p[1];
-        ls2 += p;
-      }
-    l_run = fmaf(l_run, alpha, ls2[0] + ls2[1]);
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) acc_o[dt] *= alpha;
-    // ---- O^T += V^T P^T: two 32-key k-steps, key order permuted identically in both operands ----
-#pragma unroll
-    for (int st = 0; st < 2; ++st) {
-      if (EDGE && a.causal && kv0 + 32 * st > qw + 15) continue;  // both sub-tiles above the diagonal
-      bf16x8 pf;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        pf[j] = (bf16)s[2 * st][j];
-        pf[4 + j] = (bf16)s[2 * st + 1][j];
-      }
-      const int qq = fr >> 2, pp = fr & 3;
-      const int row0 = 32 * st + 4 * g + qq;
-      const int row1 = row0 + 16;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const int colb = (16 * dt + 4 * pp) * 2;
-        const short4v r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS short4v*)(Vs + row0 * VST + colb));
-        const short4v r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS short4v*)(Vs + row1 * VST + colb));
-        typedef short short8v __attribute__((ext_vector_type(8)));
-        const short8v vv = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
-        acc_o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vv), pf, acc_o[dt], 0, 0, 0);
-      }
-    }
-  };
+  const float c = a.scale_log2;
+  const Flash2Tile<D, false> tile_body{acc_o, m_run, l_run, qf, Ks, Vs, a.causal, qw, L, c, g, fr};
   // 8-wave blocks (BERT, S <= 128: two tiles): tile 1's loads go out right behind tile 0's, as in v1
   const bool pre = NW == 8 && a.pre;
   uint4 kpre[NI], vpre[NI];
@@ -432,7 +329,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 3) void flash_fwd2_kernel(co
       const int idx = tid + NT * i;
       const int row = idx / CPR, ch = idx % CPR;
       *reinterpret_cast<uint4*>(Ks + row * (D * 2) + ((ch ^ (row & (CPR - 1))) * 16)) = kreg[i];
-      *reinterpret_cast<uint4*>(Vs + row * VST + ch * 16) = vreg[i];
+      *reinterpret_cast<uint4*>(Vs + row * T::VST + ch * 16) = vreg[i];
     }
     __syncthreads();
     if (kt + 1 < ntiles) {
@@ -457,12 +354,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 3) void flash_fwd2_kernel(co
   float l = l_run + xor16_f(l_run);
   l += xor32_f(l);
   const float inv_l = l > 0.f ? 1.f / l : 0.f;
-  // rows padded by 16 B: the 16 query rows of one 8-B write land in different banks
-  constexpr int OST = D + 8;
+  constexpr int OST = T::OST;
   bf16* Os = reinterpret_cast<bf16*>(smem) + wid * 16 * OST;  // K / V tile space: past the last barrier
-  static_assert(NW * 16 * OST * 2 <= K_BYTES + V_BYTES, "output tiles fit the K / V tiles");
+  static_assert(NW * 16 * OST * 2 <= T::K_BYTES + T::V_BYTES, "output tiles fit the K / V tiles");
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt) {
+  for (int dt = 0; dt < T::DT; ++dt) {
     bf16x4 o4;
 #pragma unroll
     for (int j = 0; j < 4; ++j) o4[j] = (bf16)(acc_o[dt][j] * inv_l);
@@ -738,13 +634,12 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const DecodeArgs a) {
 // RoPE of q / the new key and the KV append run once per block in an LDS prologue.  Partials
 // (m, l, O) are merged over the block's waves and written exactly as the VALU kernel does, so
 // decode_combine_kernel and the fused combine of mls_skinny_packed_combine are shared.
+// What does not depend on the cache holding bf16 -- the prologue's operand loads, O = P . V, the merge
+// and the empty-split exit -- is in attn_tiles.h, shared with decode_attn_fp8_kernel (kv_fp8.hip).
 template <int G, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void decode_attn_mfma_kernel(const DecodeArgs a) {
-  constexpr int D = 128, KK = D / 32, DT = D / 16;
-  constexpr int NT = WAVES * 64, CHUNK = WAVES * 32;
-  constexpr int VST = D * 2 + 32;          // padded V row (bytes): conflict-free transposed reads
-  constexpr int NPRO = (G + 1) * 16;       // prologue tasks: G query heads + the new key row, 16-B chunks
-  constexpr int PIT = (NPRO + NT - 1) / NT;
+  using T = DecodeTile<G, WAVES>;
+  constexpr int D = T::D, KK = T::KK, NT = T::NT, CHUNK = T::CHUNK, VST = T::VST, NPRO = T::NPRO, PIT = T::PIT;
   __shared__ __attribute__((aligned(16))) char vs[WAVES][32 * VST];
   __shared__ __attribute__((aligned(16))) bf16 qimg[G + 2][D];  // roped q heads, roped new K, new V
   __shared__ float sm_m[WAVES][G], sm_l[WAVES][G];
@@ -756,11 +651,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_attn_mfma_kernel(const Deco
   MLS_CHECK(sp != 0 || L0 <= a.nsplit * CHUNK, 201);
   const int L = min(L0, a.nsplit * CHUNK);
   const int start = sp * CHUNK;
-  if (start >= L) {
-    if (L <= 0 && sp == 0)
-      for (int idx = tid; idx < G * D; idx += NT) a.o[(long)b * a.o_stride + (long)hk * G * D + idx] = (bf16)0.f;
-    return;
-  }
+  if (decode_split_empty<G, NT>(start, L, sp, a.o, a.o_stride, b, hk, tid)) return;
   const int end = min(L, start + CHUNK);
   const bool rope = a.positions != nullptr;
   const int pos = rope ? a.positions[b] : 0;
@@ -783,26 +674,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_attn_mfma_kernel(const Deco
   // small operands first (so their vmcnt waits leave the cache rows in flight), then the rows
   uint4 px[PIT], pxp[PIT], pv[PIT];
   float4 pcs[PIT][4];
-#pragma unroll
-  for (int it = 0; it < PIT; ++it) {
-    const int t = tid + it * NT, r = t >> 4, c = t & 15;
-    px[it] = pxp[it] = pv[it] = make_uint4(0, 0, 0, 0);
-    pcs[it][0] = pcs[it][1] = pcs[it][2] = pcs[it][3] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (t < NPRO && (r < G || rope)) {
-      const bf16* src = qrow + (long)(r < G ? hk * G + r : a.Hq + hk) * D;
-      px[it] = ld16(src + c * 8);
-      if (rope) {
-        pxp[it] = ld16(src + ((c + 8) & 15) * 8);
-        const float* cp = a.cos_t + (long)pos * (D / 2) + (c & 7) * 8;
-        const float* sq = a.sin_t + (long)pos * (D / 2) + (c & 7) * 8;
-        pcs[it][0] = *reinterpret_cast<const float4*>(cp);
-        pcs[it][1] = *reinterpret_cast<const float4*>(cp + 4);
-        pcs[it][2] = *reinterpret_cast<const float4*>(sq);
-        pcs[it][3] = *reinterpret_cast<const float4*>(sq + 4);
-        if (r == G) pv[it] = ld16(qrow + (long)(a.Hq + a.Hkv + hk) * D + c * 8);
-      }
-    }
-  }
+  decode_pro_load<G, WAVES>(px, pxp, pv, pcs, qrow, rope, a.cos_t, a.sin_t, pos, hk, a.Hq, a.Hkv, tid);
   uint4 kraw[2][KK], vraw[8];
 #pragma unroll
   for (int t2 = 0; t2 < 2; ++t2) {
@@ -908,18 +780,8 @@ __global__ __launch_bounds__(WAVES * 64) void decode_attn_mfma_kernel(const Deco
     pf[j] = (bf16)s[0][j];
     pf[4 + j] = (bf16)s[1][j];
   }
-  const int row0 = 4 * g + (fr >> 2), row1 = row0 + 16;
-  f32x4 o[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) {
-    const int colb = (16 * dt + 4 * (fr & 3)) * 2;
-    const short4v r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS short4v*)(V + row0 * VST + colb));
-    const short4v r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS short4v*)(V + row1 * VST + colb));
-    typedef short short8v __attribute__((ext_vector_type(8)));
-    const short8v vv = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
-    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, __builtin_bit_cast(bf16x8, vv), f32x4{0.f, 0.f, 0.f, 0.f},
-                                                    0, 0, 0);
-  }
+  f32x4 o[T::DT];
+  decode_pv(o, pf, V, g, fr);
   // O rows = heads 4g + j, columns d = 16 dt + fr
   if (g == 0 && fr < G) {
     sm_m[wid][fr] = mt;
@@ -930,36 +792,12 @@ __global__ __launch_bounds__(WAVES * 64) void decode_attn_mfma_kernel(const Deco
     const int h = 4 * g + j;
     if (h < G) {
 #pragma unroll
-      for (int dt = 0; dt < DT; ++dt) sm_o[wid][h < G ? h : 0][16 * dt + fr] = o[dt][j];
+      for (int dt = 0; dt < T::DT; ++dt) sm_o[wid][h < G ? h : 0][16 * dt + fr] = o[dt][j];
     }
   }
-  __syncthreads();
-  const bool direct = L <= CHUNK;
-  for (int idx = tid; idx < G * D; idx += NT) {
-    const int hh = idx / D, d = idx % D;
-    float M = -INFINITY;
-#pragma unroll
-    for (int p = 0; p < WAVES; ++p) M = fmaxf(M, sm_m[p][hh]);
-    float Ls = 0.f, O = 0.f;
-    if (M != -INFINITY) {
-#pragma unroll
-      for (int p = 0; p < WAVES; ++p) {
-        const float w = __builtin_amdgcn_exp2f(sm_m[p][hh] - M);
-        Ls += sm_l[p][hh] * w;
-        O += sm_o[p][hh][d] * w;
-      }
-    }
-    if (direct) {
-      a.o[(long)b * a.o_stride + (long)(hk * G + hh) * D + d] = (bf16)(Ls > 0.f ? O / Ls : 0.f);
-    } else {
-      const long base = ((long)b * a.Hq + hk * G + hh) * a.nsplit + sp;
-      a.ws[base * D + d] = O;
-      if (d == 0) {
-        a.ws_ml[base * 2] = M;
-        a.ws_ml[base * 2 + 1] = Ls;
-      }
-    }
-  }
+  const DecodeMerge<G, WAVES> merge{sm_m,       sm_l, sm_o,     a.o, a.ws, a.ws_ml,
+                                    a.o_stride, a.Hq, a.nsplit, b,   hk,   sp,      tid};
+  merge(L <= CHUNK);
 }
 
 // merge the splits of one (b, q-head): block of D threads; the (m, l) of every split are read

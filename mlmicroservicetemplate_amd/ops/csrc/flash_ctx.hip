@@ -6,20 +6,20 @@
 // own rows are appended first (mls_rope_kv) and read back like any other context row.  past / lens /
 // slot_ids / the page table are device arrays, nothing is read on the host: the launch is capturable.
 //
-// flash_ctx_kernel is flash_fwd2_kernel<128> of attention.hip (S^T = K . Q^T with the key on the
-// accumulator row, O^T += V^T . P^T with the V fragment read by ds_read_b64_tr_b16, 64-key LDS tiles,
-// register double-buffered tile loads, masks on edge tiles only) with two changes:
-//   * the causal diagonal is offset by past[b]: a block's 64 queries span up to two key tiles, so the
-//     last tile can be wholly above an early wave's diagonal (all of its MFMAs are skipped);
+// flash_ctx_kernel runs the v2 flash tile of attn_tiles.h -- the 64-key LDS tile layout (FlashTile) and
+// the tile body (Flash2Tile: S^T = K . Q^T with the key on the accumulator row, O^T += V^T . P^T,
+// masks on edge tiles only) -- which it shares with flash_fwd2_kernel<128> of attention.hip; the
+// staging loop and the epilogue are that kernel's text (attn_tiles.h says why they are not shared).
+// What is this kernel's own:
+//   * the causal diagonal is offset by past[b] (the tile body gets the position past[b] + qw of the
+//     wave's first query): a block's 64 queries span up to two key tiles, so the last tile can be
+//     wholly above an early wave's diagonal (all of its MFMAs are skipped);
 //   * a K / V tile is one contiguous 64 x 256 B run of a head-major cache: rows kt*64 .. of
 //     [slot][Hkv][max_seq][D], or (paged) the whole block [page][Hkv][64][D] the table maps tile kt
 //     to.  Each run gets its own buffer descriptor -- a 64-bit base and the run's valid bytes -- so
 //     caches beyond 4 GiB are addressed exactly, rows >= lens[b] (and anything past the slot's rows)
 //     read as zero through the hardware range check, and lane offsets stay 16-bit constants.
-#include "common.h"
-
-typedef short short4v __attribute__((ext_vector_type(4)));
-#define LDS_AS __attribute__((address_space(3)))
+#include "attn_tiles.h"
 
 namespace {
 
@@ -43,21 +43,14 @@ struct CtxArgs {
   float scale_log2;
 };
 
-MLS_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
 __global__ __launch_bounds__(256, 3) void flash_ctx_kernel(const CtxArgs a) {
   constexpr int D = 128, NW = 4;
+  using T = FlashTile<D>;
   constexpr int NT = 64 * NW;
-  constexpr int BQ = 16 * NW, BKV = 64;
-  constexpr int CPR = D / 8;
-  constexpr int KK = D / 32;
-  constexpr int DT = D / 16;
-  constexpr int VST = D * 2 + 32;
-  constexpr int K_BYTES = BKV * D * 2;
-  constexpr int V_BYTES = BKV * VST;
-  __shared__ __attribute__((aligned(16))) char smem[K_BYTES + V_BYTES];
+  constexpr int BQ = 16 * NW, BKV = T::BKV, CPR = T::CPR;
+  __shared__ __attribute__((aligned(16))) char smem[T::K_BYTES + T::V_BYTES];
   char* Ks = smem;
-  char* Vs = smem + K_BYTES;
+  char* Vs = smem + T::K_BYTES;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, fr = lane & 15;
@@ -88,29 +81,26 @@ __global__ __launch_bounds__(256, 3) void flash_ctx_kernel(const CtxArgs a) {
   }
 
   const rsrc_t qr = make_rsrc(a.q, a.q_bytes);
-  bf16x8 qf[KK];  // Q^T fragments (B operand of S^T = K Q^T): Q[q = qw + fr][d = 32kk + 8g .. +7]
+  bf16x8 qf[T::KK];  // Q^T fragments (B operand of S^T = K Q^T): Q[q = qw + fr][d = 32kk + 8g .. +7]
   {
     const int q = qw + fr;
 #pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
+    for (int kk = 0; kk < T::KK; ++kk) {
       const int off = q < a.S ? (int)(((tokq + q) * a.q_stride + (long)h * D + 32 * kk + 8 * g) * 2) : OOB;
       qf[kk] = __builtin_bit_cast(bf16x8, bload16(qr, off));
     }
   }
 
-  f32x4 acc_o[DT];  // acc_o[dt][j] = O[q = qw + fr][d = 16dt + 4g + j] (unnormalised)
+  f32x4 acc_o[T::DT];
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt) acc_o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const float c = a.scale_log2;
-  float m_run = -1e30f;
-  float l_run = 0.f;
+  for (int dt = 0; dt < T::DT; ++dt) acc_o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m_run = -1e30f, l_run = 0.f;
 
   const int kv_end = min(L, P + q0 + BQ);  // one past the last key any query of the block sees
   const int ntiles = (kv_end + BKV - 1) / BKV;
   const int pw = P + qw;  // position of the wave's first query
 
-  constexpr int NI = (BKV * CPR) / NT;
-  static_assert(NI * NT == BKV * CPR, "tile chunks split evenly over the block");
+  constexpr int NI = T::ni(NT);
   const int* tab = paged ? a.page_table + (long)slot * a.pages_per_seq : nullptr;
   // ntiles <= ceil(L / 64) <= pages_per_seq: L <= rows_cap = pages_per_seq * 64
   auto page_of = [&](int kt) { return paged && kt < ntiles ? __builtin_amdgcn_readfirstlane(tab[kt]) : 0; };
@@ -130,81 +120,9 @@ __global__ __launch_bounds__(256, 3) void flash_ctx_kernel(const CtxArgs a) {
       vreg[i] = bload16(vr, (tid + NT * i) * 16);
     }
   };
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  auto tile_body = [&](int kv0, bool EDGE) {
-    f32x4 s[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      // a sub-tile wholly above the wave's diagonal: no MFMAs (masked to -inf below)
-      if (EDGE && kv0 + 16 * t > pw + 15) continue;
-      const int row = 16 * t + fr;
-#pragma unroll
-      for (int kk = 0; kk < KK; ++kk) {
-        const int ch = 4 * kk + g;
-        const bf16x8 kf = __builtin_bit_cast(
-            bf16x8, *reinterpret_cast<const uint4*>(Ks + row * (D * 2) + ((ch ^ (row & (CPR - 1))) * 16)));
-        s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], s[t], 0, 0, 0);
-      }
-    }
-    if (EDGE) {
-      const int lim = min(L - 1, pw + fr);  // last visible key of this query
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (kv0 + 16 * t + 4 * g + j > lim) s[t][j] = -INFINITY;
-    }
-    float mt = fmaxf(fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3])),
-                     fmaxf(fmaxf(s[1][0], s[1][1]), fmaxf(s[1][2], s[1][3])));
-    mt = fmaxf(mt, fmaxf(fmaxf(fmaxf(s[2][0], s[2][1]), fmaxf(s[2][2], s[2][3])),
-                         fmaxf(fmaxf(s[3][0], s[3][1]), fmaxf(s[3][2], s[3][3]))));
-    mt = fmaxf(mt, xor16_f(mt));
-    mt = fmaxf(mt, xor32_f(mt));
-    const float m_new = fmaxf(m_run, mt * c);  // -inf * c stays -inf; m_run >= -1e30
-    const float alpha = fast_exp2(m_run - m_new);
-    m_run = m_new;
-    const f32x2 c2 = {c, c}, nm2 = {-m_new, -m_new};
-    f32x2 ls2 = {0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj) {
-        f32x2 x = {s[t][2 * jj], s[t][2 * jj + 1]};
-        x = __builtin_elementwise_fma(x, c2, nm2);
-        const f32x2 p = {fast_exp2(x[0]), fast_exp2(x[1])};  // masked: exp2(-inf) = 0
-        s[t][2 * jj] = p[0];
-        s[t][2 * jj + 1] = p[1];
-        ls2 += p;
-      }
-    l_run = fmaf(l_run, alpha, ls2[0] + ls2[1]);
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) acc_o[dt] *= alpha;
-    // ---- O^T += V^T P^T: two 32-key k-steps, key order permuted identically in both operands ----
-#pragma unroll
-    for (int st = 0; st < 2; ++st) {
-      if (EDGE && kv0 + 32 * st > pw + 15) continue;  // both sub-tiles above the diagonal
-      bf16x8 pf;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        pf[j] = (bf16)s[2 * st][j];
-        pf[4 + j] = (bf16)s[2 * st + 1][j];
-      }
-      const int qq = fr >> 2, pp = fr & 3;
-      const int row0 = 32 * st + 4 * g + qq;
-      const int row1 = row0 + 16;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const int colb = (16 * dt + 4 * pp) * 2;
-        const short4v r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS short4v*)(Vs + row0 * VST + colb));
-        const short4v r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS short4v*)(Vs + row1 * VST + colb));
-        typedef short short8v __attribute__((ext_vector_type(8)));
-        const short8v vv = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
-        acc_o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vv), pf, acc_o[dt], 0, 0, 0);
-      }
-    }
-  };
-
+  const float c = a.scale_log2;
+  const int causal = 1;  // (unused: the rule is the template argument)
+  const Flash2Tile<D, true> tile_body{acc_o, m_run, l_run, qf, Ks, Vs, causal, pw, L, c, g, fr};
   // the page id of tile kt + 1 is read one tile early, so its K / V loads do not wait on the table
   int pg_next = page_of(1);
   load_tile(0, page_of(0));
@@ -215,7 +133,7 @@ __global__ __launch_bounds__(256, 3) void flash_ctx_kernel(const CtxArgs a) {
       const int idx = tid + NT * i;
       const int row = idx / CPR, ch = idx % CPR;
       *reinterpret_cast<uint4*>(Ks + row * (D * 2) + ((ch ^ (row & (CPR - 1))) * 16)) = kreg[i];
-      *reinterpret_cast<uint4*>(Vs + row * VST + ch * 16) = vreg[i];
+      *reinterpret_cast<uint4*>(Vs + row * T::VST + ch * 16) = vreg[i];
     }
     __syncthreads();
     if (kt + 1 < ntiles) {
@@ -232,11 +150,11 @@ __global__ __launch_bounds__(256, 3) void flash_ctx_kernel(const CtxArgs a) {
   float l = l_run + xor16_f(l_run);
   l += xor32_f(l);
   const float inv_l = l > 0.f ? 1.f / l : 0.f;
-  constexpr int OST = D + 8;  // rows padded by 16 B: the 16 query rows of one 8-B write land in different banks
+  constexpr int OST = T::OST;
   bf16* Os = reinterpret_cast<bf16*>(smem) + wid * 16 * OST;  // K / V tile space: past the last barrier
-  static_assert(NW * 16 * OST * 2 <= K_BYTES + V_BYTES, "output tiles fit the K / V tiles");
+  static_assert(NW * 16 * OST * 2 <= T::K_BYTES + T::V_BYTES, "output tiles fit the K / V tiles");
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt) {
+  for (int dt = 0; dt < T::DT; ++dt) {
     bf16x4 o4;
 #pragma unroll
     for (int j = 0; j < 4; ++j) o4[j] = (bf16)(acc_o[dt][j] * inv_l);

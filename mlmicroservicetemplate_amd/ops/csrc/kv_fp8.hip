@@ -8,18 +8,18 @@
 // (1) rope_kv_fp8_kernel: the prefill writer.  RoPE on Q and K in place in the bf16 QKV rows exactly
 //     as rope_kv_kernel (norm_ops.hip) -- prefill attention keeps reading unquantised bf16 -- then
 //     the quantised K / V rows and their scales go to the cache slot.
-// (2) decode_attn_fp8_kernel: decode_attn_mfma_kernel (attention.hip) reading the fp8 cache.  e4m3
-//     converts to bf16 exactly, so K bytes go through v_cvt_pk_f32_fp8 into the same
-//     v_mfma_f32_16x16x32_bf16; the per-key K scale multiplies the fp32 S^T row, the per-key V
-//     scale is folded into P.  Partials (m, l, O) have the bf16 kernel's format, so the combine
-//     kernel here and the fused combine of mls_skinny_packed_combine[_ar] consume them unchanged.
+// (2) decode_attn_fp8_kernel: matrix-core decode attention on the fp8 cache, the structure of
+//     decode_attn_mfma_kernel (attention.hip).  e4m3 converts to bf16 exactly, so K bytes go through
+//     v_cvt_pk_f32_fp8 into the same v_mfma_f32_16x16x32_bf16; the per-key K scale multiplies the
+//     fp32 S^T row, the per-key V scale is folded into P.  The kernel's own: the cache addressing and
+//     its bounds, RoPE in the prefill writer's rounding, the K loads and their dimension
+//     permutation, the scaled softmax and the V image fill.  Shared with the bf16 kernel through
+//     attn_tiles.h: the prologue's operand loads, O = P . V, the cross-wave merge with the direct /
+//     partial write, and the empty-split exit.  Partials (m, l, O) therefore have one format: the
+//     combine kernel here and the fused combine of mls_skinny_packed_combine[_ar] consume them.
 // Both writers (prefill, and the rope-mode prologue of decode) quantise through kv_fp8_quant_store:
 // identical bytes for identical input, so a token's logits do not depend on who wrote its row.
-#include "common.h"
-
-typedef short short4v __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-#define LDS_AS __attribute__((address_space(3)))
+#include "attn_tiles.h"
 
 namespace {
 
@@ -64,10 +64,10 @@ MLS_DEV float kv_fp8_quant_store(const float (&x)[8], int c, uint8_t* row, float
 
 // 8 e4m3 bytes -> 8 bf16 (exact)
 MLS_DEV bf16x8 fp8x8_to_bf16(uint32_t d0, uint32_t d1) {
-  const f32x2v f0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, false);
-  const f32x2v f1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, true);
-  const f32x2v f2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, false);
-  const f32x2v f3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, true);
+  const f32x2 f0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, false);
+  const f32x2 f1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, true);
+  const f32x2 f2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, false);
+  const f32x2 f3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, true);
   bf16x8 r;
   r[0] = (bf16)f0[0]; r[1] = (bf16)f0[1]; r[2] = (bf16)f1[0]; r[3] = (bf16)f1[1];
   r[4] = (bf16)f2[0]; r[5] = (bf16)f2[1]; r[6] = (bf16)f3[0]; r[7] = (bf16)f3[1];
@@ -170,11 +170,9 @@ struct DecodeFp8Args {
 //      the same padded row-major image that ds_read_b64_tr_b16 reads.
 template <int G, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void decode_attn_fp8_kernel(const DecodeFp8Args a) {
-  constexpr int KK = D / 32, DT = D / 16;
-  constexpr int NT = WAVES * 64, CHUNK = WAVES * 32;
-  constexpr int VST = D * 2 + 32;          // padded V row (bytes): conflict-free transposed reads
-  constexpr int NPRO = (G + 1) * 16;       // prologue tasks: G query heads + the new K / V row, 16 lanes each
-  constexpr int PIT = (NPRO + NT - 1) / NT;
+  using T = DecodeTile<G, WAVES>;
+  static_assert(T::D == D, "the shared decode pieces are D = 128");
+  constexpr int KK = T::KK, NT = T::NT, CHUNK = T::CHUNK, VST = T::VST, NPRO = T::NPRO, PIT = T::PIT;
   __shared__ __attribute__((aligned(16))) char vs[WAVES][32 * VST];
   __shared__ __attribute__((aligned(16))) bf16 qimg[G][D];      // roped q heads
   __shared__ __attribute__((aligned(16))) uint8_t newq[2][D];   // the new token's quantised K, V rows
@@ -190,11 +188,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_attn_fp8_kernel(const Decod
   MLS_CHECK(sp != 0 || L0 <= cap, 201);
   const int L = min(L0, cap);
   const int start = sp * CHUNK;
-  if (start >= L) {
-    if (L <= 0 && sp == 0)
-      for (int idx = tid; idx < G * D; idx += NT) a.o[(long)b * a.o_stride + (long)hk * G * D + idx] = (bf16)0.f;
-    return;
-  }
+  if (decode_split_empty<G, NT>(start, L, sp, a.o, a.o_stride, b, hk, tid)) return;
   const int end = min(L, start + CHUNK);
   const bool rope = a.positions != nullptr;
   const int pos = rope ? a.positions[b] : 0;
@@ -213,26 +207,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_attn_fp8_kernel(const Decod
   // small operands first (so their vmcnt waits leave the cache rows in flight), then the rows
   uint4 px[PIT], pxp[PIT], pv[PIT];
   float4 pcs[PIT][4];
-#pragma unroll
-  for (int it = 0; it < PIT; ++it) {
-    const int t = tid + it * NT, r = t >> 4, c = t & 15;
-    px[it] = pxp[it] = pv[it] = make_uint4(0, 0, 0, 0);
-    pcs[it][0] = pcs[it][1] = pcs[it][2] = pcs[it][3] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (t < NPRO && (r < G || rope)) {
-      const bf16* src = qrow + (long)(r < G ? hk * G + r : a.Hq + hk) * D;
-      px[it] = ld16(src + c * 8);
-      if (rope) {
-        pxp[it] = ld16(src + ((c + 8) & 15) * 8);
-        const float* cp = a.cos_t + (long)pos * (D / 2) + (c & 7) * 8;
-        const float* sq = a.sin_t + (long)pos * (D / 2) + (c & 7) * 8;
-        pcs[it][0] = *reinterpret_cast<const float4*>(cp);
-        pcs[it][1] = *reinterpret_cast<const float4*>(cp + 4);
-        pcs[it][2] = *reinterpret_cast<const float4*>(sq);
-        pcs[it][3] = *reinterpret_cast<const float4*>(sq + 4);
-        if (r == G) pv[it] = ld16(qrow + (long)(a.Hq + a.Hkv + hk) * D + c * 8);
-      }
-    }
-  }
+  decode_pro_load<G, WAVES>(px, pxp, pv, pcs, qrow, rope, a.cos_t, a.sin_t, pos, hk, a.Hq, a.Hkv, tid);
   uint4 kraw[2][2], vraw[4];
   float4 ksv[2], vsv[2];
 #pragma unroll
@@ -369,18 +344,8 @@ __global__ __launch_bounds__(WAVES * 64) void decode_attn_fp8_kernel(const Decod
     pf[j] = (bf16)(s[0][j] * vscale[0][j]);
     pf[4 + j] = (bf16)(s[1][j] * vscale[1][j]);
   }
-  const int row0 = 4 * g + (fr >> 2), row1 = row0 + 16;
-  f32x4 o[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) {
-    const int colb = (16 * dt + 4 * (fr & 3)) * 2;
-    const short4v r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS short4v*)(V + row0 * VST + colb));
-    const short4v r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS short4v*)(V + row1 * VST + colb));
-    typedef short short8v __attribute__((ext_vector_type(8)));
-    const short8v vv = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
-    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, __builtin_bit_cast(bf16x8, vv), f32x4{0.f, 0.f, 0.f, 0.f},
-                                                    0, 0, 0);
-  }
+  f32x4 o[T::DT];
+  decode_pv(o, pf, V, g, fr);
   // O rows = heads 4g + j, columns d = 16 dt + fr
   if (g == 0 && fr < G) {
     sm_m[wid][fr] = mt;
@@ -391,40 +356,18 @@ __global__ __launch_bounds__(WAVES * 64) void decode_attn_fp8_kernel(const Decod
     const int h = 4 * g + j;
     if (h < G) {
 #pragma unroll
-      for (int dt = 0; dt < DT; ++dt) sm_o[wid][h < G ? h : 0][16 * dt + fr] = o[dt][j];
+      for (int dt = 0; dt < T::DT; ++dt) sm_o[wid][h < G ? h : 0][16 * dt + fr] = o[dt][j];
     }
   }
-  __syncthreads();
-  const bool direct = L <= CHUNK;
-  for (int idx = tid; idx < G * D; idx += NT) {
-    const int hh = idx / D, d = idx % D;
-    float M = -INFINITY;
-#pragma unroll
-    for (int p = 0; p < WAVES; ++p) M = fmaxf(M, sm_m[p][hh]);
-    float Ls = 0.f, O = 0.f;
-    if (M != -INFINITY) {
-#pragma unroll
-      for (int p = 0; p < WAVES; ++p) {
-        const float w = __builtin_amdgcn_exp2f(sm_m[p][hh] - M);
-        Ls += sm_l[p][hh] * w;
-        O += sm_o[p][hh][d] * w;
-      }
-    }
-    if (direct) {
-      a.o[(long)b * a.o_stride + (long)(hk * G + hh) * D + d] = (bf16)(Ls > 0.f ? O / Ls : 0.f);
-    } else {
-      const long base = ((long)b * a.Hq + hk * G + hh) * a.nsplit + sp;
-      a.ws[base * D + d] = O;
-      if (d == 0) {
-        a.ws_ml[base * 2] = M;
-        a.ws_ml[base * 2 + 1] = Ls;
-      }
-    }
-  }
+  const DecodeMerge<G, WAVES> merge{sm_m,       sm_l, sm_o,     a.o, a.ws, a.ws_ml,
+                                    a.o_stride, a.Hq, a.nsplit, b,   hk,   sp,      tid};
+  merge(L <= CHUNK);
 }
 
-// merge the splits of one (b, q-head): decode_combine_kernel's arithmetic (attention.hip) on this
-// translation unit's argument block.  Block of D threads; every split's (m, l) once into LDS.
+// merge the splits of one (b, q-head): block of D threads; every split's (m, l) once into LDS.  The
+// arithmetic of decode_combine_kernel (attention.hip) in its plain-loop form, kept on purpose: on this
+// path the one-round-trip form measured 2.8 % slower at batch 8 x 8192 (128 splits of 64) and its
+// differently contracted sums moved output bits (docs/PERF_NOTES.md).
 __global__ __launch_bounds__(D) void decode_combine_fp8_kernel(const DecodeFp8Args a, int chunk) {
   __shared__ float sw[1024];
   __shared__ float s_inv;

@@ -155,6 +155,21 @@ def test_decode_plain(ops, Hq, Hkv, chunk):
     assert rel(got, ops.skinny_packed(a_ref, wp, N)) < 1e-2
 
 
+@pytest.mark.parametrize("L,max_len", [(700, 704), (8257, 8320)])
+def test_decode_plain_many_splits(ops, L, max_len):
+    """The split combine beyond test_decode_plain's 8 splits: 11 splits run its blocks of 8 plus the
+    remainder loop, 130 splits (> D, the block's threads) a second trip of its strided (m, l) passes."""
+    B, Hq, Hkv, chunk = 1, 4, 1, 64
+    k8, v8, ks, vs, kd, vd = _fp8_cache(B, max_len, Hkv, seed=7)
+    torch.manual_seed(7)
+    q = torch.randn(B, (Hq + 2 * Hkv) * D, device=DEV).to(torch.bfloat16)
+    lens = torch.tensor([L], device=DEV, dtype=torch.int32)
+    ref = R.decode_attention(q, kd, vd, lens, Hq, Hkv, D)
+    out = ops.decode_attention_fp8(q, k8, v8, ks, vs, lens, Hq, Hkv, D, chunk=chunk)
+    print("many splits rel", rel(out, ref))
+    assert rel(out, ref) < 2e-2
+
+
 # ------------------------------------------------------------------------------- 3. rope + append
 @pytest.mark.parametrize("Hq,Hkv", [(4, 1), (32, 8), (8, 1)])
 @pytest.mark.parametrize("chunk", [64, 128])

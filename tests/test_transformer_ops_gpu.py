@@ -191,6 +191,20 @@ def test_decode_attention_8k_context(ops, impl, chunk):
     assert not cnt.any()
 
 
+def test_decode_attention_more_splits_than_lanes(ops):
+    """130 splits of 64 against the combine kernel's block of D = 128 threads: the (m, l) of the splits
+    no longer fit one per lane, so both of its passes take their strided form."""
+    torch.manual_seed(7)
+    B, max_len, Hq, Hkv, D = 1, 8320, 4, 1, 128
+    kc = torch.randn(B, max_len, Hkv, D, device=DEV).to(torch.bfloat16)
+    vc = torch.randn(B, max_len, Hkv, D, device=DEV).to(torch.bfloat16)
+    q = torch.randn(B, (Hq + 2 * Hkv) * D, device=DEV).to(torch.bfloat16)
+    lens = torch.tensor([8257], device=DEV, dtype=torch.int32)
+    ref = R.decode_attention(q, kc, vc, lens, Hq, Hkv, D)
+    out = ops.decode_attention(q, kc, vc, lens, Hq, Hkv, D, chunk=64, impl="mfma")
+    assert rel(out, ref) < 2e-2
+
+
 @pytest.mark.parametrize("cfg", [
     # B, S, Hq, Hkv, D, causal, lens, spike row
     (8, 512, 32, 8, 128, True, None, None),          # Llama-3-8B TP = 1 prefill shape
