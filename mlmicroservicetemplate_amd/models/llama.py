@@ -424,17 +424,29 @@ class LlamaTP:
 
     def __init__(self, params: Dict[str, torch.Tensor], cfg: LlamaConfig, tp: int = 1, rank: int = 0,
                  comm: Optional[TPComm] = None, backend: str = "reference", device="cpu", max_batch: int = 8,
-                 max_seq: int = 1024, top_k_max: int = 50, kv_pages: int = 0, kv_dtype: str = "bf16"):
+                 max_seq: int = 1024, top_k_max: int = 50, kv_pages: int = 0, kv_dtype: str = "bf16",
+                 weight_dtype: str = "bf16"):
         """``kv_pages > 0``: paged KV cache -- per layer a pool of ``kv_pages`` pages of 64 rows
         shared by all sequences (:class:`~.kv_pages.PageTable`), instead of ``max_batch x max_seq``.
         ``kv_dtype="fp8"``: e4m3 KV rows with one fp32 scale per (row, KV head)
         (``ops.reference.kv_quant_fp8``) -- 132 instead of 256 bytes per head row.  Fused backend: uint8
         caches + scale tensors, written and read by ``ops.rope_kv_fp8_`` / ``ops.decode_attention_fp8``
         (head-major layout, head_dim 128, Hq / Hkv in 1, 2, 4, 8 only); reference backend: the fp32
-        caches hold the round-tripped rows (the CPU oracle).  Prefill attention stays unquantised."""
+        caches hold the round-tripped rows (the CPU oracle).  Prefill attention stays unquantised.
+        ``weight_dtype="int4"``: W4A16 layer projections (qkv, o, gate / up, down) -- symmetric 4-bit
+        codes with one bf16 scale per (row, 128 k) (``ops.reference.w4_quant``), quantised with the
+        RMSNorm gains folded in; ``lm_head`` and the embedding stay bf16 (the usual quality choice).
+        Both backends hold the dequantised product as the model's weights; the fused backend also
+        keeps the packed codes (``self.w4``) and streams them in decode steps of up to
+        ``w4_max_rows`` rows (``ops.skinny_w4``), larger steps run the bf16 rounding of the same
+        weights.  Every quantised matrix needs K % 128 == 0 on this rank (row-parallel shards
+        then cut K at group boundaries, so every TP degree sees the same groups).  Changes numerics."""
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
+        if weight_dtype not in ("bf16", "int4"):
+            raise ValueError(f"weight_dtype must be 'bf16' or 'int4', got {weight_dtype!r}")
         self.kv_dtype = kv_dtype
+        self.weight_dtype = weight_dtype
         self.cfg = cfg
         self.sd = shard_dims(cfg, tp, rank)
         self.tp, self.rank = tp, rank
@@ -448,6 +460,27 @@ class LlamaTP:
         self.top_k_max = top_k_max
         D = cfg.head_dim
         self.p = {k: v.to(self.device) for k, v in params.items()}
+        # int4: name -> (packed codes, scales) of the layer projections (fused backend only)
+        self.w4: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self.w4_max_rows = self.w4_variant = 0
+        if weight_dtype == "int4":
+            for i in range(cfg.layers):
+                for n in ("qkv", "o", "gate", "up", "down"):
+                    N_, K_ = self.p[f"l{i}.{n}"].shape
+                    if K_ % R.W4_GROUP or (backend == "fused" and N_ % (8 if n in ("gate", "up") else 16)):
+                        raise ValueError(f"weight_dtype='int4': l{i}.{n} is [{N_}, {K_}] on this rank (tp {tp}); "
+                                         f"needs K % {R.W4_GROUP} == 0" + (", N % 16 == 0" if backend == "fused" else ""))
+        if weight_dtype == "int4" and backend != "fused":
+            # the CPU oracle: gains folded as ops.fold_norm (fp32 product, one bf16 rounding), then the
+            # exact dequantised product as the weights; the folded norms become ones
+            for i in range(cfg.layers):
+                for n, gain in (("qkv", "attn_norm"), ("gate", "mlp_norm"), ("up", "mlp_norm"), ("o", None), ("down", None)):
+                    w = self.p[f"l{i}.{n}"]
+                    if gain is not None:
+                        w = (w.float() * self.p[f"l{i}.{gain}"].float().view(1, -1)).to(w.dtype)
+                    self.p[f"l{i}.{n}"] = R.w4_dequant(*R.w4_quant(w))
+                for gain in ("attn_norm", "mlp_norm"):
+                    self.p[f"l{i}.{gain}"] = torch.ones_like(self.p[f"l{i}.{gain}"])
         if backend == "fused":
             from .. import ops
 
@@ -459,6 +492,22 @@ class LlamaTP:
                 self.p[f"l{i}.gate_up"] = ops.fold_norm(gu, mlp_g)
                 self.p[f"l{i}.qkv"] = ops.fold_norm(self.p[f"l{i}.qkv"], self.p.pop(f"l{i}.attn_norm"))
             self.p["lm_head"] = ops.fold_norm(self.p["lm_head"], self.p.pop("final_norm"))
+            if weight_dtype == "int4":
+                # quantised as held here (gain folded, gate / up interleaved: a row permutation).  p
+                # keeps the bf16 rounding of the dequantised matrix for the > w4_max_rows GEMMs
+                # (prefill, chunked prefill), w4 the packed codes the decode steps stream; no
+                # granule-packed bf16 copy of these names below
+                for i in range(cfg.layers):
+                    for n in ("qkv", "o", "gate_up", "down"):
+                        q, sc = R.w4_quant(self.p[f"l{i}.{n}"])
+                        self.p[f"l{i}.{n}"] = R.w4_dequant(q, sc).to(torch.bfloat16)
+                        self.w4[f"l{i}.{n}"] = ops.pack_skinny_w4_codes(q, sc)
+                        del q, sc
+                # decode steps up to this many rows stream the int4 codes: the kernel's own limit, it was
+                # ahead of the bf16 routes at every row count measured, 1 to 32 (Llama-3-8B, batch 32:
+                # 4.13 vs 4.50 ms/step; profiles/w4_decode_ab.jsonl, docs/PERF_NOTES.md "W4A16 decode")
+                self.w4_max_rows = min(32, int(os.environ.get("MLS_W4_MAX_ROWS", "32")))
+                self.w4_variant = int(os.environ.get("MLS_W4_VARIANT", "0"))  # probe knob: the launch shape
             # Decode (<= 24 tokens per step) streams a second, granule-packed copy of every projection
             # (ops.pack_skinny: each wave reads contiguous 1 KiB granules, non-temporal): 3.4-4.5 ->
             # 4.6-6.2 TB/s on the Llama-3-8B shapes (profiles/r2_decode_packed_weight_probe.jsonl).
@@ -478,7 +527,7 @@ class LlamaTP:
                 names = [f"l{i}.{n}" for i in range(cfg.layers) for n in ("qkv", "o", "gate_up", "down")]
                 names.append("lm_head")
                 names = [n for n in names if self.p[n].shape[0] % 16 == 0 and self.p[n].shape[1] % 32 == 0
-                         and self.p[n].numel() * 2 < (1 << 31)]
+                         and self.p[n].numel() * 2 < (1 << 31) and n not in self.w4]
                 total = sum(self.p[n].numel() * 2 for n in names)
                 cap = torch.cuda.get_device_properties(self.device).total_memory
                 if mode == "1" or total <= cap // 4:
@@ -497,7 +546,7 @@ class LlamaTP:
                 min_el = int(os.environ.get("MLS_DECODE_FP8_MIN", str(1 << 24)))
                 self.fp8 = {n: ops.pack_skinny_fp8(self.p[n]) for n in names
                             if self.p[n].shape[0] % 16 == 0 and self.p[n].shape[1] % 64 == 0
-                            and min_el <= self.p[n].numel() < (1 << 31)}
+                            and min_el <= self.p[n].numel() < (1 << 31) and n not in self.w4}  # int4 wins
             self.ones = torch.ones(cfg.hidden, device=self.device, dtype=torch.bfloat16)
             self.workspace = torch.empty(32 << 20, device=self.device, dtype=torch.float32)
             self.dec_chunk = int(os.environ.get("MLS_DEC_CHUNK", "0"))  # 0: auto (see _fused_forward)
@@ -565,6 +614,16 @@ class LlamaTP:
     @property
     def qkv_width(self) -> int:
         return (self.sd.hq + 2 * self.sd.hkv) * self.cfg.head_dim
+
+    def layer_weight_bytes(self) -> int:
+        """Bytes of the layer projections a decode step streams on this rank: the int4 codes + scales
+        where the model holds them (fused ``weight_dtype="int4"``), else the matrices as held."""
+        total = 0
+        for name, w in self.p.items():
+            if name.rsplit(".", 1)[-1] in ("qkv", "o", "gate", "up", "gate_up", "down"):
+                held = self.w4.get(name, (w,))
+                total += sum(t.numel() * t.element_size() for t in held)
+        return total
 
     def _embed(self, ids: torch.Tensor) -> torch.Tensor:
         sd = self.sd
@@ -704,11 +763,14 @@ class LlamaTP:
         # every column-tile block re-reads A, and the row-major split-K kernel is ahead (batch 24:
         # 4.99 vs 5.36 ms/step, batch 32: 5.75 vs 5.64; profiles/r2_llama8b_decode_packed_ab.jsonl)
         packed = self.packed if T <= 24 else {}
+        # weight_dtype="int4": the layer projections stream their 4-bit codes (ops.skinny_w4) instead;
+        # no all-reduce tail / combine prologue there, so those run as separate launches
+        w4 = self.w4 if T <= self.w4_max_rows else {}
 
         # TP = 1: the residual add rides in the o / down epilogues (h = r + a Wo^T, r' = h + g Wd^T), so
         # the next pre-norm GEMM reads one activation stream instead of two (r + delta) and writes no
         # residual copy.  With TP > 1 the add has to wait for the all-reduce.
-        fold = self.tp == 1 and ((bool(packed) and self.pk_fold) or (not decode and getattr(self, "prefill_fold", False)))
+        fold = self.tp == 1 and (((bool(packed) or bool(w4)) and self.pk_fold) or (not decode and getattr(self, "prefill_fold", False)))
         # decode: the o-projection merges the split-KV partials in its prologue (one launch instead of
         # two) while every block's share of partials is small -- B x local q heads <= 32: one emulated
         # TP = 8 rank 1.166 -> 1.125 ms/token at batch 1, 1.294 -> 1.254 at 4; TP = 1 batch 1 level,
@@ -738,6 +800,8 @@ class LlamaTP:
             return self.comm.all_reduce_(linear(x, name))
 
         def linear(x, name, residual=None):
+            if name in w4:
+                return ops.skinny_w4(x, *w4[name], p[name].shape[0], residual=residual, variant=self.w4_variant)
             if use_fp8(name, x.shape[1]):
                 q, sc = fp8[name]
                 return ops.skinny_fp8(x, q, sc, p[name].shape[0], residual=residual)
@@ -765,6 +829,11 @@ class LlamaTP:
             if xn_pending[0] is not None:
                 xn, xn_pending[0] = xn_pending[0], None
                 return ops.linear(xn, w, act=act, workspace=ws), x
+            if name in w4:
+                r_new = None if d is None else torch.empty_like(x)
+                y = ops.skinny_w4(x, *w4[name], w.shape[0], delta=d, resid_out=r_new, norm=True, act=act, eps=eps,
+                                  variant=self.w4_variant)
+                return y, (x if d is None else r_new)
             if use_fp8(name, x.shape[1]):
                 q, sc = fp8[name]
                 r_new = None if d is None else torch.empty_like(x)
@@ -873,7 +942,8 @@ class LlamaTP:
         elif B <= 16:
             logits = ops.gemm_rmsnorm(r, p["lm_head"], delta, eps=eps, workspace=ws)
         else:  # 1 GB of weights: the weight-streaming native tile up to 64 rows, the tile GEMM above
-            xn = ops.rmsnorm(delta, self.ones, residual=r, eps=eps)
+            # (delta is None when the residual adds rode in the o / down epilogues: int4 steps of 25-32 rows)
+            xn = ops.rmsnorm(r, self.ones, eps=eps) if delta is None else ops.rmsnorm(delta, self.ones, residual=r, eps=eps)
             logits = ops.linear(xn, p["lm_head"], workspace=ws, impl="native" if B <= 64 else "auto")
         return self._local_topk(logits, k)
 

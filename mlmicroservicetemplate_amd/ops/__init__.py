@@ -47,12 +47,18 @@ from .gemm_ops import (  # noqa: F401
     pack_skinny,
     pack_skinny_fp8,
     pack_skinny_reference,
+    pack_skinny_w4,
+    pack_skinny_w4_codes,
     silu_mul_interleaved,
     skinny_fp8,
     mgemm,
     skinny_packed,
     skinny_packed_ar,
+    skinny_w4,
     split_counters,
+    unpack_skinny_w4_reference,
+    w4_reference,
+    W4_VARIANTS,
 )
 from .dispatch import (  # noqa: F401
     BLAS_MIN_M,

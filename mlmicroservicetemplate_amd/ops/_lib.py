@@ -109,6 +109,8 @@ _SIGS = {
     "mls_skinny_packed_ar": [P, P, P, P, P, I, I, I, I, F, I, P, P],
     "mls_skinny_packed_combine_ar": [P, P, P, P, I, I, I, I, P, P, I, I, I, I, P, P],
     "mls_skinny_fp8": [P, P, P, P, P, P, P, P, I, I, I, I, I, F, I, P],
+    "mls_skinny_w4": [P, P, P, P, P, P, P, P, I, I, I, I, I, F, I, P],
+    "mls_skinny_w4_num_variants": [],
     "mls_stream_create_cumask": [P, I, _c.POINTER(P)],
     "mls_stream_get_cumask": [P, P, I],
     "mls_stream_destroy": [P],

@@ -432,6 +432,110 @@ def skinny_fp8(x: torch.Tensor, wq: torch.Tensor, wscale: torch.Tensor, N: int, 
     return out
 
 
+# nibble slot (4-bit position inside a 32-bit word) of a k-step's k-ordered weights e = 0..7:
+# e = 2p sits at bits 4p, e = 2p + 1 at bits 4p + 16
+_W4_SLOT = (0, 4, 1, 5, 2, 6, 3, 7)
+W4_VARIANTS = 13  # launch shapes of csrc/skinny_w4.hip (W4_SHAPES; 0: the launcher's pick)
+
+
+def pack_skinny_w4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``w [N, K]`` (N % 16 == 0, K % 128 == 0) -> (int4 weights in the 1 KiB granule layout of
+    :func:`skinny_w4`, flat uint8 ``[N * K / 2]``; bf16 scales ``[N/16][K/128][16]``, flat), quantised
+    by ``reference.w4_quant``.
+
+    One granule = one 16-row tile x 128 k = one scale group: ``[N/16][K/128][g=4][nr=16][kstep=4]``
+    32-bit words, so a lane's 16-byte load carries its MFMA B fragments (row ``nr``, k ``32 kstep +
+    8 g .. + 8``) of four consecutive k-steps.  A word holds the fragment's eight codes ``q + 8``;
+    weight ``e`` (k order) sits at bits ``4 * (e // 2) + 16 * (e % 2)``, so ``(word >> 4p) & 0x000F000F``
+    is the pair (e = 2p, 2p + 1) already in the two bf16 halves of the MFMA operand's dword ``p``."""
+    from .reference import w4_quant
+
+    N, K = w.shape
+    if N % 16 or K % 128:
+        raise ValueError("pack_skinny_w4: N % 16 == 0 and K % 128 == 0")
+    return pack_skinny_w4_codes(*w4_quant(w))
+
+
+def pack_skinny_w4_codes(q: torch.Tensor, scale: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`pack_skinny_w4` of already quantised weights: ``(q int8 [N, K], scale bf16 [N, K / 128])``."""
+    N, K = q.shape
+    if N % 16 or K % 128 or tuple(scale.shape) != (N, K // 128):
+        raise ValueError("pack_skinny_w4_codes: N % 16 == 0, K % 128 == 0, scale [N, K / 128]")
+    code = (q.to(torch.int64) + 8).view(N // 16, 16, K // 128, 4, 4, 8).permute(0, 2, 4, 1, 3, 5)  # [t][kg][g][nr][ks][e]
+    shift = torch.tensor([4 * s for s in _W4_SLOT], device=q.device, dtype=torch.int64)
+    words = (code << shift).sum(-1)  # disjoint bit fields
+    wq = words.contiguous().view(torch.uint8).view(-1, 8)[:, :4]  # the low 32 bits, little-endian
+    scales = scale.view(N // 16, 16, K // 128).permute(0, 2, 1)
+    return wq.contiguous().reshape(-1), scales.contiguous().reshape(-1)
+
+
+def unpack_skinny_w4_reference(wq: torch.Tensor, scales: torch.Tensor, N: int, K: int):
+    """Inverse of :func:`pack_skinny_w4`'s layout: ``(q int8 [N, K], scale bf16 [N, K / 128])``."""
+    b = wq.view(N // 16, K // 128, 4, 16, 4, 4).to(torch.int64)  # bytes of each little-endian word
+    words = b[..., 0] | (b[..., 1] << 8) | (b[..., 2] << 16) | (b[..., 3] << 24)
+    shift = torch.tensor([4 * s for s in _W4_SLOT], device=wq.device, dtype=torch.int64)
+    code = (words.unsqueeze(-1) >> shift) & 15  # [t][kg][g][nr][ks][e]
+    q = (code - 8).to(torch.int8).permute(0, 3, 1, 4, 2, 5).reshape(N, K)
+    scale = scales.view(N // 16, K // 128, 16).permute(0, 2, 1).reshape(N, K // 128)
+    return q.contiguous(), scale.contiguous()
+
+
+def w4_reference(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """fp32 ``x @ dequant(quant(w))^T``: the product :func:`skinny_w4` computes on the packed ``w``."""
+    from .reference import w4_dequant, w4_quant
+
+    return x.float() @ w4_dequant(*w4_quant(w)).T
+
+
+def skinny_w4(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, N: int, *,
+              delta: Optional[torch.Tensor] = None, resid_out: Optional[torch.Tensor] = None, norm: bool = False,
+              act=ACT_NONE, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+              eps: float = 1e-5, variant: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Decode product (M <= 32) against int4 weights (W4A16): ``act([RMSNorm](x [+ delta]) @ W^T + b
+    [+ residual])`` with ``(wq, scales)`` from :func:`pack_skinny_w4` (the RMSNorm gain folded into W
+    before quantising).  Activations stay bf16; the weights are expanded from nibbles in registers.
+    ``variant``: launch shape, see csrc/skinny_w4.hip (0: the launcher's pick)."""
+    dev = x.device
+    _need(x, "x", torch.bfloat16, dev)
+    M, K = x.shape
+    if (not 0 < M <= 32 or N % 16 or K % 128 or wq.dtype != torch.uint8 or wq.device != dev or not wq.is_contiguous()
+            or wq.numel() * 2 != N * K):
+        raise ValueError("skinny_w4: M <= 32, N % 16 == 0, K % 128 == 0, wq of N*K/2 uint8")
+    _need(scales, "scales", torch.bfloat16, dev)
+    if scales.numel() * 128 != N * K:
+        raise ValueError("skinny_w4: scales of N*K/128 elements")
+    if not 0 <= int(variant) < W4_VARIANTS:
+        raise ValueError(f"skinny_w4: variant in 0..{W4_VARIANTS - 1}")
+    if resid_out is not None and delta is None:
+        raise ValueError("resid_out needs delta")
+    if (delta is not None) and not norm:
+        raise ValueError("delta exists only with norm")
+    for name, t in (("delta", delta), ("resid_out", resid_out)):
+        if t is not None:
+            _need(t, name, torch.bfloat16, dev)
+            if tuple(t.shape) != (M, K):
+                raise ValueError(f"{name} must be [M, K]")
+    if bias is not None:
+        _need(bias, "bias", torch.float32, dev)
+        if bias.numel() != N:
+            raise ValueError("bias must have N elements")
+    if residual is not None:
+        _need(residual, "residual", torch.bfloat16, dev)
+        if tuple(residual.shape) != (M, N):
+            raise ValueError("residual must be [M, N]")
+    code = _act(act)
+    n_out = N // 2 if code == ACT_SILU_MUL else N
+    if out is None:
+        out = torch.empty(M, n_out, device=dev, dtype=torch.bfloat16)
+    elif tuple(out.shape) != (M, n_out) or out.dtype != torch.bfloat16 or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous bf16 [M, {n_out}]")
+    rc = lib().mls_skinny_w4(x.data_ptr(), _ptr(delta), _ptr(resid_out), wq.data_ptr(), scales.data_ptr(),
+                             _ptr(bias), _ptr(residual), out.data_ptr(), M, N, K, code, int(norm), float(eps),
+                             int(variant), stream_ptr(dev))
+    check(rc, "mls_skinny_w4")
+    return out
+
+
 def fold_norm(w: torch.Tensor, gain: torch.Tensor) -> torch.Tensor:
     """``W[:, k] * gain[k]`` in fp32, rounded once to bf16: RMSNorm(x) @ W^T == rstd * (x @ fold^T)."""
     return (w.float() * gain.float().view(1, -1)).to(w.dtype)

@@ -140,5 +140,33 @@ def kv_dequant_fp8(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return q.view(torch.float8_e4m3fn).float() * scale.float().unsqueeze(-1)
 
 
+W4_GROUP = 128                 # k values that share one int4 scale
+W4_SCALE_FLOOR = 2.0 ** -40    # keeps the scale of an all-zero group non-zero (q = 0 there)
+
+
+def w4_quant(w: torch.Tensor, group: int = W4_GROUP) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The int4 (W4A16) weight rule for ``w [N, K]``, ``K % group == 0``: symmetric, per output row
+    and per ``group`` consecutive k: ``scale = max(bf16_rne(max|w_group| / 7), 2^-40)`` held as bf16,
+    ``q = clamp(rne(w / scale), -8, 7)`` held as int8.  ``scale * 7 * (1 + 2^-8) < 7.5 * scale``, so the
+    clamp never bites and ``|q * scale - w| <= scale / 2``.  Returns ``(int8 [N, K], bf16 [N, K / group])``."""
+    N, K = w.shape
+    if group != W4_GROUP or K % group:
+        raise ValueError(f"w4_quant: groups of {W4_GROUP} k values, K % {W4_GROUP} == 0 (got K {K}, group {group})")
+    wf = w.float().reshape(N, K // group, group)
+    amax = wf.abs().amax(dim=-1)
+    # tensor / tensor: a true IEEE division on every device
+    scale = (amax / torch.full_like(amax, 7.0)).to(torch.bfloat16)
+    scale = torch.clamp(scale.float(), min=W4_SCALE_FLOOR)
+    q = torch.clamp(torch.round(wf / scale.unsqueeze(-1)), -8, 7).to(torch.int8)
+    return q.reshape(N, K), scale.to(torch.bfloat16)
+
+
+def w4_dequant(q: torch.Tensor, scale: torch.Tensor, group: int = W4_GROUP) -> torch.Tensor:
+    """fp32 ``float(q) * float(scale)`` of :func:`w4_quant`'s output, the scale expanded over its group:
+    an exact product (4-bit times 8-bit significands) -- the quantised model's weights."""
+    N, K = q.shape
+    return (q.float().reshape(N, K // group, group) * scale.float().unsqueeze(-1)).reshape(N, K)
+
+
 def gelu(x):
     return F.gelu(x)

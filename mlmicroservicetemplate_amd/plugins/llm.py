@@ -45,6 +45,7 @@ class LlamaPlugin(ModelPlugin):
         self.ctx = ctx
         s = ctx.settings
         extra = s.model_yaml() if hasattr(s, "model_yaml") else {}
+        weight_dtype = self.parse_weight_dtype(extra)  # before any weight is read or allocated
         size = extra.get("config", "8b")
         cfg = llama.LLAMA3_8B if size == "8b" else llama.tiny_config(**extra.get("overrides", {}))
         tp = ctx.world_size if int(s.TP) > 1 else 1
@@ -73,7 +74,7 @@ class LlamaPlugin(ModelPlugin):
             kv_pages = int(-mdist.max_over_ranks(-float(kv_pages)))
         self.model = llama.LlamaTP(params, cfg, tp=tp, rank=ctx.rank, comm=llama.TPComm(None, tp, device=dev), backend=backend,
                                    device=dev, max_batch=max_batch, max_seq=max_seq, kv_pages=kv_pages,
-                                   kv_dtype=kv_dtype)
+                                   kv_dtype=kv_dtype, weight_dtype=weight_dtype)
         self.tok = llama.LlamaTokenizer(cfg, extra.get("tokenizer_file"))
         self.cfg = cfg
         self.engine = None
@@ -84,8 +85,18 @@ class LlamaPlugin(ModelPlugin):
                                           prefill_chunk=self.prefill_chunk)
             if ctx.rank == 0:
                 self.engine.start()
-        logger.info("llama ready: tp=%d rank=%d backend=%s device=%s kv_dtype=%s kv_bytes_per_token=%d", tp, ctx.rank,
-                    backend, dev, kv_dtype, self.kv_page_bytes(cfg, tp, backend, kv_dtype) // 64)
+        logger.info("llama ready: tp=%d rank=%d backend=%s device=%s kv_dtype=%s kv_bytes_per_token=%d "
+                    "weight_dtype=%s layer_weight_bytes=%d", tp, ctx.rank, backend, dev, kv_dtype,
+                    self.kv_page_bytes(cfg, tp, backend, kv_dtype) // 64, weight_dtype, self.model.layer_weight_bytes())
+
+    @staticmethod
+    def parse_weight_dtype(extra: dict) -> str:
+        """MODEL_CONFIG ``weight_dtype``: ``bf16`` (default) | ``int4`` (W4A16 layer projections,
+        :class:`~..models.llama.LlamaTP`)."""
+        wd = str(extra.get("weight_dtype", "bf16"))
+        if wd not in ("bf16", "int4"):
+            raise ValueError(f"weight_dtype must be 'bf16' or 'int4', got {wd!r}")
+        return wd
 
     @staticmethod
     def kv_page_bytes(cfg, tp: int, backend: str = "fused", kv_dtype: str = "bf16") -> int:

@@ -95,13 +95,14 @@ def bench_llama(args):
     p = init_llama_shard(LLAMA3_8B, tp, 0, seed=0, device=dev)
     comm = ShardEmulationComm(tp) if tp > 1 else None
     m = LlamaTP(p, LLAMA3_8B, tp=tp, rank=0, comm=comm, backend="fused", device=dev, max_batch=max(args.batches),
-                max_seq=args.max_seq, kv_pages=args.kv_pages, kv_dtype=args.kv_dtype)
+                max_seq=args.max_seq, kv_pages=args.kv_pages, kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype)
     if m.pages is not None and args.shuffle_pages:  # pages scattered as in a long-running server
         import random
 
         random.Random(0).shuffle(m.pages._free)
     print(json.dumps({"bench": "llama3-8b", "tp": tp, "collectives": "stubbed" if tp > 1 else "none",
                       "skinny_max_split": args.skinny_max_split, "kv_pages": args.kv_pages, "kv_dtype": args.kv_dtype,
+                      "weight_dtype": args.weight_dtype, "layer_weight_bytes": m.layer_weight_bytes(),
                       "init_s": round(time.time() - t0, 1)}), flush=True)
     for B in args.batches:
         S = args.prompt
@@ -132,7 +133,7 @@ def bench_llama(args):
         torch.cuda.synchronize()
         dec = (time.perf_counter() - t2) / n
         print(json.dumps({"bench": "llama3-8b", "tp": tp, "batch": B, "prompt": S, "kv_pages": args.kv_pages,
-                          "kv_dtype": args.kv_dtype, "prefill_ms": round(pre * 1e3, 2), "prefill_tok_s": round(B * S / pre, 1),
+                          "kv_dtype": args.kv_dtype, "weight_dtype": args.weight_dtype, "prefill_ms": round(pre * 1e3, 2), "prefill_tok_s": round(B * S / pre, 1),
                           "decode_ms_per_step": round(dec * 1e3, 3), "decode_tok_s": round(B / dec, 1)}), flush=True)
 
 
@@ -146,7 +147,7 @@ def bench_llama_serve(args):
     B = args.batches[0]
     p = init_llama_shard(LLAMA3_8B, 1, 0, seed=0, device=dev)
     m = LlamaTP(p, LLAMA3_8B, backend="fused", device=dev, max_batch=B, max_seq=args.max_seq, kv_pages=args.kv_pages,
-                kv_dtype=args.kv_dtype)
+                kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype)
     eng = ContinuousLlama(m).start()
     rng = np.random.default_rng(0)
     warm = [eng.submit(rng.integers(1000, 100000, args.prompt).tolist(), GenParams(4)) for _ in range(B)]
@@ -162,7 +163,7 @@ def bench_llama_serve(args):
     toks = sum(len(f.result()) for f in futs)
     eng.stop()
     print(json.dumps({"bench": "llama3-8b-continuous", "max_batch": B, "kv_pages": args.kv_pages,
-                      "kv_dtype": args.kv_dtype, "requests": args.requests,
+                      "kv_dtype": args.kv_dtype, "weight_dtype": args.weight_dtype, "requests": args.requests,
                       "prompt": args.prompt, "new_tokens": args.new, "tokens_per_s": round(toks / dt, 1),
                       "requests_per_s": round(args.requests / dt, 2), "p50_latency_s": round(float(np.median(lat)), 3),
                       "iterations": eng.iterations}), flush=True)
@@ -187,6 +188,8 @@ def main():
     ap.add_argument("--kv-pages", type=int, default=0, help="llama: paged KV pool of N 64-row pages (0: per-slot)")
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
                     help="llama: KV cache rows in bf16, or e4m3 with one fp32 scale per (row, KV head)")
+    ap.add_argument("--weight-dtype", choices=["bf16", "int4"], default="bf16",
+                    help="llama: layer projections in bf16, or W4A16 (4-bit codes, one bf16 scale per row and 128 k)")
     ap.add_argument("--max-seq", type=int, default=2048, help="llama: cache rows per sequence")
     ap.add_argument("--shuffle-pages", action="store_true", help="llama: hand out pages in random order")
     args = ap.parse_args()

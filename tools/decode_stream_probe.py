@@ -72,13 +72,29 @@ def main():
                     impls[f"fused_norm_packed_v{v}"] = (
                         lambda v=v: [ops.skinny_packed(x, wp, N, delta=d, resid_out=r_out, norm=True, act=act, variant=v)
                                      for wp in wp_list])
-        for impl, fn in impls.items():
-            t = _time(fn, iters=3) * 1e-3 / 32
-            print(json.dumps({"shape": name, "M": M, "impl": impl, "us_per_call": round(t * 1e6, 2),
-                              "hbm_tb_s": round(N * K * 2 / t / 1e12, 2)}), flush=True)
+        wbytes = {}  # weight bytes an impl reads per call, where not N K 2
+        if M <= 32 and os.environ.get("W4_VARIANTS"):  # W4A16 (ops.pack_skinny_w4): 4.25 bits per weight, variants of mls_skinny_w4
+            w4_list = [ops.pack_skinny_w4(w) for w in ws_list]
+            norm_fused = K == 4096 and name != "o"
+            for v in [int(t) for t in os.environ["W4_VARIANTS"].split(",")]:
+                impls[f"w4_v{v}"] = (lambda v=v: [ops.skinny_w4(x, q, sc, N, act=act, variant=v) for q, sc in w4_list])
+                if norm_fused:
+                    impls[f"fused_norm_w4_v{v}"] = (
+                        lambda v=v: [ops.skinny_w4(x, q, sc, N, delta=d, resid_out=r_out, norm=True, act=act, variant=v)
+                                     for q, sc in w4_list])
+            wbytes = {k: N * K // 2 + N * K // 128 * 2 for k in impls if "w4_v" in k}
+        only = [t for t in os.environ.get("ONLY", "").split(",") if t]  # impl name prefixes to time (default: all)
+        for rep in range(int(os.environ.get("REPEAT", "1"))):  # > 1: the impls alternate, for the spread
+            for impl, fn in impls.items():
+                if only and not any(impl.startswith(t) for t in only):
+                    continue
+                t = _time(fn, iters=3) * 1e-3 / 32
+                nb = wbytes.get(impl, N * K * 2)
+                print(json.dumps({"shape": name, "M": M, "impl": impl, "rep": rep, "us_per_call": round(t * 1e6, 2),
+                                  "weight_bytes": nb, "hbm_tb_s": round(nb / t / 1e12, 2)}), flush=True)
         del ws_list
         impls.clear()
-        wp_list = None
+        wp_list = w4_list = None
         torch.cuda.empty_cache()
 
 
