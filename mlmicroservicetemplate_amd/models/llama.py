@@ -553,6 +553,9 @@ class LlamaTP:
             self.dec_ws = torch.empty(max_batch * self.sd.hq * (-(-max_seq // 64)) * (D + 2) + 16,
                                       device=self.device, dtype=torch.float32)
             self.dec_cnt = torch.zeros(max_batch * self.sd.hkv, device=self.device, dtype=torch.int32)
+            self.ver_ws: Optional[torch.Tensor] = None  # split-KV partials of the uncaptured verify steps
+            self._ver_ws_graph: Optional[torch.Tensor] = None  # ... of the verify graph being warmed up / captured
+            self.verify_attn = os.environ.get("MLS_VERIFY_ATTN", "multi")  # "ctx": verify through flash_attention_ctx
         cdt = torch.bfloat16 if backend == "fused" else torch.float32
         # fused: head-major caches ([.., Hkv, rows, D]) -- one head's rows contiguous, so a decode split
         # block streams one 16 KiB run instead of 64 slices of 256 B (MLS_KV_HEAD_MAJOR=0: row-major)
@@ -600,6 +603,10 @@ class LlamaTP:
             tp == 1 or getattr(self.comm, "graph_safe", False) or self._rccl_graphs
             or getattr(self.comm, "car", None) is not None)
         self._graphs: Dict[Tuple[int, int, int], tuple] = {}
+        self._ver_graphs: Dict[Tuple[int, int, int, int, str], tuple] = {}
+        # speculative decoding: the most positions per sequence a verify step may carry (drafts + 1)
+        self.spec_max_tokens = 8
+        self.spec_stats = {"steps": 0, "drafted": 0, "accepted": 0}
         self._dec_ctx: Optional[int] = None  # host bound on decode context (sizes the split grid)
         # device-resident decode loop (X4 on device, _generate_device): per-batch-size static state
         # shared by the captured steps of every context bucket, so switching buckets copies nothing
@@ -710,12 +717,12 @@ class LlamaTP:
 
     def _ref_forward(self, ids: torch.Tensor, positions: torch.Tensor, lens: torch.Tensor, B: int, S: int,
                      decode: bool, k: int, slot_ids: Optional[torch.Tensor] = None,
-                     past: Optional[torch.Tensor] = None):
+                     past: Optional[torch.Tensor] = None, all_rows: bool = False):
         x = self._embed(ids.reshape(-1))
         for i in range(self.cfg.layers):
             x = self._ref_layer(i, x, B, S, positions.reshape(-1), lens, slot_ids, decode, past)
         xn = R.layernorm(x, self.p["final_norm"], None, eps=self.cfg.eps, rms=True)[0]
-        if not decode:
+        if not decode and not all_rows:
             n = lens.long() if past is None else lens.long() - past.long()  # valid rows of this forward
             last = (torch.arange(B, device=x.device) * S + n - 1)
             xn = xn[last]
@@ -725,7 +732,7 @@ class LlamaTP:
     # ---------------------------------------------------------------- fused backend
     def _fused_forward(self, ids: torch.Tensor, positions: torch.Tensor, lens: torch.Tensor, B: int, S: int,
                        decode: bool, k: int, slot_ids: Optional[torch.Tensor] = None,
-                       past: Optional[torch.Tensor] = None):
+                       past: Optional[torch.Tensor] = None, all_rows: bool = False):
         """Native-kernel forward.  The RMSNorm gains are folded into the following projections, so
         for decode-shaped token counts (<= 16) each pre-norm + residual add rides inside the skinny
         GEMM (``ops.gemm_rmsnorm``: 7 launches per layer); larger counts run a gain-free RMSNorm and
@@ -779,6 +786,25 @@ class LlamaTP:
                         and B * sd.hq <= 32 and B * sd.hq * D * 2 <= 65536)
 
         fp8 = self.fp8 if T <= 4 else {}
+        # a verify step (all_rows: every row's candidates) of a few positions per sequence: its attention
+        # runs split-KV on the matrix cores with the T positions x G heads of a KV head on one MFMA's lane
+        # columns (ops.decode_attention_multi); MLS_VERIFY_ATTN=ctx keeps the chunk kernel (the A/B arm).
+        # Chunked prefill (all_rows False) stays on flash_attention_ctx.
+        multi = (past is not None and all_rows and self.verify_attn != "ctx" and S <= self.spec_max_tokens
+                 and S * (sd.hq // max(sd.hkv, 1)) <= 16)
+        if multi:
+            chunk_v = self.page_rows if self.pages is not None else (dec_chunk if dec_chunk in (64, 128) else 64)
+            cap_v = self.pages.pages_per_seq * self.page_rows if self.pages is not None else self.max_seq
+            need = T * sd.hq * (-(-min(self._dec_ctx or cap_v, cap_v) // chunk_v)) * (D + 2)
+            # a captured step owns its workspace (_verify_graph keeps it alive with the graph, whose launches
+            # hold its address); only the uncaptured steps share one, which may therefore be regrown
+            ws_v = self._ver_ws_graph
+            if ws_v is None:
+                if self.ver_ws is None or self.ver_ws.numel() < need:
+                    self.ver_ws = torch.empty(need, device=self.device, dtype=torch.float32)
+                ws_v = self.ver_ws
+            elif ws_v.numel() < need:
+                ws_v = self._ver_ws_graph = torch.empty(need, device=self.device, dtype=torch.float32)
 
         def use_fp8(name, K):
             return name in fp8 and T * K * 2 <= 65536
@@ -888,7 +914,12 @@ class LlamaTP:
                 else:
                     ops.rope_kv_(qkv, pos, self.cos, self.sin, sd.hq, sd.hkv, D, explicit_slots, self.k_cache[i],
                                  self.v_cache[i], lens=lens, seq=S, max_seq=self.max_seq, hm_rows=self.kv_hm_rows)
-                if past is not None:  # chunked prefill: the chunk's queries against the cache rows just written
+                if multi:
+                    a = ops.decode_attention_multi(qkv, self.k_cache[i], self.v_cache[i], past, lens, B, S, sd.hq,
+                                                   sd.hkv, D, slot_ids=sid, chunk=chunk_v, max_len=self._dec_ctx,
+                                                   page_table=self.pages.dev if self.pages is not None else None,
+                                                   workspace=ws_v)
+                elif past is not None:  # chunked prefill: the chunk's queries against the cache rows just written
                     a = ops.flash_attention_ctx(qkv, self.k_cache[i], self.v_cache[i], past, lens, B, S, sd.hq, sd.hkv,
                                                 D, slot_ids=sid,
                                                 page_table=self.pages.dev if self.pages is not None else None)
@@ -927,24 +958,25 @@ class LlamaTP:
             o = row_parallel(a, f"l{i}.o")
             gu, r = pre_norm(r, f"l{i}.gate_up", o, act=ops.ACT_SILU_MUL)
             delta = row_parallel(gu, f"l{i}.down")
-        if not decode:  # each sequence's last valid token (one native gather of r and delta)
+        if not decode and not all_rows:  # each sequence's last valid token (one native gather of r and delta)
             rows = lens if past is None else lens - past  # valid rows of this forward (on the device)
             if delta is None:
                 r = ops.last_rows(r, rows, B, S)
             else:
                 r, delta = ops.last_rows(r, rows, B, S, delta)
-        if B <= 4 and "lm_head" in self.fp8 and B * r.shape[1] * 2 <= 65536:
+        nb = r.shape[0]  # rows that reach the lm_head: B, or every row of the step (all_rows)
+        if nb <= 4 and "lm_head" in self.fp8 and nb * r.shape[1] * 2 <= 65536:
             q, sc = self.fp8["lm_head"]
             logits = ops.skinny_fp8(r, q, sc, p["lm_head"].shape[0], delta=delta, norm=True, eps=eps)
-        elif B <= 24 and "lm_head" in self.packed:
+        elif nb <= 24 and "lm_head" in self.packed:
             logits = ops.skinny_packed(r, self.packed["lm_head"], p["lm_head"].shape[0], delta=delta, norm=True,
                                        eps=eps, variant=self.pk_variant)
-        elif B <= 16:
+        elif nb <= 16:
             logits = ops.gemm_rmsnorm(r, p["lm_head"], delta, eps=eps, workspace=ws)
         else:  # 1 GB of weights: the weight-streaming native tile up to 64 rows, the tile GEMM above
             # (delta is None when the residual adds rode in the o / down epilogues: int4 steps of 25-32 rows)
             xn = ops.rmsnorm(r, self.ones, eps=eps) if delta is None else ops.rmsnorm(delta, self.ones, residual=r, eps=eps)
-            logits = ops.linear(xn, p["lm_head"], workspace=ws, impl="native" if B <= 64 else "auto")
+            logits = ops.linear(xn, p["lm_head"], workspace=ws, impl="native" if nb <= 64 else "auto")
         return self._local_topk(logits, k)
 
     def _prefill_overlapped(self, r, pos, lens, B: int, S: int, explicit_slots, pre_norm, linear):
@@ -1020,16 +1052,112 @@ class LlamaTP:
             if self.cfg.head_dim != 128:
                 raise ValueError(f"chunked prefill on the fused backend needs head_dim 128 (got {self.cfg.head_dim})")
 
+    def check_speculate(self, speculate: int = 1) -> None:
+        """Speculative decoding (``verify_step`` of ``speculate + 1`` positions per sequence) reads its
+        context from the KV cache like a prefill chunk: raises ``ValueError`` for what that refuses and,
+        on the fused backend, for more positions x query heads per KV head than the verify attention's
+        16 lane columns (nothing falls back to the chunk kernel)."""
+        speculate = int(speculate)
+        if speculate < 1 or speculate + 1 > self.spec_max_tokens:
+            raise ValueError(f"speculate must be in [1, {self.spec_max_tokens - 1}], got {speculate}")
+        try:
+            self.check_prefill_chunk()
+        except ValueError as e:
+            raise ValueError(str(e).replace("chunked prefill", "speculative decoding")) from None
+        if self.backend == "fused":
+            G = self.sd.hq // max(self.sd.hkv, 1)
+            if G not in (1, 2, 4, 8) or (speculate + 1) * G > 16:
+                raise ValueError(f"speculative decoding on the fused backend needs Hq / Hkv in 1, 2, 4, 8 and "
+                                 f"(speculate + 1) * Hq / Hkv <= 16 (got speculate {speculate}, "
+                                 f"{self.sd.hq} / {self.sd.hkv} heads on this rank)")
+
+    def _verify_graph(self, B: int, T: int, k: int, ctx: int):
+        """Captured verify step for B sequences of T positions under the context bound ctx (static id /
+        past / lens / slot buffers, as :meth:`_decode_graph`).  Warm-up and capture run with
+        ``lens == past``: every row is padding, so no cache row is written."""
+        key = (B, T, k, ctx, getattr(self, "verify_attn", "multi"))  # one graph per attention route (A/B arms)
+        if key in self._ver_graphs:
+            return self._ver_graphs[key]
+        dev = self.device
+        ids = torch.zeros(B, T, dtype=torch.int32, device=dev)
+        past = torch.zeros(B, dtype=torch.int32, device=dev)
+        lens = torch.zeros(B, dtype=torch.int32, device=dev)
+        slots = torch.arange(B, dtype=torch.int32, device=dev)
+        off = torch.arange(T, dtype=torch.int32, device=dev).unsqueeze(0)
+        if self.pages is not None:
+            self.pages.device_table()
+        self._dec_ctx = ctx
+        # this graph's own split-KV workspace: the first warm-up step sizes it, the capture bakes its address
+        self._ver_ws_graph = torch.empty(0, device=dev, dtype=torch.float32)
+        try:
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    self.step(ids, past.unsqueeze(1) + off, lens, decode=False, k=k, slot_ids=slots, past=past,
+                              all_rows=True)
+            torch.cuda.current_stream(dev).wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                vals, idx = self.step(ids, past.unsqueeze(1) + off, lens, decode=False, k=k, slot_ids=slots,
+                                      past=past, all_rows=True)
+        finally:
+            self._dec_ctx = None
+            ws, self._ver_ws_graph = self._ver_ws_graph, None
+        # off and ws stay referenced: the captured launches read / write them at every replay
+        self._ver_graphs[key] = (g, ids, past, lens, slots, vals, idx, off, ws)
+        return self._ver_graphs[key]
+
+    @torch.no_grad()
+    def verify_step(self, ids: torch.Tensor, past: torch.Tensor, n: torch.Tensor, k: int,
+                    slot_ids: Optional[torch.Tensor] = None, max_ctx: Optional[int] = None):
+        """Speculative decoding's one forward: row b feeds ``n[b] <= T`` tokens ``ids[b, :n[b]]`` at
+        positions ``past[b] ..`` of cache slot ``slot_ids[b]`` (default b) and gets the local top-k of
+        every position, ``(vals, idx) [B, T, k]``.  Rows ``t >= n[b]`` are padding: never stored, their
+        candidates unspecified.  ``max_ctx``: a host bound on ``past + n`` (sizes the split grid).  On
+        the fused backend the step is a graph replay per (B, T, k, context bucket)."""
+        B, T = ids.shape
+        dev = self.device
+        self.check_speculate(max(1, T - 1))
+        ids = ids.to(dev).to(torch.int32)
+        past = past.to(dev).to(torch.int32).view(B)
+        lens = past + n.to(dev).to(torch.int32).view(B)
+        slots = (torch.arange(B, dtype=torch.int32, device=dev) if slot_ids is None
+                 else slot_ids.to(dev).to(torch.int32).view(B))
+        ctx = self.ctx_bucket(max_ctx)
+        if self.use_graphs and self._graph_ok(B * T):
+            g, i_s, p_s, l_s, s_s, v_s, x_s = self._verify_graph(B, T, k, ctx)[:7]
+            if self.pages is not None:
+                self.pages.device_table()  # the graph reads the table buffer in place
+            i_s.copy_(ids)
+            p_s.copy_(past)
+            l_s.copy_(lens)
+            s_s.copy_(slots)
+            with tracing.range("llama.verify"):
+                g.replay()
+            return v_s.view(B, T, -1), x_s.view(B, T, -1)
+        pos = past.unsqueeze(1) + torch.arange(T, dtype=torch.int32, device=dev).unsqueeze(0)
+        self._dec_ctx = ctx if self.backend == "fused" else None
+        try:
+            vals, idx = self.step(ids, pos, lens, decode=False, k=k, slot_ids=slots, past=past, all_rows=True)
+        finally:
+            self._dec_ctx = None
+        return vals.view(B, T, -1), idx.view(B, T, -1)
+
     @torch.no_grad()
     def step(self, ids: torch.Tensor, positions: torch.Tensor, lens: torch.Tensor, decode: bool, k: int,
-             slot_ids: Optional[torch.Tensor] = None, past: Optional[torch.Tensor] = None):
+             slot_ids: Optional[torch.Tensor] = None, past: Optional[torch.Tensor] = None, all_rows: bool = False):
         """One forward.  ``slot_ids`` (prefill only): cache row of each batch row (default: the
         batch row itself) -- how continuous batching prefills new requests into free slots.
         ``past`` (prefill only, int32 ``[B]``): rows of each sequence already in the cache -- this
         forward is the chunk at ``positions`` ``past[b] + i`` (absolute), ``lens`` the absolute end
         after it; its attention reads the cache (``ops.flash_attention_ctx``) and the returned
-        candidates are those of row ``lens[b] - past[b] - 1``."""
+        candidates are those of row ``lens[b] - past[b] - 1``.
+        ``all_rows`` (with ``past``): the candidates of EVERY row, ``[B*S, k]`` -- a speculative-decoding
+        verify step (:meth:`verify_step`); rows at or past ``lens[b] - past[b]`` are padding."""
         B, S = ids.shape
+        if all_rows and past is None:
+            raise ValueError("all_rows needs past (a verify step reads its context from the cache)")
         ids, positions, lens = ids.contiguous(), positions.contiguous(), lens.contiguous()
         if past is not None:
             if decode:
@@ -1043,8 +1171,8 @@ class LlamaTP:
         with tracing.range("llama.decode" if decode else "llama.prefill"):
             if self.backend == "fused":
                 return self._fused_forward(ids.to(torch.int32), positions.to(torch.int32), lens.to(torch.int32), B,
-                                           S, decode, k, slot_ids, past)
-            return self._ref_forward(ids, positions, lens, B, S, decode, k, slot_ids, past)
+                                           S, decode, k, slot_ids, past, all_rows)
+            return self._ref_forward(ids, positions, lens, B, S, decode, k, slot_ids, past, all_rows)
 
     @torch.no_grad()
     def prefill_chunked(self, ids: torch.Tensor, lens: torch.Tensor, chunk: int, k: int,
@@ -1189,16 +1317,26 @@ class LlamaTP:
             self._dec_ctx = None
 
     @torch.no_grad()
-    def generate(self, ids: torch.Tensor, lens: torch.Tensor, gp: GenParams, prefill_chunk: int = 0) -> torch.Tensor:
+    def generate(self, ids: torch.Tensor, lens: torch.Tensor, gp: GenParams, prefill_chunk: int = 0,
+                 speculate: int = 0, drafter=None) -> torch.Tensor:
         """ids int ``[B, S]`` (right-padded), lens ``[B]`` -> generated ``[B, max_new_tokens]``.
         ``prefill_chunk = N > 0``: the prompts are prefilled N positions at a time
-        (:meth:`prefill_chunked`) instead of in one forward."""
+        (:meth:`prefill_chunked`) instead of in one forward.
+        ``speculate = K > 0``: speculative decoding (models/speculative.py) -- each sequence proposes up to
+        K draft tokens (``drafter(tokens, n_draft)``, default prompt lookup), one :meth:`verify_step`
+        scores them and the sequence keeps the drafts that equal what it would have sampled anyway; a
+        host loop, ``self.spec_stats`` counts its steps / drafted / accepted tokens."""
         B, S = ids.shape
         prefill_chunk = int(prefill_chunk)
         if prefill_chunk < 0:
             raise ValueError(f"prefill_chunk must be >= 0, got {prefill_chunk}")
         if prefill_chunk:
             self.check_prefill_chunk()
+        speculate = int(speculate)
+        if speculate < 0:
+            raise ValueError(f"speculate must be >= 0, got {speculate}")
+        if speculate:
+            self.check_speculate(speculate)
         if B > self.max_batch or S + gp.max_new_tokens > self.max_seq:
             raise ValueError("batch / sequence exceed the KV cache")
         lens_host = lens.detach().to("cpu")
@@ -1208,7 +1346,7 @@ class LlamaTP:
         ids = ids.to(dev)
         lens = lens.to(dev).to(torch.int32)
         k = max(1, min(gp.top_k, self.top_k_max))
-        if self._device_loop_ok(B, k):
+        if not speculate and self._device_loop_ok(B, k):
             return self._generate_device(ids, lens, gp, k, prefill_chunk)
         assigned = 0
         try:
@@ -1217,6 +1355,8 @@ class LlamaTP:
                     self.pages.assign(b, S + gp.max_new_tokens)
                     assigned = b + 1
             vals, idx = self._prefill(ids, lens, k, prefill_chunk)
+            if speculate:
+                return self._generate_speculative(ids, lens_host, vals, idx, gp, k, speculate, drafter)
             out = []
             tok = self._sample_rows(vals, idx, gp, 0)
             out.append(tok)
@@ -1232,6 +1372,45 @@ class LlamaTP:
             if self.pages is not None:  # also on OutOfPages part-way: release exactly the rows assigned
                 for b in range(assigned):
                     self.pages.release(b)
+
+    def _generate_speculative(self, ids: torch.Tensor, lens_host: torch.Tensor, vals, idx, gp: GenParams, k: int,
+                              K: int, drafter) -> torch.Tensor:
+        """generate()'s decode loop with K drafts per sequence and step: rows advance at their own rate
+        and drop out of the verify batch (``slot_ids``) once they hold ``max_new_tokens``.  Every rank
+        drafts from the same tokens and accepts from the same gathered candidates: no new message."""
+        from . import speculative as SP
+
+        B, S = ids.shape
+        drafter = drafter or SP.prompt_lookup_draft
+        ids_h = ids.to("cpu")
+        seqs = [ids_h[b, : int(lens_host[b])].tolist() for b in range(B)]  # prompt + generated, per row
+        first = self._sample_rows(vals, idx, gp, 0).tolist()
+        outs: List[List[int]] = [[int(first[b])] for b in range(B)]
+        cur = [int(x) for x in lens_host.tolist()]  # position of each row's last emitted token
+        st = self.spec_stats = {"steps": 0, "drafted": 0, "accepted": 0}
+        T = K + 1
+        while True:
+            rows = [b for b in range(B) if len(outs[b]) < gp.max_new_tokens]
+            if not rows:
+                break
+            feeds = [SP.spec_feed(seqs[b] + outs[b], K, gp.max_new_tokens - len(outs[b]), drafter) for b in rows]
+            ft = torch.zeros(len(rows), T, dtype=torch.int32)
+            for j, f in enumerate(feeds):
+                ft[j, : len(f)] = torch.tensor(f, dtype=torch.int32)
+            n = torch.tensor([len(f) for f in feeds], dtype=torch.int32)
+            past = torch.tensor([cur[b] for b in rows], dtype=torch.int32)
+            v, i = self.verify_step(ft, past, n, k, slot_ids=torch.tensor(rows, dtype=torch.int32),
+                                    max_ctx=int((past + n).max()))
+            cv, ci = self.gather_candidates(v.reshape(len(rows) * T, -1), i.reshape(len(rows) * T, -1))
+            st["steps"] += 1
+            for j, b in enumerate(rows):
+                e = len(outs[b])
+                got = SP.accept(feeds[j], lambda t: self.pick_token(cv[j * T + t], ci[j * T + t], gp, e + t))
+                outs[b] += got
+                cur[b] += len(got)
+                st["drafted"] += len(feeds[j]) - 1
+                st["accepted"] += len(got) - 1
+        return torch.tensor(outs, dtype=torch.int32)
 
     # ---------------------------------------------------------------- device-resident decode loop
     def _gather_pad(self, k: int) -> int:
@@ -1412,6 +1591,7 @@ class LlamaTP:
             car.reset()
             self.comm.car = None
             self._graphs.clear()
+            self._ver_graphs.clear()
             self._dev_graphs.clear()
             raise TPCommError("a tensor-parallel peer missed a one-shot collective; falling back to RCCL")
 

@@ -24,6 +24,15 @@ dummy decode row goes to its first unwritten row (``pos = rows done``), which th
 overwrites, never to row 0 of its live prompt.  The chunk plan is a function of the slots alone, so
 TP followers replaying rank 0's admissions compute the same chunks.
 
+Speculative decoding (``ContinuousLlama(speculate=K)``, opt-in, models/speculative.py): while ``1 <=
+decoding sequences <= 16 // (K + 1)`` step 2 is one ``LlamaTP.verify_step`` over the decoding slots
+only -- each proposes up to K draft tokens (prompt lookup unless a ``drafter`` is given) and keeps the
+longest prefix that equals what it would have sampled anyway, so a step yields 1 to K + 1 tokens per
+sequence and the tokens are those of ``speculate=0``.  With more sequences in flight it is the normal
+decode step.  The choice is a function of the slots alone.  Iterations run on the host path (the
+device-resident iteration picks one token per slot), and TP > 1 is refused: the carried-header
+protocol is tied to the device iterations (follow-up).
+
 Each sequence samples with its own parameters and the same seeded rule as a batch-of-one
 ``LlamaTP.generate`` (``pick_token``), so results do not depend on what else is in flight.
 
@@ -106,7 +115,7 @@ class _Seq:
 class ContinuousLlama:
     def __init__(self, model: LlamaTP, max_queue: int = 4096,
                  broadcast: Optional[Callable[[Optional[List[_Seq]]], Optional[List[_Seq]]]] = None,
-                 channel=None, prefill_chunk: int = 0):
+                 channel=None, prefill_chunk: int = 0, speculate: int = 0, drafter=None):
         """``prefill_chunk = N > 0`` (chunked prefill): an admitted prompt advances by at most N
         positions per iteration, batched over all prefilling slots, and the decoding slots get their
         step in the same iteration -- a long prompt no longer holds every decoding sequence for its
@@ -116,6 +125,16 @@ class ContinuousLlama:
             raise ValueError(f"prefill_chunk must be >= 0, got {prefill_chunk}")
         if self.prefill_chunk:
             model.check_prefill_chunk()  # ValueError: fp8 KV cache, row-major cache, head_dim != 128
+        self.speculate = int(speculate)
+        if self.speculate < 0:
+            raise ValueError(f"speculate must be >= 0, got {speculate}")
+        if self.speculate:
+            if model.tp > 1:
+                raise ValueError("speculate is not available with tp > 1 in the continuous engine: its iterations "
+                                 "run on the host path, the TP header protocol rides the device iterations")
+            model.check_speculate(self.speculate)  # ValueError: what chunked prefill refuses, T * G > 16 (fused)
+        self.drafter = drafter
+        self.spec = {"spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0}
         self.m = model
         self.B = model.max_batch
         self.max_queue = max_queue
@@ -192,6 +211,8 @@ class ContinuousLlama:
         if self.m.pages is not None:
             d["kv_pages_free"] = self.m.pages.free_pages
             d["kv_pages"] = self.m.pages.num_pages
+        if self.speculate:
+            d.update(self.spec)
         return d
 
     # ---------------------------------------------------------------- scheduler (rank 0)
@@ -379,7 +400,7 @@ class ContinuousLlama:
 
     # ---------------------------------------------------------------- one iteration (all ranks)
     def _dev_ok(self) -> bool:
-        if not self._want_dev:
+        if not self._want_dev or self.speculate:  # a verify step emits a variable number of tokens: host path
             return False
         if any(s is not None for s in self.slots):  # sequences in flight keep their mode
             return self.dev_mode
@@ -443,7 +464,10 @@ class ContinuousLlama:
             self.tokens += len(fin)
             done += self._retire()
         active = [s for s in self.slots if s is not None and s.done >= len(s.ids)]
-        if active:
+        if self._spec_ok(active):
+            self._spec_step(active)
+            done += self._retire()
+        elif active:
             # a slot still prefilling decodes its dummy token into its first unwritten row (the next
             # chunk overwrites it; prompt + max_new_tokens <= max_seq keeps it in bounds) -- row 0, the
             # idle slots' dummy row, already holds its prompt
@@ -670,7 +694,10 @@ class ContinuousLlama:
             self.tokens += len(admit)
             done += self._retire()
         active = [s for s in self.slots if s is not None]
-        if active:
+        if self._spec_ok(active):
+            self._spec_step(active)
+            done += self._retire()
+        elif active:
             # host lists -> one tensor each (per-element tensor writes cost ~us apiece at 128 slots)
             tok_l, cur_l = [0] * self.B, [0] * self.B
             for s in active:
@@ -690,6 +717,38 @@ class ContinuousLlama:
             done += self._retire()
         self.iterations += 1
         return done
+
+    def _spec_ok(self, active: List[_Seq]) -> bool:
+        """Is this iteration's decode step a verify step?  A function of the slots alone."""
+        return self.speculate > 0 and 1 <= len(active) <= 16 // (self.speculate + 1)
+
+    def _spec_step(self, active: List[_Seq]) -> None:
+        """One verify step over the decoding slots: each feeds its last token and its drafts, and emits
+        the picks of the rows its drafts reached (``speculative.accept``), up to its first EOS."""
+        from . import speculative as SP
+
+        m, K = self.m, self.speculate
+        T = K + 1
+        drafter = self.drafter or SP.prompt_lookup_draft
+        feeds = [SP.spec_feed(s.ids + s.out, K, s.gp.max_new_tokens - len(s.out), drafter) for s in active]
+        ids = torch.zeros(len(active), T, dtype=torch.int32)
+        for j, f in enumerate(feeds):
+            ids[j, : len(f)] = torch.tensor(f, dtype=torch.int32)
+        n = torch.tensor([len(f) for f in feeds], dtype=torch.int32)
+        past = torch.tensor([s.cur for s in active], dtype=torch.int32)
+        slots = torch.tensor([s.slot for s in active], dtype=torch.int32)
+        k = max(1, min(max(s.gp.top_k for s in active), m.top_k_max))
+        vals, idx = m.verify_step(ids, past, n, k, slot_ids=slots, max_ctx=int((past + n).max()))
+        cv, ci = m.gather_candidates(vals.reshape(len(active) * T, -1), idx.reshape(len(active) * T, -1))
+        self.spec["spec_steps"] += 1
+        for j, s in enumerate(active):
+            e = len(s.out)
+            got = SP.accept(feeds[j], lambda t: m.pick_token(cv[j * T + t], ci[j * T + t], s.gp, e + t), self.eos)
+            s.out += got
+            s.cur += len(got)
+            self.tokens += len(got)
+            self.spec["spec_drafted"] += len(feeds[j]) - 1
+            self.spec["spec_accepted"] += len(got) - 1
 
     def _pick_rows(self, cv: torch.Tensor, ci: torch.Tensor, rows) -> List[int]:
         """Next token of each ``(row, gen params, step)``: the greedy rows in one vectorised

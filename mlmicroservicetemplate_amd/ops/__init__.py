@@ -107,6 +107,7 @@ from .transformer import (  # noqa: F401
     DecodePartials,
     decode_attention,
     decode_attention_fp8,
+    decode_attention_multi,
     decode_pick,
     embed_layernorm,
     embed_layernorm_packed,

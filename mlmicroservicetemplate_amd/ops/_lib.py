@@ -98,6 +98,8 @@ _SIGS = {
     "mls_flash_attention": [P, P, P, P, I, I, I, I, I, I, I, I, I, P, I, F, P],
     "mls_flash_attention_rows": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P, I, F, P],
     "mls_flash_attention_ctx": [P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, F, P],
+    "mls_decode_attention_multi": [P, P, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F, P],
+    "mls_decode_combine": [P, P, P, I, P, I, I, I, I, P],
     "mls_skinny_gemm": [P, P, P, P, P, P, SZ, I, I, I, I, I, P],
     "mls_mgemm": [P, P, P, P, P, P, SZ, I, I, I, I, I, I, P], "mls_mgemm_auto_split": [I, I, I],
     "mls_gemm_slabs": [P, P, P, SZ, I, I, I, I, I, P, P], "mls_splitk_add_rmsnorm": [P, SZ, I, I, I, P, P, P, F, P],
@@ -144,7 +146,7 @@ def _bind(lib: ctypes.CDLL) -> None:
 
 
 DEBUG = os.environ.get("MLS_DEBUG", "0") == "1"
-DEBUG_TUS = ("attention", "norm_ops", "stem_pool", "conv3x3_halo", "kv_fp8", "flash_ctx")  # translation units with MLS_CHECK bounds
+DEBUG_TUS = ("attention", "norm_ops", "stem_pool", "conv3x3_halo", "kv_fp8", "flash_ctx", "decode_verify")  # translation units with MLS_CHECK bounds
 DEBUG_CODES = {
     101: "rope/KV append: cache slot beyond the cache",
     102: "rope/KV append: position beyond the RoPE table",
@@ -155,6 +157,9 @@ DEBUG_CODES = {
     311: "flash attention (ctx): not 0 <= past[b] <= lens[b] <= the rows of a slot",
     312: "flash attention (ctx): slot outside the cache",
     313: "flash attention (ctx): page id outside the pool",
+    321: "decode attention (multi): not 0 <= past[b] <= lens[b] <= the rows of a slot / the split grid (max_len)",
+    322: "decode attention (multi): slot outside the cache",
+    323: "decode attention (multi): page id outside the pool",
 }
 
 

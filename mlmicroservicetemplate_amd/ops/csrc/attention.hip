@@ -1056,6 +1056,25 @@ int mls_decode_attention(const void* q, void* k_cache, void* v_cache, void* o, f
   return (int)hipGetLastError();
 }
 
+// The split-KV combine alone (D = 128), for partials another translation unit left in the layout above:
+// ws [B][Hq][nsplit][D], ws_ml [B][Hq][nsplit][2]; rows of lens[b] <= chunk were written directly.
+// decode_verify.hip feeds it T queries per sequence as T * Hq heads of one row.
+int mls_decode_combine(void* o, float* ws, float* ws_ml, int o_stride, const int* lens, int B, int Hq, int nsplit,
+                       int chunk, void* stream) {
+  if (!o || !ws || !ws_ml || !lens || B <= 0 || Hq <= 0 || nsplit <= 0 || chunk <= 0) return MLS_BAD_ARG;
+  if (nsplit > 1024) return MLS_UNSUPPORTED;  // one weight per split in LDS
+  DecodeArgs a{};
+  a.o = (bf16*)o;
+  a.ws = ws;
+  a.ws_ml = ws_ml;
+  a.o_stride = o_stride;
+  a.lens = lens;
+  a.Hq = Hq;
+  a.nsplit = nsplit;
+  hipLaunchKernelGGL(decode_combine_kernel<128>, dim3(B * Hq), dim3(128), 0, (hipStream_t)stream, a, chunk);
+  return (int)hipGetLastError();
+}
+
 }  // extern "C"
 
 MLS_DEBUG_EXPORT(attention)

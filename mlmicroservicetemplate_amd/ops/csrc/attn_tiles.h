@@ -225,19 +225,22 @@ MLS_DEV void decode_pv(f32x4 (&o)[DecodeDims::DT], bf16x8 pf, const char* V, int
   }
 }
 
-// Merge the block's waves through LDS once each has stored (mt, ls) of head fr in sm_m / sm_l and its O
-// rows (heads 4g + j) in sm_o -- that store stays in the kernels: through this struct one instantiation
+// Merge the block's waves through LDS once each has stored (mt, ls) of column fr in sm_m / sm_l and its O
+// rows (columns 4g + j) in sm_o -- that store stays in the kernels: through this struct one instantiation
 // paired its ds_write_b32 differently.  A sequence that fits one split (`direct`) gets its output row,
 // otherwise split sp's fp32 partial (m, l, O) goes to ws / ws_ml for the combine kernels or the fused
 // combine of mls_skinny_packed_combine.
+// C = G (the single-token kernels): column = query head hh of the KV head, one output row per sequence.
+// C > G (decode_verify_kernel): nq queries per sequence, column = query * G + head; output / partial row
+// b * nq + query, so the partials of a sequence are those of nq * Hq heads of one row.
 namespace {
-template <int G, int WAVES>
+template <int G, int WAVES, int C = G>
 struct DecodeMerge {
   using T = DecodeTile<G, WAVES>;
   static constexpr int D = T::D;
-  float (&sm_m)[WAVES][G];
-  float (&sm_l)[WAVES][G];
-  float (&sm_o)[WAVES][G][D];
+  float (&sm_m)[WAVES][C];
+  float (&sm_l)[WAVES][C];
+  float (&sm_o)[WAVES][C][D];
   bf16* const& out;
   float* const& ws;
   float* const& ws_ml;
@@ -248,26 +251,29 @@ struct DecodeMerge {
   const int& hk;
   const int& sp;
   const int& tid;
-  __device__ void operator()(bool direct) const {
+  __device__ void operator()(bool direct, int nq = 1) const {
     __syncthreads();
-    for (int idx = tid; idx < G * D; idx += T::NT) {
-      const int hh = idx / D, d = idx % D;
+    const int cols = C == G ? G : nq * G;
+    for (int idx = tid; idx < cols * D; idx += T::NT) {
+      const int cc = idx / D, d = idx % D;
+      const int hh = C == G ? cc : cc % G;
+      const long row = C == G ? (long)b : (long)b * nq + cc / G;
       float M = -INFINITY;
 #pragma unroll
-      for (int p = 0; p < WAVES; ++p) M = fmaxf(M, sm_m[p][hh]);
+      for (int p = 0; p < WAVES; ++p) M = fmaxf(M, sm_m[p][cc]);
       float Ls = 0.f, O = 0.f;
       if (M != -INFINITY) {
 #pragma unroll
         for (int p = 0; p < WAVES; ++p) {
-          const float w = __builtin_amdgcn_exp2f(sm_m[p][hh] - M);
-          Ls += sm_l[p][hh] * w;
-          O += sm_o[p][hh][d] * w;
+          const float w = __builtin_amdgcn_exp2f(sm_m[p][cc] - M);
+          Ls += sm_l[p][cc] * w;
+          O += sm_o[p][cc][d] * w;
         }
       }
       if (direct) {
-        out[(long)b * o_stride + (long)(hk * G + hh) * D + d] = (bf16)(Ls > 0.f ? O / Ls : 0.f);
+        out[row * o_stride + (long)(hk * G + hh) * D + d] = (bf16)(Ls > 0.f ? O / Ls : 0.f);
       } else {
-        const long base = ((long)b * Hq + hk * G + hh) * nsplit + sp;
+        const long base = (row * Hq + hk * G + hh) * nsplit + sp;
         ws[base * D + d] = O;
         if (d == 0) {
           ws_ml[base * 2] = M;

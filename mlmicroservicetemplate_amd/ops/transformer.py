@@ -290,6 +290,88 @@ def flash_attention_ctx(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
     return out
 
 
+def decode_attention_multi(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, past: torch.Tensor,
+                           lens: torch.Tensor, batch: int, seq: int, n_q_heads: int, n_kv_heads: int, head_dim: int, *,
+                           slot_ids: Optional[torch.Tensor] = None, page_table: Optional[torch.Tensor] = None,
+                           chunk: int = 64, max_len: Optional[int] = None, scale: Optional[float] = None,
+                           workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A few queries per sequence against the KV cache, split-KV on the matrix cores: the attention of
+    a speculative-decoding verify step.  The contract is :func:`flash_attention_ctx`'s (same arguments,
+    same oracle ``reference.attention_ctx``): query ``t`` of row ``b`` (``t < lens[b] - past[b]``) sits
+    at position ``past[b] + t`` and attends cache rows ``0 .. past[b] + t`` of slot ``slot_ids[b]``; the
+    step's own rows must have been appended first (:func:`rope_kv_`); nothing is read on the host.
+    ``seq * Hq / Hkv <= 16`` (the queries and heads of a KV head share one MFMA's lane columns),
+    Hq / Hkv in 1, 2, 4, 8.  ``chunk``: cache rows per split block, 64 or 128 (paged: 64, one page);
+    ``max_len``: a host bound on ``lens`` (default: what a slot holds) that sizes the split grid, as
+    :func:`decode_attention` takes it.  ``workspace``: fp32, ``B*seq*Hq*nsplit*(D+2)`` elements."""
+    dev = qkv.device
+    _need(qkv, "qkv", torch.bfloat16, dev)
+    _need(k_cache, "k_cache", torch.bfloat16, dev)
+    _need(v_cache, "v_cache", torch.bfloat16, dev)
+    _need(past, "past", torch.int32, dev)
+    _need(lens, "lens", torch.int32, dev)
+    if batch <= 0 or seq <= 0 or n_kv_heads <= 0 or n_q_heads % n_kv_heads:
+        raise ValueError("batch, seq > 0 and Hq a multiple of Hkv")
+    if head_dim != 128:
+        raise ValueError(f"decode_attention_multi: head_dim must be 128, got {head_dim}")
+    G = n_q_heads // n_kv_heads
+    if G not in (1, 2, 4, 8) or seq * G > 16:
+        raise ValueError(f"decode_attention_multi: Hq / Hkv in 1, 2, 4, 8 and seq * Hq / Hkv <= 16 "
+                         f"(got seq {seq}, Hq / Hkv {n_q_heads} / {n_kv_heads})")
+    W = (n_q_heads + 2 * n_kv_heads) * head_dim
+    if qkv.dim() != 2 or tuple(qkv.shape) != (batch * seq, W):
+        raise ValueError("qkv shape does not match batch/seq/heads")
+    if past.numel() != batch or lens.numel() != batch:
+        raise ValueError(f"past and lens must have {batch} elements")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
+        raise ValueError("k_cache and v_cache must be 4-d and of the same shape")
+    if k_cache.shape[1] != n_kv_heads or k_cache.shape[3] != head_dim:
+        raise ValueError(f"decode_attention_multi reads head-major caches [blocks, Hkv={n_kv_heads}, rows, {head_dim}] "
+                         f"only (a row-major cache is not supported), got {tuple(k_cache.shape)}")
+    blocks, rows = k_cache.shape[0], k_cache.shape[2]
+    if slot_ids is not None:
+        _need(slot_ids, "slot_ids", torch.int32, dev)
+        if slot_ids.numel() != batch:
+            raise ValueError(f"slot_ids must have {batch} elements")
+    if chunk not in (64, 128):
+        raise ValueError(f"decode_attention_multi: splits of 64 or 128 rows, got {chunk}")
+    if page_table is not None:
+        _need(page_table, "page_table", torch.int32, dev)
+        if page_table.dim() != 2:
+            raise ValueError("page_table must be [slots, pages_per_seq]")
+        if rows != 64 or chunk != 64:
+            raise ValueError(f"paged decode_attention_multi: pages and splits of 64 rows, got {rows} / {chunk}")
+        slots, pps = page_table.shape
+        cap = pps * 64
+    else:
+        slots, pps, cap = blocks, 0, rows
+    if slot_ids is None and batch > slots:
+        raise ValueError("the cache holds fewer slots than the batch")
+    max_len = cap if max_len is None else max(1, min(int(max_len), cap))
+    nsplit = (max_len + chunk - 1) // chunk
+    if nsplit > 1024:
+        raise ValueError(f"decode_attention_multi: at most 1024 splits (max_len {max_len} / chunk {chunk})")
+    n_o = batch * seq * n_q_heads * nsplit * head_dim
+    need = n_o // head_dim * (head_dim + 2)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=dev, dtype=torch.float32)
+    _need(workspace, "workspace", torch.float32, dev)
+    if out is not None:
+        _need(out, "out", torch.bfloat16, dev)
+        if tuple(out.shape) != (batch * seq, n_q_heads * head_dim) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [B*S, Hq*D]")
+    else:
+        out = torch.empty(batch * seq, n_q_heads * head_dim, device=dev, dtype=torch.bfloat16)
+    scale = head_dim ** -0.5 if scale is None else scale
+    rc = lib().mls_decode_attention_multi(qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(),
+                                          workspace.data_ptr(), workspace[n_o:].data_ptr(), W, out.stride(0),
+                                          past.data_ptr(), lens.data_ptr(), _ptr(slot_ids), _ptr(page_table), pps,
+                                          slots, batch, seq, n_q_heads, n_kv_heads, head_dim, blocks, rows, max_len,
+                                          chunk, float(scale), stream_ptr(dev))
+    check(rc, "mls_decode_attention_multi")
+    return out
+
+
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, lens: torch.Tensor,
                      n_q_heads: int, n_kv_heads: int, head_dim: int, *, chunk: int = 64,
                      scale: Optional[float] = None, workspace: Optional[torch.Tensor] = None,

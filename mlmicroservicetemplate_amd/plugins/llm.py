@@ -37,6 +37,7 @@ class LlamaPlugin(ModelPlugin):
         self.ctx = None
         self.comm_dev = None
         self.prefill_chunk = 0
+        self.speculate, self.speculate_ngram = 0, 3
         self._lock = threading.Lock()
 
     def init(self, ctx: PluginContext) -> None:
@@ -46,6 +47,7 @@ class LlamaPlugin(ModelPlugin):
         s = ctx.settings
         extra = s.model_yaml() if hasattr(s, "model_yaml") else {}
         weight_dtype = self.parse_weight_dtype(extra)  # before any weight is read or allocated
+        self.speculate, self.speculate_ngram = self.parse_speculate(extra)
         size = extra.get("config", "8b")
         cfg = llama.LLAMA3_8B if size == "8b" else llama.tiny_config(**extra.get("overrides", {}))
         tp = ctx.world_size if int(s.TP) > 1 else 1
@@ -75,6 +77,8 @@ class LlamaPlugin(ModelPlugin):
         self.model = llama.LlamaTP(params, cfg, tp=tp, rank=ctx.rank, comm=llama.TPComm(None, tp, device=dev), backend=backend,
                                    device=dev, max_batch=max_batch, max_seq=max_seq, kv_pages=kv_pages,
                                    kv_dtype=kv_dtype, weight_dtype=weight_dtype)
+        if self.speculate:  # refused at start-up on the lockstep path too (the engine below checks for itself)
+            self.model.check_speculate(self.speculate)
         self.tok = llama.LlamaTokenizer(cfg, extra.get("tokenizer_file"))
         self.cfg = cfg
         self.engine = None
@@ -82,7 +86,8 @@ class LlamaPlugin(ModelPlugin):
             from ..models.llama_serving import ContinuousLlama
 
             self.engine = ContinuousLlama(self.model, max_queue=int(s.MAX_QUEUE), channel=self if tp > 1 else None,
-                                          prefill_chunk=self.prefill_chunk)
+                                          prefill_chunk=self.prefill_chunk, speculate=self.speculate,
+                                          drafter=self._drafter())
             if ctx.rank == 0:
                 self.engine.start()
         logger.info("llama ready: tp=%d rank=%d backend=%s device=%s kv_dtype=%s kv_bytes_per_token=%d "
@@ -97,6 +102,25 @@ class LlamaPlugin(ModelPlugin):
         if wd not in ("bf16", "int4"):
             raise ValueError(f"weight_dtype must be 'bf16' or 'int4', got {wd!r}")
         return wd
+
+    @staticmethod
+    def parse_speculate(extra: dict):
+        """MODEL_CONFIG ``speculate``: K draft tokens per sequence and decode step, an integer in [0, 7]
+        (default 0 = off), and ``speculate_ngram``: the longest n-gram prompt lookup matches (default 3)."""
+        out = []
+        for key, default, lo, hi in (("speculate", 0, 0, 7), ("speculate_ngram", 3, 1, 64)):
+            v = extra.get(key, default)
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError(f"{key} must be an integer in [{lo}, {hi}], got {v!r}")
+            out.append(v)
+        return tuple(out)
+
+    def _drafter(self):
+        if not self.speculate:
+            return None
+        from ..models.speculative import make_prompt_lookup
+
+        return make_prompt_lookup(max_ngram=self.speculate_ngram)
 
     @staticmethod
     def kv_page_bytes(cfg, tp: int, backend: str = "fused", kv_dtype: str = "bf16") -> int:
@@ -224,7 +248,8 @@ class LlamaPlugin(ModelPlugin):
         lens = torch.tensor([len(t) for t in ids_l], dtype=torch.int32)
         with self._lock:
             self._broadcast_cmd(OP_GENERATE, ids, lens, gp)
-            out = self.model.generate(ids, lens, gp, prefill_chunk=self.prefill_chunk)
+            out = self.model.generate(ids, lens, gp, prefill_chunk=self.prefill_chunk, speculate=self.speculate,
+                                      drafter=self._drafter())
         return out.cpu().tolist()
 
     # ---- the continuous engine's TP control channel (models/llama_serving.py ContinuousLlama):
@@ -340,7 +365,7 @@ class LlamaPlugin(ModelPlugin):
             dist.broadcast(ids, src=0)
             dist.broadcast(lens, src=0)
             self.model.generate(ids, lens, GenParams(mnt, topk, temp / 1000.0, seed),
-                                prefill_chunk=self.prefill_chunk)
+                                prefill_chunk=self.prefill_chunk, speculate=self.speculate, drafter=self._drafter())
 
     def close(self) -> None:
         if self.engine is not None and self.ctx.rank == 0:
@@ -357,5 +382,6 @@ class LlamaPlugin(ModelPlugin):
         d = super().describe()
         if self.model is not None:
             d.update({"tp": self.model.tp, "backend": self.model.backend, "max_batch": self.model.max_batch,
-                      "max_seq": self.model.max_seq})
+                      "max_seq": self.model.max_seq, "speculate": self.speculate,
+                      "speculate_ngram": self.speculate_ngram})
         return d

@@ -3,7 +3,9 @@
 bert : sequences/s at (batch, seq) through the GpuEngine (hipGraph per bucket), fused kernels
        vs stock PyTorch-ROCm (hipBLASLt + SDPA) on the same random weights.
 llama: TP=1 (all of Llama-3-8B on one GPU): prefill tokens/s and decode ms/step at several
-       batch sizes with the fused kernels.
+       batch sizes with the fused kernels.  ``--speculate K``: also ms per verify step of K + 1 positions
+       (both attention routes) interleaved with the decode step, and with ``--spec-accept P`` tokens/s of
+       ``generate(speculate=K)`` under a synthetic drafter that is right with probability P.
 One JSON line per measurement.
 """
 import argparse
@@ -35,6 +37,95 @@ def _closed_loop(eng, x, n):
             pend.pop(0).wait()
     for t in pend:
         t.wait()
+
+
+def synthetic_drafter(prompts, continuations, p_right, vocab, seed=0):
+    """A drafter that is right with probability ``p_right`` per draft, for models whose prompt-lookup
+    acceptance means nothing (random weights): ``continuations[b]`` is a recorded run from ``prompts[b]``
+    (distinct prompts of one length).  Draws are keyed by (seed, sequence, position), so every rerun drafts
+    alike; a wrong draft is never the recorded token; a sequence that left its record gets a plain guess."""
+    import random
+
+    L = len(prompts[0])
+    row = {tuple(p): b for b, p in enumerate(prompts)}
+    conts = [list(c) for c in continuations]
+
+    def draft(tokens, n_draft):
+        toks = list(tokens)
+        b = row.get(tuple(toks[:L]), -1)
+        e = len(toks) - L
+        if b < 0 or toks[L:] != conts[b][:e]:
+            return [toks[-1]] * n_draft
+        out = []
+        for t in range(n_draft):
+            right = conts[b][e + t] if e + t < len(conts[b]) else toks[-1]
+            ok = random.Random(seed * 1000003 + b * 10007 + e + t).random() < p_right
+            out.append(right if ok else (right + 1) % vocab)
+        return out
+
+    return draft
+
+
+def bench_verify_attn(args):
+    """Kernel alone: ``ops.decode_attention_multi`` at T = 2, 3, 4 against ``ops.decode_attention`` (one query,
+    matrix-core kernel, no RoPE / append prologue: q and the cache are used as they are) and
+    ``ops.flash_attention_ctx`` at S = T.  Hq 32 / Hkv 8; every arm interleaved after a warm floor; us per call
+    from events around ``--steps`` back-to-back launches, median and minimum of 5 windows.  The same K / V are
+    re-read by every launch, so the numbers are L2-warm."""
+    from mlmicroservicetemplate_amd import ops
+
+    dev = torch.device("cuda:0")
+    Hq, Hkv, D, N = 32, 8, 128, args.steps
+
+    def window(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(N):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / N
+
+    for paged in (False, True):
+        for B in args.batches:
+            for ctx in args.contexts:
+                rows = ctx + 64
+                g = torch.Generator(device=dev).manual_seed(0)
+                table = None
+                if paged:
+                    pps = rows // 64
+                    kc = torch.randn(B * pps + 1, Hkv, 64, D, device=dev, generator=g).to(torch.bfloat16)
+                    table = (1 + torch.randperm(B * pps, device=dev, generator=g)).view(B, pps).to(torch.int32)
+                else:
+                    kc = torch.randn(B, Hkv, rows, D, device=dev, generator=g).to(torch.bfloat16)
+                vc = torch.randn_like(kc)
+                lens = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+                W = (Hq + 2 * Hkv) * D
+                q1 = torch.randn(B, W, device=dev, generator=g).to(torch.bfloat16)
+                ws1 = torch.empty(B * Hq * (rows // 64 + 1) * (D + 2), device=dev, dtype=torch.float32)
+                o1 = torch.empty(B, Hq * D, device=dev, dtype=torch.bfloat16)
+                arms = {"decode_T1": lambda: ops.decode_attention(q1, kc, vc, lens, Hq, Hkv, D, chunk=64, head_major=True,
+                                                                  workspace=ws1, out=o1, max_len=ctx, page_table=table)}
+                for T in (2, 3, 4):
+                    past = torch.full((B,), ctx - T, dtype=torch.int32, device=dev)
+                    qT = torch.randn(B * T, W, device=dev, generator=g).to(torch.bfloat16)
+                    wsT = torch.empty(B * T * Hq * (rows // 64 + 1) * (D + 2), device=dev, dtype=torch.float32)
+                    oT = torch.empty(B * T, Hq * D, device=dev, dtype=torch.bfloat16)
+                    oC = torch.empty_like(oT)
+                    arms[f"multi_T{T}"] = (lambda T=T, past=past, qT=qT, wsT=wsT, oT=oT: ops.decode_attention_multi(
+                        qT, kc, vc, past, lens, B, T, Hq, Hkv, D, page_table=table, max_len=ctx, workspace=wsT, out=oT))
+                    arms[f"ctx_S{T}"] = (lambda T=T, past=past, qT=qT, oC=oC: ops.flash_attention_ctx(
+                        qT, kc, vc, past, lens, B, T, Hq, Hkv, D, page_table=table, out=oC))
+                _warm(lambda: [fn() for fn in arms.values()], args.warm_ms)
+                res = {a: [] for a in arms}
+                for _ in range(5):
+                    for a, fn in arms.items():
+                        res[a].append(window(fn))
+                print(json.dumps({"bench": "verify_attention_kernel", "Hq": Hq, "Hkv": Hkv, "batch": B, "ctx": ctx,
+                                  "paged": paged, "launches_per_window": N,
+                                  **{a + "_us": round(sorted(v)[2], 2) for a, v in res.items()},
+                                  **{a + "_us_min": round(min(v), 2) for a, v in res.items()}}), flush=True)
+                del kc, vc
 
 
 def bench_bert(args):
@@ -135,6 +226,83 @@ def bench_llama(args):
         print(json.dumps({"bench": "llama3-8b", "tp": tp, "batch": B, "prompt": S, "kv_pages": args.kv_pages,
                           "kv_dtype": args.kv_dtype, "weight_dtype": args.weight_dtype, "prefill_ms": round(pre * 1e3, 2), "prefill_tok_s": round(B * S / pre, 1),
                           "decode_ms_per_step": round(dec * 1e3, 3), "decode_tok_s": round(B / dec, 1)}), flush=True)
+        for K in args.speculate:
+            _bench_speculate(m, args, K, B, S, ids, lens, tok, cur)
+
+
+def _bench_speculate(m, args, K, B, S, ids, lens, tok, cur):
+    """Verify step (K + 1 positions per sequence) against the decode step, both arms interleaved in this
+    process after a warm floor; then, with --spec-accept, generate() with and without speculation."""
+    from mlmicroservicetemplate_amd.models.llama import GenParams
+
+    dev = ids.device
+    T = K + 1
+    m.check_speculate(K)
+    if m.pages is not None:
+        for b in range(B):
+            m.pages.assign(b, S + T)
+    feed = torch.randint(1000, 100000, (B, T), device=dev, dtype=torch.int32)
+    n = torch.full((B,), T, device=dev, dtype=torch.int32)
+    arms = {"decode": lambda: m.decode_step(tok, cur, 1, max_ctx=S + 1)}
+    for route in ("multi", "ctx"):  # the verify step's two attention routes (LlamaTP.verify_attn; a graph per route)
+        def step(route=route):
+            m.verify_attn = route
+            return m.verify_step(feed, lens, n, 1, max_ctx=S + T)
+
+        step()
+        arms["verify_" + route] = step
+    times = {a: [] for a in arms}
+    _warm(lambda: [f() for f in arms.values()], args.warm_ms)
+    for _ in range(5):  # interleaved windows: a drift of the clocks hits every arm alike
+        for a, f in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                f()
+            torch.cuda.synchronize()
+            times[a].append((time.perf_counter() - t0) / args.steps * 1e3)
+    m.verify_attn = "multi"
+    med = {a: float(np.median(v)) for a, v in times.items()}
+    print(json.dumps({"bench": "llama3-8b-verify", "batch": B, "prompt": S, "T": T, "kv_pages": args.kv_pages,
+                      "weight_dtype": args.weight_dtype,
+                      **{a + "_ms": round(v, 3) for a, v in med.items()},
+                      **{a + "_ms_min": round(min(times[a]), 3) for a in times},
+                      # accepted drafts per step above which a verify step yields more tokens per ms than a decode step
+                      "break_even_accepted_per_step": round(med["verify_multi"] / med["decode"] - 1, 3)}), flush=True)
+    if not args.spec_accept:
+        return
+    if m.pages is not None:
+        m.pages.reset()  # generate() assigns its own pages
+    gp = GenParams(args.new)
+    prompts = [ids[b].tolist() for b in range(B)]
+    m.generate(ids, lens, gp)  # warm-up of the plain arm
+    # the recorded run the drafter is right about: one token per verify step (every draft a token the step
+    # does not pick), i.e. plain decoding's schedule through the verify step's own kernels -- on random
+    # weights, where near-ties are everywhere, a record from the single-token route would diverge from what
+    # the verify route picks within a few tokens and no draft would ever be "right"
+    rec = m.generate(ids, lens, gp, speculate=K, drafter=lambda toks, n: [(toks[-1] + 1) % 100000] * n).tolist()
+    arms = {"plain": {}}
+    for P in args.spec_accept:
+        arms[f"accept_{P}"] = dict(speculate=K, drafter=synthetic_drafter(prompts, rec, P, 100000, seed=0))
+    res, stats = {}, {}
+    for rnd in range(3):  # round 0 warms every arm's graphs and is dropped
+        for name, kw in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m.generate(ids, lens, gp, **kw)
+            torch.cuda.synchronize()
+            if rnd:
+                res.setdefault(name, []).append(B * args.new / (time.perf_counter() - t0))
+            stats[name] = dict(m.spec_stats)
+    for name in arms:
+        if name != "plain":
+            print(json.dumps({"bench": "llama3-8b-speculate", "batch": B, "prompt": S, "new_tokens": args.new,
+                              "speculate": K, "spec_accept": float(name.split("_")[1]), "kv_pages": args.kv_pages,
+                              "weight_dtype": args.weight_dtype, "plain_tok_s": round(max(res["plain"]), 1),
+                              "speculative_tok_s": round(max(res[name]), 1), **stats[name]}), flush=True)
+    if m.pages is not None:
+        for b in range(B):
+            m.pages.assign(b, S + 1)
 
 
 def bench_llama_serve(args):
@@ -171,7 +339,8 @@ def bench_llama_serve(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("which", choices=["bert", "llama", "llama-serve"])
+    ap.add_argument("which", choices=["bert", "llama", "llama-serve", "verify-attn"])
+    ap.add_argument("--contexts", type=int, nargs="+", default=[512, 2048, 8192], help="verify-attn: context lengths")
     ap.add_argument("--requests", type=int, default=128)
     ap.add_argument("--new", type=int, default=64)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8, 32])
@@ -191,13 +360,18 @@ def main():
     ap.add_argument("--weight-dtype", choices=["bf16", "int4"], default="bf16",
                     help="llama: layer projections in bf16, or W4A16 (4-bit codes, one bf16 scale per row and 128 k)")
     ap.add_argument("--max-seq", type=int, default=2048, help="llama: cache rows per sequence")
+    ap.add_argument("--speculate", type=int, nargs="*", default=[],
+                    help="llama: also time the verify step of K + 1 positions per sequence (speculative decoding)")
+    ap.add_argument("--spec-accept", type=float, nargs="*", default=[],
+                    help="llama --speculate: generate() tokens/s with a synthetic drafter right with probability P")
     ap.add_argument("--shuffle-pages", action="store_true", help="llama: hand out pages in random order")
     args = ap.parse_args()
     if args.skinny_max_split:
         from mlmicroservicetemplate_amd.ops import _lib
 
         _lib.lib().mls_skinny_set_max_split(args.skinny_max_split)
-    {"bert": bench_bert, "llama": bench_llama, "llama-serve": bench_llama_serve}[args.which](args)
+    {"bert": bench_bert, "llama": bench_llama, "llama-serve": bench_llama_serve,
+     "verify-attn": bench_verify_attn}[args.which](args)
 
 
 if __name__ == "__main__":
