@@ -608,6 +608,11 @@ class LlamaTP:
         self.spec_max_tokens = 8
         self.spec_stats = {"steps": 0, "drafted": 0, "accepted": 0}
         self._dec_ctx: Optional[int] = None  # host bound on decode context (sizes the split grid)
+        # prefix caching (ContinuousLlama(prefix_cache=True) sets ctx_split): a prefill chunk of few
+        # queries against a long cached context may run split-KV (ctx_splits); off: always one split
+        self.ctx_split = False
+        self.ctx_splits_forced = int(os.environ.get("MLS_CTX_SPLITS", "0"))  # A/B runs: this many splits
+        self.ctx_ws: Optional[torch.Tensor] = None  # split-KV partials of the (uncaptured) prefill chunks
         # device-resident decode loop (X4 on device, _generate_device): per-batch-size static state
         # shared by the captured steps of every context bucket, so switching buckets copies nothing
         self._dev_graphs: Dict[Tuple[int, int, int], torch.cuda.CUDAGraph] = {}
@@ -732,7 +737,7 @@ class LlamaTP:
     # ---------------------------------------------------------------- fused backend
     def _fused_forward(self, ids: torch.Tensor, positions: torch.Tensor, lens: torch.Tensor, B: int, S: int,
                        decode: bool, k: int, slot_ids: Optional[torch.Tensor] = None,
-                       past: Optional[torch.Tensor] = None, all_rows: bool = False):
+                       past: Optional[torch.Tensor] = None, all_rows: bool = False, max_ctx: Optional[int] = None):
         """Native-kernel forward.  The RMSNorm gains are folded into the following projections, so
         for decode-shaped token counts (<= 16) each pre-norm + residual add rides inside the skinny
         GEMM (``ops.gemm_rmsnorm``: 7 launches per layer); larger counts run a gain-free RMSNorm and
@@ -805,6 +810,19 @@ class LlamaTP:
                 ws_v = self.ver_ws
             elif ws_v.numel() < need:
                 ws_v = self._ver_ws_graph = torch.empty(need, device=self.device, dtype=torch.float32)
+
+        # prefix caching on: a prefill chunk (not a verify step, whose graphs own their workspaces) of few
+        # queries against a long cached context runs split-KV where ctx_splits says so
+        ctx_kw = {}
+        if self.ctx_split and past is not None and not all_rows and not multi:
+            cap_c = self.pages.pages_per_seq * self.page_rows if self.pages is not None else self.max_seq
+            ctx_max = min(int(max_ctx) if max_ctx else cap_c, cap_c)  # no host bound given: what a slot holds
+            n_split = self.ctx_splits(B, S, sd.hq, ctx_max)
+            if n_split > 1:
+                need = ops.flash_ctx_workspace_elems(B, S, sd.hq, D, n_split)
+                if self.ctx_ws is None or self.ctx_ws.numel() < need:
+                    self.ctx_ws = torch.empty(need, device=self.device, dtype=torch.float32)
+                ctx_kw = dict(splits=n_split, max_ctx=ctx_max, workspace=self.ctx_ws)
 
         def use_fp8(name, K):
             return name in fp8 and T * K * 2 <= 65536
@@ -922,7 +940,8 @@ class LlamaTP:
                 elif past is not None:  # chunked prefill: the chunk's queries against the cache rows just written
                     a = ops.flash_attention_ctx(qkv, self.k_cache[i], self.v_cache[i], past, lens, B, S, sd.hq, sd.hkv,
                                                 D, slot_ids=sid,
-                                                page_table=self.pages.dev if self.pages is not None else None)
+                                                page_table=self.pages.dev if self.pages is not None else None,
+                                                **ctx_kw)
                 else:
                     a = ops.flash_attention(qkv, B, S, sd.hq, sd.hkv, D, kv_lens=lens, causal=True)
             if parts is not None:  # split-KV combine in the o-projection's prologue (one launch, not two)
@@ -1071,6 +1090,46 @@ class LlamaTP:
                                  f"(speculate + 1) * Hq / Hkv <= 16 (got speculate {speculate}, "
                                  f"{self.sd.hq} / {self.sd.hkv} heads on this rank)")
 
+    def check_prefix_cache(self) -> None:
+        """Prefix caching shares filled KV pages between sequences and prefills a suffix against them
+        like a prefill chunk: raises ``ValueError`` without the paged cache and for what chunked
+        prefill refuses (nothing falls back to recomputing the prefix)."""
+        if self.pages is None:
+            raise ValueError("prefix caching needs the paged KV cache (kv_pages is 0): it shares pages, "
+                             "a per-slot cache has none")
+        try:
+            self.check_prefill_chunk()
+        except ValueError as e:
+            raise ValueError(str(e).replace("chunked prefill", "prefix caching")) from None
+
+    # split-KV routing of a prefill chunk (ops.flash_attention_ctx(splits=...)).  The constants come from
+    # the kernel table of docs/PERF_NOTES.md "Prefix caching" (profiles/prefix_cache_ab.jsonl; Hq 32, Hkv 8,
+    # paged, unsplit -> routed, us): 32 blocks x 65 tiles 112 -> 25 (16 splits), 128 blocks x 68 tiles
+    # 117 -> 45 (4), 256 blocks x 65 tiles 118 -> 85 (2; 4 splits 94), 1024 blocks x 20 tiles 84 -> 92 (2
+    # splits lose).  One tile per split loses to two and four (32 blocks x 17 tiles: 16.7 / 13.8 / 14.2).
+    CTX_SPLIT_BLOCKS = 512     # bring the grid to this many blocks; at or above it: unsplit
+    CTX_SPLIT_MIN_TILES = 4    # every split keeps at least this many 64-key tiles
+    CTX_SPLIT_MAX = 16         # the largest count measured
+
+    @classmethod
+    def ctx_split_rule(cls, B: int, S: int, Hq: int, max_ctx: Optional[int]) -> int:
+        """Splits of a prefill chunk's context attention: a host-side function of the launch shape and
+        the host bound on ``past + n`` alone.  The largest power of two (the counts measured) that is
+        at most ``CTX_SPLIT_BLOCKS`` / the unsplit grid's blocks, leaves every split
+        ``CTX_SPLIT_MIN_TILES`` key tiles and does not exceed ``CTX_SPLIT_MAX``; 1 otherwise."""
+        if max_ctx is None:
+            return 1
+        blocks = -(-S // 64) * Hq * B
+        tiles = -(-int(max_ctx) // 64)
+        n = min(-(-cls.CTX_SPLIT_BLOCKS // blocks), tiles // cls.CTX_SPLIT_MIN_TILES, cls.CTX_SPLIT_MAX)
+        return 1 << (n.bit_length() - 1) if n >= 2 else 1
+
+    def ctx_splits(self, B: int, S: int, Hq: int, max_ctx: Optional[int]) -> int:
+        """:meth:`ctx_split_rule`, unless ``MLS_CTX_SPLITS=n`` forces n (A/B runs)."""
+        if self.ctx_splits_forced > 0:
+            return max(1, min(64, self.ctx_splits_forced))
+        return self.ctx_split_rule(B, S, Hq, max_ctx)
+
     def _verify_graph(self, B: int, T: int, k: int, ctx: int):
         """Captured verify step for B sequences of T positions under the context bound ctx (static id /
         past / lens / slot buffers, as :meth:`_decode_graph`).  Warm-up and capture run with
@@ -1146,8 +1205,11 @@ class LlamaTP:
 
     @torch.no_grad()
     def step(self, ids: torch.Tensor, positions: torch.Tensor, lens: torch.Tensor, decode: bool, k: int,
-             slot_ids: Optional[torch.Tensor] = None, past: Optional[torch.Tensor] = None, all_rows: bool = False):
-        """One forward.  ``slot_ids`` (prefill only): cache row of each batch row (default: the
+             slot_ids: Optional[torch.Tensor] = None, past: Optional[torch.Tensor] = None, all_rows: bool = False,
+             max_ctx: Optional[int] = None):
+        """One forward.  ``max_ctx`` (with ``past``): a host bound on ``lens`` -- with prefix caching on
+        it decides whether the chunk's attention runs split-KV (:meth:`ctx_splits`) and where the
+        splits are cut.  ``slot_ids`` (prefill only): cache row of each batch row (default: the
         batch row itself) -- how continuous batching prefills new requests into free slots.
         ``past`` (prefill only, int32 ``[B]``): rows of each sequence already in the cache -- this
         forward is the chunk at ``positions`` ``past[b] + i`` (absolute), ``lens`` the absolute end
@@ -1171,7 +1233,7 @@ class LlamaTP:
         with tracing.range("llama.decode" if decode else "llama.prefill"):
             if self.backend == "fused":
                 return self._fused_forward(ids.to(torch.int32), positions.to(torch.int32), lens.to(torch.int32), B,
-                                           S, decode, k, slot_ids, past, all_rows)
+                                           S, decode, k, slot_ids, past, all_rows, max_ctx)
             return self._ref_forward(ids, positions, lens, B, S, decode, k, slot_ids, past, all_rows)
 
     @torch.no_grad()

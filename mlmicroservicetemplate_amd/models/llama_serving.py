@@ -33,6 +33,14 @@ decode step.  The choice is a function of the slots alone.  Iterations run on th
 device-resident iteration picks one token per slot), and TP > 1 is refused: the carried-header
 protocol is tied to the device iterations (follow-up).
 
+Prefix caching (``ContinuousLlama(prefix_cache=True)``, opt-in, paged KV only, models/prefix_cache.py):
+full pages of a prompt stay indexed once its prefill (or last chunk) has been issued, and step 1 of a
+later request whose prompt begins with the same tokens adopts those pages and prefills only the rest --
+``LlamaTP.step(ids[hit:], past=hit rows)`` per row in one-shot mode, ``rows done = hit`` at admission in
+chunked mode.  Admission counts fresh pages only; pages nobody holds stay indexed until ``assign`` needs
+them.  Matching, adoption, indexing and eviction are functions of the admissions and retirements alone, so
+every TP rank keeps an identical index of its own and the headers carry nothing about it.
+
 Each sequence samples with its own parameters and the same seeded rule as a batch-of-one
 ``LlamaTP.generate`` (``pick_token``), so results do not depend on what else is in flight.
 
@@ -109,17 +117,22 @@ class _Seq:
     out: List[int] = field(default_factory=list)
     cur: int = 0  # position of the next token to feed
     done: int = 0  # chunked prefill: prompt rows already in the cache (== len(ids): decoding)
+    hit: int = 0  # prefix caching: prompt rows adopted from the prefix index (a multiple of the page size)
     t_submit: float = field(default_factory=time.perf_counter)
 
 
 class ContinuousLlama:
     def __init__(self, model: LlamaTP, max_queue: int = 4096,
                  broadcast: Optional[Callable[[Optional[List[_Seq]]], Optional[List[_Seq]]]] = None,
-                 channel=None, prefill_chunk: int = 0, speculate: int = 0, drafter=None):
+                 channel=None, prefill_chunk: int = 0, speculate: int = 0, drafter=None,
+                 prefix_cache: bool = False):
         """``prefill_chunk = N > 0`` (chunked prefill): an admitted prompt advances by at most N
         positions per iteration, batched over all prefilling slots, and the decoding slots get their
         step in the same iteration -- a long prompt no longer holds every decoding sequence for its
-        whole prefill.  0: each iteration prefills its admissions in one forward."""
+        whole prefill.  0: each iteration prefills its admissions in one forward.
+        ``prefix_cache`` (paged KV only): full pages of prompt tokens stay indexed after their prefill
+        (models/prefix_cache.py); a later prompt that begins with the same tokens adopts those pages
+        and prefills only the rest, ``step(past=hit rows)``."""
         self.prefill_chunk = int(prefill_chunk)
         if self.prefill_chunk < 0:
             raise ValueError(f"prefill_chunk must be >= 0, got {prefill_chunk}")
@@ -133,6 +146,14 @@ class ContinuousLlama:
                 raise ValueError("speculate is not available with tp > 1 in the continuous engine: its iterations "
                                  "run on the host path, the TP header protocol rides the device iterations")
             model.check_speculate(self.speculate)  # ValueError: what chunked prefill refuses, T * G > 16 (fused)
+        self.prefix = None
+        if prefix_cache:
+            from .prefix_cache import PrefixCache
+
+            model.check_prefix_cache()  # ValueError: no paged KV, fp8 KV cache, row-major cache, head_dim != 128
+            self.prefix = PrefixCache(model.pages)
+            model.ctx_split = True  # a suffix against a long cached prefix may run split-KV (LlamaTP.ctx_splits)
+        self.pstats = {"prefix_queries": 0, "prefix_hits": 0, "prefix_hit_tokens": 0}
         self.drafter = drafter
         self.spec = {"spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0}
         self.m = model
@@ -204,6 +225,15 @@ class ContinuousLlama:
             self._wake.notify()
         return fut
 
+    def detach_prefix_cache(self) -> None:
+        """This engine is done with its model and another one takes it over: drop the prefix index, leave
+        the page table without one and the model on the unsplit route.  No-op with the feature off."""
+        if self.prefix is not None:
+            self.prefix.clear()
+            self.m.pages.index = None
+            self.m.ctx_split = False
+            self.prefix = None
+
     def stats(self) -> dict:
         d = {"active": sum(s is not None for s in self.slots), "queued": len(self._pending),
              "iterations": self.iterations, "tokens": self.tokens, "slots": self.B,
@@ -213,6 +243,8 @@ class ContinuousLlama:
             d["kv_pages"] = self.m.pages.num_pages
         if self.speculate:
             d.update(self.spec)
+        if self.prefix is not None:
+            d.update(self.pstats, prefix_cached_pages=len(self.prefix), prefix_evictions=self.prefix.evictions)
         return d
 
     # ---------------------------------------------------------------- scheduler (rank 0)
@@ -228,6 +260,7 @@ class ContinuousLlama:
             admit = []
             pages = self.m.pages
             budget = pages.free_pages if pages is not None else 0
+            pinned = set()  # prefix caching: reclaimable pages this batch's earlier admissions will adopt
             while self._pending and free:
                 seq = self._pending[0]
                 if seq.future is not None and seq.future.cancelled():
@@ -235,9 +268,18 @@ class ContinuousLlama:
                     continue
                 if pages is not None:  # paged KV: admit while the pool holds prompt + budget (FIFO)
                     need = pages.pages_for(len(seq.ids) + seq.gp.max_new_tokens)
+                    if self.prefix is not None:
+                        # fresh pages only; a matched page nobody holds stops counting as available (the
+                        # iteration adopts every admission's matches before it assigns any page, so an
+                        # admission of the same batch cannot evict them)
+                        hit = self.prefix.match(seq.ids)
+                        pin = {pg for pg in hit if pages.refcount(pg) == 0} - pinned
+                        need += len(pin) - len(hit)
                     if need > budget:
                         break
                     budget -= need
+                    if self.prefix is not None:
+                        pinned |= pin
                 self._pending.popleft()
                 seq.slot = free.pop(0)
                 admit.append(seq)
@@ -392,6 +434,8 @@ class ContinuousLlama:
                     self.slots[i] = None
                     if self.m.pages is not None:
                         self.m.pages.release(i)
+            if self.prefix is not None:  # rows a failed step may have left half-written are never served
+                self.prefix.clear()
             if self.dev_mode:
                 st = self.m.serve_state(self.B)
                 st["active"].zero_()
@@ -441,11 +485,7 @@ class ContinuousLlama:
         m = self.m
         dev = m.device
         done: List[_Seq] = []
-        for seq in admit:
-            self.slots[seq.slot] = seq
-            seq.done = 0
-            if m.pages is not None:  # every rank assigns the same pages (same calls, same order)
-                m.pages.assign(seq.slot, len(seq.ids) + seq.gp.max_new_tokens)
+        self._admit(admit)
         pre, w = self._chunk_plan()
         if pre:
             ids, meta = self._chunk_inputs(pre, w)
@@ -453,9 +493,11 @@ class ContinuousLlama:
             slot_ids, past, lens = mt[:, 0].contiguous(), mt[:, 1].contiguous(), mt[:, 2].contiguous()
             pos = past.unsqueeze(1) + torch.arange(w, dtype=torch.int32, device=dev).unsqueeze(0)
             k = max(1, min(max(s.gp.top_k for s in pre), m.top_k_max))
-            vals, idx = m.step(ids.to(dev), pos, lens, decode=False, k=k, slot_ids=slot_ids, past=past)
+            vals, idx = m.step(ids.to(dev), pos, lens, decode=False, k=k, slot_ids=slot_ids, past=past,
+                               max_ctx=max(row[2] for row in meta))
             cv, ci = m.gather_candidates(vals, idx)
             fin = [(j, s) for j, s in enumerate(pre) if s.done + w >= len(s.ids)]  # the chunk holds their last token
+            self._index_prompts([s for _j, s in fin])
             for (j, s), t in zip(fin, self._pick_rows(cv, ci, [(j, s.gp, 0) for j, s in fin])):
                 s.out.append(t)
                 s.cur = len(s.ids)
@@ -497,11 +539,7 @@ class ContinuousLlama:
         dev = m.device
         st = m.serve_state(self.B)
         ops = m.ops
-        for seq in admit:
-            self.slots[seq.slot] = seq
-            seq.done = 0
-            if m.pages is not None:
-                m.pages.assign(seq.slot, len(seq.ids) + seq.gp.max_new_tokens)
+        self._admit(admit)
         pre, w = self._chunk_plan()
         fin: List[_Seq] = []
         if pre:
@@ -522,7 +560,9 @@ class ContinuousLlama:
             lens = mt[:, 2].to(torch.int32)
             pos = past.unsqueeze(1) + torch.arange(w, dtype=torch.int32, device=dev).unsqueeze(0)
             k = max(1, min(max(s.gp.top_k for s in pre), m.top_k_max))
-            vals, idx = m.step(ids.to(dev), pos, lens, decode=False, k=k, slot_ids=slot_ids, past=past)
+            vals, idx = m.step(ids.to(dev), pos, lens, decode=False, k=k, slot_ids=slot_ids, past=past,
+                               max_ctx=max(row[2] for row in meta))
+            self._index_prompts(fin)
             sl = mt[:, 0]
             st["pos"][sl] = mt[:, 3].to(torch.int32)
             st["lens"][sl] = mt[:, 4].to(torch.int32)
@@ -591,14 +631,11 @@ class ContinuousLlama:
         st = m.serve_state(self.B)
         ops = m.ops
         if admit:
-            for seq in admit:
-                self.slots[seq.slot] = seq
-                if m.pages is not None:
-                    m.pages.assign(seq.slot, len(seq.ids) + seq.gp.max_new_tokens)
-            S = max(len(s.ids) for s in admit)
+            self._admit(admit)
+            S = max(len(s.ids) - s.hit for s in admit)  # the longest suffix (hit = 0 without prefix caching)
             ids = torch.zeros(len(admit), S, dtype=torch.int32)
             for j, s in enumerate(admit):
-                ids[j, : len(s.ids)] = torch.tensor(s.ids, dtype=torch.int32)
+                ids[j, : len(s.ids) - s.hit] = torch.tensor(s.ids[s.hit:], dtype=torch.int32)
             # one H2D of the new slots' state: slot, pos (the pick advances it to the prompt length),
             # lens, top_k, seed; temperatures separately (fp32)
             meta = torch.tensor([[s.slot, len(s.ids) - 1, len(s.ids), s.gp.top_k, s.gp.seed] for s in admit],
@@ -606,9 +643,16 @@ class ContinuousLlama:
             temps = torch.tensor([s.gp.temperature for s in admit], dtype=torch.float32).to(dev, non_blocking=True)
             slot_ids = meta[:, 0].to(torch.int32)
             lens = meta[:, 2].to(torch.int32)
-            pos = torch.arange(S, dtype=torch.int32, device=dev).unsqueeze(0).expand(len(admit), S).contiguous()
             k = max(1, min(max(s.gp.top_k for s in admit), m.top_k_max))
-            vals, idx = m.step(ids.to(dev), pos, lens, decode=False, k=k, slot_ids=slot_ids)
+            if self.prefix is not None:  # the suffixes against the adopted rows (past = 0: a miss)
+                past = torch.tensor([s.hit for s in admit], dtype=torch.int32).to(dev, non_blocking=True)
+                pos = past.unsqueeze(1) + torch.arange(S, dtype=torch.int32, device=dev).unsqueeze(0)
+                vals, idx = m.step(ids.to(dev), pos, lens, decode=False, k=k, slot_ids=slot_ids, past=past,
+                                   max_ctx=max(len(s.ids) for s in admit))
+                self._index_prompts(admit)
+            else:
+                pos = torch.arange(S, dtype=torch.int32, device=dev).unsqueeze(0).expand(len(admit), S).contiguous()
+                vals, idx = m.step(ids.to(dev), pos, lens, decode=False, k=k, slot_ids=slot_ids)
             cv, ci = m._gather_dev(vals, idx)
             sl = meta[:, 0]
             st["pos"][sl] = meta[:, 1].to(torch.int32)
@@ -674,19 +718,23 @@ class ContinuousLlama:
         m = self.m
         done: List[_Seq] = []
         if admit:
-            for seq in admit:
-                self.slots[seq.slot] = seq
-                if m.pages is not None:  # every rank assigns the same pages (same calls, same order)
-                    m.pages.assign(seq.slot, len(seq.ids) + seq.gp.max_new_tokens)
-            S = max(len(s.ids) for s in admit)
+            self._admit(admit)
+            S = max(len(s.ids) - s.hit for s in admit)  # the longest suffix (hit = 0 without prefix caching)
             ids = torch.zeros(len(admit), S, dtype=torch.int32)
             for j, s in enumerate(admit):
-                ids[j, : len(s.ids)] = torch.tensor(s.ids, dtype=torch.int32)
+                ids[j, : len(s.ids) - s.hit] = torch.tensor(s.ids[s.hit:], dtype=torch.int32)
             lens = torch.tensor([len(s.ids) for s in admit], dtype=torch.int32, device=m.device)
-            pos = torch.arange(S, dtype=torch.int32, device=m.device).unsqueeze(0).expand(len(admit), S).contiguous()
             k = max(1, min(max(s.gp.top_k for s in admit), m.top_k_max))
             slot_ids = torch.tensor([s.slot for s in admit], dtype=torch.int32, device=m.device)
-            vals, idx = m.step(ids.to(m.device), pos, lens, decode=False, k=k, slot_ids=slot_ids)
+            if self.prefix is not None:  # the suffixes against the adopted rows (past = 0: a miss)
+                past = torch.tensor([s.hit for s in admit], dtype=torch.int32, device=m.device)
+                pos = past.unsqueeze(1) + torch.arange(S, dtype=torch.int32, device=m.device).unsqueeze(0)
+                vals, idx = m.step(ids.to(m.device), pos, lens, decode=False, k=k, slot_ids=slot_ids, past=past,
+                                   max_ctx=max(len(s.ids) for s in admit))
+                self._index_prompts(admit)
+            else:
+                pos = torch.arange(S, dtype=torch.int32, device=m.device).unsqueeze(0).expand(len(admit), S).contiguous()
+                vals, idx = m.step(ids.to(m.device), pos, lens, decode=False, k=k, slot_ids=slot_ids)
             cv, ci = m.gather_candidates(vals, idx)
             for s, t in zip(admit, self._pick_rows(cv, ci, [(j, s.gp, 0) for j, s in enumerate(admit)])):
                 s.out.append(t)
@@ -717,6 +765,35 @@ class ContinuousLlama:
             done += self._retire()
         self.iterations += 1
         return done
+
+    def _admit(self, admit: List[_Seq]) -> None:
+        """Seat this iteration's admissions and give them their pages -- every rank makes the same calls
+        in the same order, so every rank holds the same pages.  Prefix caching: first every admission
+        adopts (pins) the pages the index matches for its prompt, only then does any of them take
+        fresh pages, so none can evict what another one of the batch shares."""
+        pages = self.m.pages
+        for seq in admit:
+            self.slots[seq.slot] = seq
+            seq.done = seq.hit = 0
+            if self.prefix is not None:
+                hit = self.prefix.match(seq.ids, stamp=self.iterations)
+                pages.adopt(seq.slot, hit)
+                seq.hit = len(hit) * pages.page_rows
+                if self.prefill_chunk:
+                    seq.done = seq.hit  # the chunks start after the adopted rows
+                self.pstats["prefix_queries"] += 1
+                self.pstats["prefix_hits"] += bool(hit)
+                self.pstats["prefix_hit_tokens"] += seq.hit
+        if pages is not None:
+            for seq in admit:
+                pages.assign(seq.slot, len(seq.ids) + seq.gp.max_new_tokens)
+
+    def _index_prompts(self, seqs: List[_Seq]) -> None:
+        """Prefix caching: the prompts of ``seqs`` are completely in the cache (this iteration's prefill
+        or last chunk has been issued; later launches are ordered behind it) -- index their full pages."""
+        if self.prefix is not None:
+            for s in seqs:
+                self.prefix.insert(s.ids, self.m.pages.pages_of(s.slot), self.iterations)
 
     def _spec_ok(self, active: List[_Seq]) -> bool:
         """Is this iteration's decode step a verify step?  A function of the slots alone."""

@@ -115,6 +115,7 @@ from .transformer import (  # noqa: F401
     flash_attention,
     flash_attention_ctx,
     flash_attention_rows,
+    flash_ctx_workspace_elems,
     kv_append,
     last_rows,
     layernorm,

@@ -98,6 +98,7 @@ _SIGS = {
     "mls_flash_attention": [P, P, P, P, I, I, I, I, I, I, I, I, I, P, I, F, P],
     "mls_flash_attention_rows": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P, I, F, P],
     "mls_flash_attention_ctx": [P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, F, P],
+    "mls_flash_attention_ctx_split": [P, P, P, P, P, L, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F, P],
     "mls_decode_attention_multi": [P, P, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F, P],
     "mls_decode_combine": [P, P, P, I, P, I, I, I, I, P],
     "mls_skinny_gemm": [P, P, P, P, P, P, SZ, I, I, I, I, I, P],
@@ -157,6 +158,7 @@ DEBUG_CODES = {
     311: "flash attention (ctx): not 0 <= past[b] <= lens[b] <= the rows of a slot",
     312: "flash attention (ctx): slot outside the cache",
     313: "flash attention (ctx): page id outside the pool",
+    314: "flash attention (ctx, split): lens[b] beyond the host bound max_ctx that sized the splits",
     321: "decode attention (multi): not 0 <= past[b] <= lens[b] <= the rows of a slot / the split grid (max_len)",
     322: "decode attention (multi): slot outside the cache",
     323: "decode attention (multi): page id outside the pool",

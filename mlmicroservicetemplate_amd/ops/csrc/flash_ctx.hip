@@ -169,6 +169,221 @@ __global__ __launch_bounds__(256, 3) void flash_ctx_kernel(const CtxArgs a) {
   }
 }
 
+// ---- split-KV variant: a few queries against a long cached context (a prefix-cache hit) --------------
+// flash_ctx_kernel's grid is (q tiles, Hq, B): 32 new tokens against 4064 cached rows is Hq blocks
+// that each walk 64 key tiles.  flash_ctx_split_kernel cuts every (b, q tile)'s key tiles into nsplit
+// runs of tiles_per_split tiles -- both from the HOST bound on past + n, so every block of a launch
+// cuts at the same tile boundaries whatever lens[] holds, per-slot and paged alike -- and stores the
+// unnormalised partial (O, m, l) of its run to an fp32 workspace; flash_ctx_combine_kernel merges the
+// partials of a (token, q head) in split order and writes the bf16 row.  Staging loop, per-tile
+// descriptors, page-table read-ahead and edge masks are flash_ctx_kernel's text; its own are the
+// tile loop's bounds and the epilogue.
+struct CtxSplitArgs {
+  CtxArgs c;
+  float* ws_o;   // [nsplit][B*S][Hq][128] unnormalised O
+  float* ws_ml;  // [nsplit][B*S][Hq][2]   m (log2 domain, as m_run) and l
+  int nsplit, tiles_per_split;
+};
+
+// valid queries of batch row b (flash_ctx_kernel's clamps), for the combine's padding rows
+MLS_DEV int ctx_valid_queries(const CtxArgs& a, int b) {
+  const int slot = a.slot_ids ? a.slot_ids[b] : b;
+  const bool slot_ok = slot >= 0 && slot < a.slots;
+  const int L = slot_ok ? min(a.lens[b], a.rows_cap) : 0;
+  const int P = max(0, min(a.past[b], L));
+  return min(L - P, a.S);
+}
+
+__global__ __launch_bounds__(256, 3) void flash_ctx_split_kernel(const CtxSplitArgs sa) {
+  const CtxArgs& a = sa.c;
+  constexpr int D = 128, NW = 4;
+  using T = FlashTile<D>;
+  constexpr int NT = 64 * NW;
+  constexpr int BQ = 16 * NW, BKV = T::BKV, CPR = T::CPR;
+  __shared__ __attribute__((aligned(16))) char smem[T::K_BYTES + T::V_BYTES];
+  char* Ks = smem;
+  char* Vs = smem + T::K_BYTES;
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4, fr = lane & 15;
+  const int b = blockIdx.z / sa.nsplit, sp = blockIdx.z % sa.nsplit, h = blockIdx.y;
+  const int hk = h / (a.Hq / a.Hkv);
+  const int q0 = blockIdx.x * BQ;
+  const int qw = q0 + wid * 16;
+  const bool paged = a.page_table != nullptr;
+
+  const int slot = __builtin_amdgcn_readfirstlane(a.slot_ids ? a.slot_ids[b] : b);
+  const int L0 = __builtin_amdgcn_readfirstlane(a.lens[b]);
+  const int P0 = __builtin_amdgcn_readfirstlane(a.past[b]);
+  const bool slot_ok = slot >= 0 && slot < a.slots;
+  MLS_CHECK(slot_ok, 312);
+  MLS_CHECK(P0 >= 0 && P0 <= L0 && L0 <= a.rows_cap, 311);
+  const int L = slot_ok ? min(L0, a.rows_cap) : 0;
+  const int P = max(0, min(P0, L));
+  const int n = min(L - P, a.S);
+  const long tokq = (long)b * a.S;
+
+  if (q0 >= n) return;  // padding rows only: the combine writes their zeros without reading a partial
+
+  const rsrc_t qr = make_rsrc(a.q, a.q_bytes);
+  bf16x8 qf[T::KK];
+  {
+    const int q = qw + fr;
+#pragma unroll
+    for (int kk = 0; kk < T::KK; ++kk) {
+      const int off = q < a.S ? (int)(((tokq + q) * a.q_stride + (long)h * D + 32 * kk + 8 * g) * 2) : OOB;
+      qf[kk] = __builtin_bit_cast(bf16x8, bload16(qr, off));
+    }
+  }
+
+  f32x4 acc_o[T::DT];
+#pragma unroll
+  for (int dt = 0; dt < T::DT; ++dt) acc_o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m_run = -1e30f, l_run = 0.f;
+
+  const int kv_end = min(L, P + q0 + BQ);
+  const int ntiles = (kv_end + BKV - 1) / BKV;
+  // the host bound on past + n covers every tile (else the tail tiles would be dropped silently)
+  MLS_CHECK(ntiles <= sa.nsplit * sa.tiles_per_split, 314);
+  const int kt0 = sp * sa.tiles_per_split;                 // this split's run of key tiles: [kt0, kt1)
+  const int kt1 = min(kt0 + sa.tiles_per_split, ntiles);   // kt0 >= kt1: an empty split (O = 0, l = 0)
+  const int pw = P + qw;
+
+  constexpr int NI = T::ni(NT);
+  const int* tab = paged ? a.page_table + (long)slot * a.pages_per_seq : nullptr;
+  auto page_of = [&](int kt) { return paged && kt < kt1 ? __builtin_amdgcn_readfirstlane(tab[kt]) : 0; };
+  uint4 kreg[NI], vreg[NI];
+  auto load_tile = [&](int kt, int pg) {
+    const bool blk_ok = !paged || (pg >= 0 && pg < a.blocks);
+    MLS_CHECK(blk_ok, 313);
+    const long row0 = paged ? ((long)(blk_ok ? pg : 0) * a.Hkv + hk) * BKV
+                            : ((long)slot * a.Hkv + hk) * a.block_rows + (long)kt * BKV;
+    const uint32_t bytes = blk_ok ? (uint32_t)(min(BKV, L - kt * BKV) * D * 2) : 0u;
+    const rsrc_t kr = make_rsrc(a.kc + row0 * D, bytes);
+    const rsrc_t vr = make_rsrc(a.vc + row0 * D, bytes);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      kreg[i] = bload16(kr, (tid + NT * i) * 16);
+      vreg[i] = bload16(vr, (tid + NT * i) * 16);
+    }
+  };
+  const float c = a.scale_log2;
+  const int causal = 1;
+  const Flash2Tile<D, true> tile_body{acc_o, m_run, l_run, qf, Ks, Vs, causal, pw, L, c, g, fr};
+  if (kt0 < kt1) {  // (a tile at or past ntiles has no valid byte count: never described)
+    int pg_next = page_of(kt0 + 1);
+    load_tile(kt0, page_of(kt0));
+    for (int kt = kt0; kt < kt1; ++kt) {
+      const int kv0 = kt * BKV;
+#pragma unroll
+      for (int i = 0; i < NI; ++i) {
+        const int idx = tid + NT * i;
+        const int row = idx / CPR, ch = idx % CPR;
+        *reinterpret_cast<uint4*>(Ks + row * (D * 2) + ((ch ^ (row & (CPR - 1))) * 16)) = kreg[i];
+        *reinterpret_cast<uint4*>(Vs + row * T::VST + ch * 16) = vreg[i];
+      }
+      __syncthreads();
+      if (kt + 1 < kt1) {
+        load_tile(kt + 1, pg_next);
+        pg_next = page_of(kt + 2);
+      }
+      tile_body(kv0, kv0 + BKV > L || kv0 + BKV - 1 > pw);
+      __syncthreads();
+    }
+  }
+
+  // ---- the partial as it stands: lane (g, fr) holds O[q = qw + fr][16 dt + 4 g .. + 3]; a query with
+  // no visible key in this run keeps m = -1e30, l = 0, O = 0 (2^(m - M) is 0 in the combine)
+  float l = l_run + xor16_f(l_run);
+  l += xor32_f(l);
+  const int q = qw + fr;
+  if (q < a.S) {
+    const long row = ((long)sp * a.B * a.S + tokq + q) * a.Hq + h;
+    float* po = sa.ws_o + row * D + 4 * g;
+#pragma unroll
+    for (int dt = 0; dt < T::DT; ++dt)
+      *reinterpret_cast<float4*>(po + 16 * dt) = make_float4(acc_o[dt][0], acc_o[dt][1], acc_o[dt][2], acc_o[dt][3]);
+    if (g == 0) *reinterpret_cast<float2*>(sa.ws_ml + row * 2) = make_float2(m_run, l);
+  }
+}
+
+// one (token, q head) per 32 lanes, 4 output columns per lane; splits summed in split order
+__global__ __launch_bounds__(256) void flash_ctx_combine_kernel(const CtxSplitArgs sa) {
+  const CtxArgs& a = sa.c;
+  constexpr int D = 128;
+  const long rows = (long)a.B * a.S * a.Hq;
+  const long row = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
+  if (row >= rows) return;
+  const int d = (threadIdx.x & 31) * 4;
+  const int h = (int)(row % a.Hq);
+  const long tok = row / a.Hq;
+  const int b = (int)(tok / a.S), q = (int)(tok % a.S);
+  float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+  float l = 0.f;
+  if (q < ctx_valid_queries(a, b)) {
+    float M = -1e30f;
+    for (int s = 0; s < sa.nsplit; ++s) M = fmaxf(M, sa.ws_ml[(s * rows + row) * 2]);
+    for (int s = 0; s < sa.nsplit; ++s) {
+      const float2 ml = *reinterpret_cast<const float2*>(sa.ws_ml + (s * rows + row) * 2);
+      const float w = exp2f(ml.x - M);
+      const float4 p = *reinterpret_cast<const float4*>(sa.ws_o + (s * rows + row) * D + d);
+      o.x = fmaf(w, p.x, o.x);
+      o.y = fmaf(w, p.y, o.y);
+      o.z = fmaf(w, p.z, o.z);
+      o.w = fmaf(w, p.w, o.w);
+      l = fmaf(w, ml.y, l);
+    }
+  }
+  const float inv_l = l > 0.f ? 1.f / l : 0.f;  // padding rows and tokens with no visible key: zeros
+  bf16x4 o4;
+  o4[0] = (bf16)(o.x * inv_l);
+  o4[1] = (bf16)(o.y * inv_l);
+  o4[2] = (bf16)(o.z * inv_l);
+  o4[3] = (bf16)(o.w * inv_l);
+  *reinterpret_cast<bf16x4*>(a.o + tok * a.o_stride + (long)h * D + d) = o4;
+}
+
+// The split entry's argument checks and CtxArgs.  A COPY of the checks mls_flash_attention_ctx makes
+// inline (that entry point keeps its text): the two launches share one contract, so a check changed in
+// one place must be changed in the other.
+int ctx_args(CtxArgs& a, const void* qkv, const void* k_cache, const void* v_cache, void* o, int q_stride, int o_stride,
+             const int* past, const int* lens, const int* slot_ids, const int* page_table, int pages_per_seq,
+             int slots, int B, int S, int Hq, int Hkv, int D, long blocks, int hm_rows, float scale) {
+  if (B <= 0 || S <= 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv || blocks <= 0 || slots <= 0) return MLS_BAD_ARG;
+  if (!qkv || !k_cache || !v_cache || !o || !past || !lens) return MLS_BAD_ARG;
+  if (D != 128) return MLS_UNSUPPORTED;
+  if (hm_rows <= 0) return MLS_UNSUPPORTED;
+  if (page_table && (hm_rows != 64 || pages_per_seq <= 0)) return MLS_UNSUPPORTED;
+  if (!page_table && slots != blocks) return MLS_BAD_ARG;
+  if (q_stride % 8 || o_stride % 8 || q_stride < Hq * D || o_stride < Hq * D) return MLS_BAD_ARG;
+  if ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(o) | reinterpret_cast<uintptr_t>(k_cache) |
+       reinterpret_cast<uintptr_t>(v_cache)) & 15)
+    return MLS_BAD_ARG;
+  if (blocks > 0x7FFFFFFFl || (long)B * S > 0x7FFFFFFFl) return MLS_BAD_ARG;
+  const size_t qb = ((size_t)((long)B * S - 1) * q_stride + (size_t)Hq * D) * 2;
+  if (qb >= 0x7FFFFFFFull) return MLS_UNSUPPORTED;
+  a.q = (const bf16*)qkv;
+  a.kc = (const bf16*)k_cache;
+  a.vc = (const bf16*)v_cache;
+  a.o = (bf16*)o;
+  a.q_stride = q_stride;
+  a.o_stride = o_stride;
+  a.q_bytes = (uint32_t)qb;
+  a.past = past;
+  a.lens = lens;
+  a.slot_ids = slot_ids;
+  a.page_table = page_table;
+  a.pages_per_seq = pages_per_seq;
+  a.B = B; a.S = S; a.Hq = Hq; a.Hkv = Hkv;
+  a.blocks = (int)blocks;
+  a.block_rows = hm_rows;
+  a.slots = slots;
+  const long cap = page_table ? (long)pages_per_seq * 64 : (long)hm_rows;
+  a.rows_cap = (int)(cap > 0x7FFFFFC0l ? 0x7FFFFFC0l : cap);
+  a.scale_log2 = scale * 1.4426950408889634f;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -216,6 +431,34 @@ int mls_flash_attention_ctx(const void* qkv, const void* k_cache, const void* v_
   a.scale_log2 = scale * 1.4426950408889634f;
   dim3 grid((S + 63) / 64, Hq, B);
   hipLaunchKernelGGL(flash_ctx_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+// Split-KV launch of the same contract + the combine.  max_ctx: a host bound on lens[] (past + n); it and
+// nsplit fix tiles_per_split = ceil(ceil(min(max_ctx, slot rows) / 64) / nsplit) for every block.
+// workspace: fp32, nsplit * B*S*Hq * (D + 2) elements (ws_elems: what the caller holds).
+int mls_flash_attention_ctx_split(const void* qkv, const void* k_cache, const void* v_cache, void* o, void* workspace,
+                                  long ws_elems, int q_stride, int o_stride, const int* past, const int* lens,
+                                  const int* slot_ids, const int* page_table, int pages_per_seq, int slots, int B,
+                                  int S, int Hq, int Hkv, int D, long blocks, int hm_rows, int max_ctx, int nsplit,
+                                  float scale, void* stream) {
+  CtxSplitArgs sa{};
+  const int rc = ctx_args(sa.c, qkv, k_cache, v_cache, o, q_stride, o_stride, past, lens, slot_ids, page_table,
+                          pages_per_seq, slots, B, S, Hq, Hkv, D, blocks, hm_rows, scale);
+  if (rc) return rc;
+  if (nsplit < 1 || nsplit > 64 || max_ctx < 1 || !workspace) return MLS_BAD_ARG;
+  if (reinterpret_cast<uintptr_t>(workspace) & 15) return MLS_BAD_ARG;  // 16-B partial stores
+  const long rows = (long)B * S * Hq;
+  if ((long)B * nsplit > 65535 || rows > 0x7FFFFFFFl / 8) return MLS_BAD_ARG;  // grid z; the combine's grid x
+  if (ws_elems < (long)nsplit * rows * (D + 2)) return MLS_BAD_ARG;
+  const int ntiles = ((max_ctx < sa.c.rows_cap ? max_ctx : sa.c.rows_cap) + 63) / 64;
+  sa.nsplit = nsplit;
+  sa.tiles_per_split = (ntiles + nsplit - 1) / nsplit;
+  sa.ws_o = (float*)workspace;
+  sa.ws_ml = sa.ws_o + (long)nsplit * rows * D;
+  dim3 grid((S + 63) / 64, Hq, B * nsplit);
+  hipLaunchKernelGGL(flash_ctx_split_kernel, grid, dim3(256), 0, (hipStream_t)stream, sa);
+  hipLaunchKernelGGL(flash_ctx_combine_kernel, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, (hipStream_t)stream, sa);
   return (int)hipGetLastError();
 }
 

@@ -225,10 +225,17 @@ def flash_attention_rows(q: torch.Tensor, kv: torch.Tensor, batch: int, seq: int
     return out
 
 
+def flash_ctx_workspace_elems(batch: int, seq: int, n_q_heads: int, head_dim: int, splits: int) -> int:
+    """fp32 elements of :func:`flash_attention_ctx`'s split-KV workspace: per (split, token, q head)
+    the unnormalised O row and (m, l)."""
+    return int(splits) * batch * seq * n_q_heads * (head_dim + 2)
+
+
 def flash_attention_ctx(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, past: torch.Tensor,
                         lens: torch.Tensor, batch: int, seq: int, n_q_heads: int, n_kv_heads: int, head_dim: int, *,
                         slot_ids: Optional[torch.Tensor] = None, page_table: Optional[torch.Tensor] = None,
-                        scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        scale: Optional[float] = None, out: Optional[torch.Tensor] = None, splits: int = 1,
+                        max_ctx: Optional[int] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Chunked-prefill attention: a chunk of ``seq`` new queries per batch row against the KV cache.
     Query ``i`` of row ``b`` (``i < lens[b] - past[b]``) sits at position ``past[b] + i`` and attends to
     cache rows ``0 .. past[b] + i`` of slot ``slot_ids[b]`` (``b`` when None).  Q is read in place from
@@ -238,8 +245,22 @@ def flash_attention_ctx(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
     nothing is read on the host (capturable).  Head-major bf16 caches only, D = 128:
     ``[slots, Hkv, max_seq, D]``, or page pools ``[pages, Hkv, 64, D]`` through ``page_table
     [slots, pages_per_seq]``.  Returns ``[B*S, Hq*D]``; rows at or past a row's valid length are
-    unspecified."""
+    unspecified.
+
+    ``splits`` > 1 (at most 64): split-KV -- every (row, query tile)'s key tiles are cut into ``splits``
+    runs that separate blocks walk, then merged (few queries against a long context: a prefix-cache
+    hit).  It needs ``max_ctx``, a host bound on ``lens`` that fixes where the runs are cut, and an
+    fp32 ``workspace`` of :func:`flash_ctx_workspace_elems` elements (allocated when None).  Padding
+    rows are zeros on this route.  ``max_ctx`` is the caller's promise: ``lens`` is device data the host
+    never reads, so a ``lens[b]`` above it is NOT refused -- the key tiles past the last split are
+    dropped and that row's result is silently wrong (nothing is read or written out of bounds); only the
+    ``MLS_DEBUG`` build reports it (code 314).  A bound that is too large is always safe."""
     dev = qkv.device
+    splits = int(splits)
+    if splits < 1 or splits > 64:
+        raise ValueError(f"flash_attention_ctx: splits must be in [1, 64], got {splits}")
+    if splits > 1 and max_ctx is None:
+        raise ValueError("flash_attention_ctx: splits > 1 needs max_ctx (a host bound on lens)")
     _need(qkv, "qkv", torch.bfloat16, dev)
     _need(k_cache, "k_cache", torch.bfloat16, dev)
     _need(v_cache, "v_cache", torch.bfloat16, dev)
@@ -282,6 +303,26 @@ def flash_attention_ctx(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
     else:
         out = torch.empty(batch * seq, n_q_heads * head_dim, device=dev, dtype=torch.bfloat16)
     scale = head_dim ** -0.5 if scale is None else scale
+    if splits > 1:
+        if int(max_ctx) < 1:
+            raise ValueError(f"flash_attention_ctx: max_ctx must be positive, got {max_ctx}")
+        need = flash_ctx_workspace_elems(batch, seq, n_q_heads, head_dim, splits)
+        if workspace is None:
+            workspace = torch.empty(need, device=dev, dtype=torch.float32)
+        _need(workspace, "workspace", torch.float32, dev)
+        if workspace.numel() < need or not workspace.is_contiguous():
+            raise ValueError(f"flash_attention_ctx: the workspace holds {workspace.numel()} fp32 elements, "
+                             f"{splits} splits need {need} (contiguous)")
+        if batch * splits > 65535:
+            raise ValueError(f"flash_attention_ctx: batch x splits = {batch * splits} exceeds the grid's 65535")
+        rc = lib().mls_flash_attention_ctx_split(qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                                 out.data_ptr(), workspace.data_ptr(), workspace.numel(), W,
+                                                 out.stride(0), past.data_ptr(), lens.data_ptr(), _ptr(slot_ids),
+                                                 _ptr(page_table), pps, slots, batch, seq, n_q_heads, n_kv_heads,
+                                                 head_dim, blocks, rows, min(int(max_ctx), 0x7FFFFFFF), splits, float(scale),
+                                                 stream_ptr(dev))
+        check(rc, "mls_flash_attention_ctx_split")
+        return out
     rc = lib().mls_flash_attention_ctx(qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), W,
                                        out.stride(0), past.data_ptr(), lens.data_ptr(), _ptr(slot_ids),
                                        _ptr(page_table), pps, slots, batch, seq, n_q_heads, n_kv_heads, head_dim,

@@ -38,6 +38,7 @@ class LlamaPlugin(ModelPlugin):
         self.comm_dev = None
         self.prefill_chunk = 0
         self.speculate, self.speculate_ngram = 0, 3
+        self.prefix_cache = False
         self._lock = threading.Lock()
 
     def init(self, ctx: PluginContext) -> None:
@@ -48,6 +49,7 @@ class LlamaPlugin(ModelPlugin):
         extra = s.model_yaml() if hasattr(s, "model_yaml") else {}
         weight_dtype = self.parse_weight_dtype(extra)  # before any weight is read or allocated
         self.speculate, self.speculate_ngram = self.parse_speculate(extra)
+        self.prefix_cache = self.parse_prefix_cache(extra)
         size = extra.get("config", "8b")
         cfg = llama.LLAMA3_8B if size == "8b" else llama.tiny_config(**extra.get("overrides", {}))
         tp = ctx.world_size if int(s.TP) > 1 else 1
@@ -79,6 +81,10 @@ class LlamaPlugin(ModelPlugin):
                                    kv_dtype=kv_dtype, weight_dtype=weight_dtype)
         if self.speculate:  # refused at start-up on the lockstep path too (the engine below checks for itself)
             self.model.check_speculate(self.speculate)
+        if self.prefix_cache:  # no paged KV, fp8 KV, row-major cache, head_dim != 128: refused, nothing falls back
+            self.model.check_prefix_cache()
+            if not bool(getattr(s, "CONTINUOUS_BATCHING", True)):
+                raise ValueError("prefix_cache needs continuous batching (the lockstep generate path has no page sharing)")
         self.tok = llama.LlamaTokenizer(cfg, extra.get("tokenizer_file"))
         self.cfg = cfg
         self.engine = None
@@ -87,12 +93,13 @@ class LlamaPlugin(ModelPlugin):
 
             self.engine = ContinuousLlama(self.model, max_queue=int(s.MAX_QUEUE), channel=self if tp > 1 else None,
                                           prefill_chunk=self.prefill_chunk, speculate=self.speculate,
-                                          drafter=self._drafter())
+                                          drafter=self._drafter(), prefix_cache=self.prefix_cache)
             if ctx.rank == 0:
                 self.engine.start()
         logger.info("llama ready: tp=%d rank=%d backend=%s device=%s kv_dtype=%s kv_bytes_per_token=%d "
-                    "weight_dtype=%s layer_weight_bytes=%d", tp, ctx.rank, backend, dev, kv_dtype,
-                    self.kv_page_bytes(cfg, tp, backend, kv_dtype) // 64, weight_dtype, self.model.layer_weight_bytes())
+                    "weight_dtype=%s layer_weight_bytes=%d prefix_cache=%s", tp, ctx.rank, backend, dev, kv_dtype,
+                    self.kv_page_bytes(cfg, tp, backend, kv_dtype) // 64, weight_dtype, self.model.layer_weight_bytes(),
+                    self.prefix_cache)
 
     @staticmethod
     def parse_weight_dtype(extra: dict) -> str:
@@ -102,6 +109,15 @@ class LlamaPlugin(ModelPlugin):
         if wd not in ("bf16", "int4"):
             raise ValueError(f"weight_dtype must be 'bf16' or 'int4', got {wd!r}")
         return wd
+
+    @staticmethod
+    def parse_prefix_cache(extra: dict) -> bool:
+        """MODEL_CONFIG ``prefix_cache``: ``true`` | ``false`` (default): share the KV pages of repeated
+        prompt prefixes between requests (models/prefix_cache.py; needs ``kv_pages``)."""
+        v = extra.get("prefix_cache", False)
+        if not isinstance(v, bool):
+            raise ValueError(f"prefix_cache must be true or false, got {v!r}")
+        return v
 
     @staticmethod
     def parse_speculate(extra: dict):
@@ -383,5 +399,5 @@ class LlamaPlugin(ModelPlugin):
         if self.model is not None:
             d.update({"tp": self.model.tp, "backend": self.model.backend, "max_batch": self.model.max_batch,
                       "max_seq": self.model.max_seq, "speculate": self.speculate,
-                      "speculate_ngram": self.speculate_ngram})
+                      "speculate_ngram": self.speculate_ngram, "prefix_cache": self.prefix_cache})
         return d
