@@ -341,6 +341,10 @@ class ResNet50Fused:
         self.chain_conv2 = mode != "0"
         self.chain_conv2_shapes = ops.CHAIN_CONV2_SHAPES if mode == "2" else CHAIN_CONV2_DEFAULT
         self.chain_conv2_skip: set = {b for b in os.environ.get("MLS_CHAIN_CONV2_SKIP", "").split(",") if b}
+        # a chained stage boundary in front of a stride-2 dual block (layer1.2 -> layer2.0, layer2.3 ->
+        # layer3.0) stores only the pixels (2i, 2j) of its block output: the downsample projection is
+        # its only reader besides the chained conv1.  MLS_CHAIN_Y_STRIDE2=0 stores the full tensor (A/B)
+        self.chain_y_stride2 = os.environ.get("MLS_CHAIN_Y_STRIDE2", "1") != "0"
         # layer3 boundaries (K 256, N1 1024, N2 256): instantiated and tested, off by default --
         # interleaved A/B 51.3k vs 52.2k req/s with them (profiles/r2_chain_v2_ab.jsonl)
         self.chain_l3 = os.environ.get("MLS_CHAIN_L3", "0") == "1"
@@ -455,6 +459,18 @@ class ResNet50Fused:
         return (c2.k == 3 and c2.stride == 1 and c2.pad == 1 and c2.cin == 64 and c2.cout == 64
                 and shape in self.chain_conv2_shapes and t1.shape[2] <= self.ops.CHAIN_CONV2_MAX_W)
 
+    def _y_stride2(self, p: str, nxt: str, dual: bool, t1: torch.Tensor, conv2_fused: bool) -> bool:
+        """Store only ``y[:, ::2, ::2]`` at the chained boundary ``p`` -> ``nxt`` (ops ``y_stride2``)?
+        ``nxt`` must read y through its stride-2 projection alone: a dual block, so no residual."""
+        if not self.chain_y_stride2 or not (self.fuse_down and nxt.endswith(".0")):
+            return False
+        down, c3 = self.specs[nxt + ".down"], self.specs[p + ".conv3"]
+        kb = self.specs[p + ".down"].cin if dual else 0
+        n12 = (c3.cout, self.specs[nxt + ".conv1"].cout)
+        ok = ((kb,) + n12 in self.ops.CHAIN_CONV2_Y_STRIDE2_SHAPES if conv2_fused
+              else (c3.cin + kb,) + n12 in self.ops.CHAIN_Y_STRIDE2_SHAPES)
+        return ok and down.k == 1 and down.stride == 2 and t1.shape[1] % 2 == 0 and t1.shape[2] % 2 == 0
+
     def forward(self, images_u8_nhwc: torch.Tensor) -> torch.Tensor:
         """uint8 ``[B,H,W,3]`` on device -> bf16 logits ``[B, num_classes]``."""
         ops = self.ops
@@ -507,23 +523,28 @@ class ResNet50Fused:
                 x = ops.maxpool2d_nhwc(x, 3, 2, 1)
             t1 = self._conv(x, "layer1.0.conv1", ops.ACT_RELU)
         blocks = [(si, bi) for si, (nblocks, _m, _c, _s) in enumerate(STAGES) for bi in range(nblocks)]
+        x_sub = False  # x holds only the pixels (2i, 2j) of the previous block's output (y_stride2)
         for idx, (si, bi) in enumerate(blocks):
             p = f"layer{si + 1}.{bi}"
             nxt = f"layer{blocks[idx + 1][0] + 1}.{blocks[idx + 1][1]}" if idx + 1 < len(blocks) else None
             dual = bi == 0 and self.fuse_down
+            # the dual operand's sampling stride of x: 1 where the boundary before already subsampled it
+            ds = (1 if x_sub else self.specs[p + ".down"].stride) if dual else 1
+            x_sub = False
             chained = nxt is not None and self._chained(p, nxt, dual)
             if chained and self._conv2_fused(p, nxt, dual, t1):
                 # conv2, conv3 (+ residual / downsample) and the next block's conv1 in one kernel
                 w1n, b1n = self.w[nxt + ".conv1"], self.b[nxt + ".conv1"]
                 w1n = w1n.reshape(w1n.shape[0], -1)
                 w2, b2 = self.w[p + ".conv2"], self.b[p + ".conv2"]
+                x_sub = self._y_stride2(p, nxt, dual, t1, True)
                 if dual:
                     x, t1 = ops.conv3x3_chain(t1, w2, b2, self.dual_w[p], self.dual_b[p], w1n, b1n, a2=x,
-                                              stride2=self.specs[p + ".down"].stride)
+                                              stride2=ds, y_stride2=x_sub)
                 else:
                     w3 = self.w[p + ".conv3"]
                     x, t1 = ops.conv3x3_chain(t1, w2, b2, w3.reshape(w3.shape[0], -1), self.b[p + ".conv3"], w1n,
-                                              b1n, residual=x)
+                                              b1n, residual=x, y_stride2=x_sub)
                 continue
             t2 = self._conv(t1, p + ".conv2", ops.ACT_RELU)
             if chained:
@@ -531,18 +552,19 @@ class ResNet50Fused:
                 # kernel: the block output goes to HBM once and is never read back
                 w1n, b1n = self.w[nxt + ".conv1"], self.b[nxt + ".conv1"]
                 w1n = w1n.reshape(w1n.shape[0], -1)
+                x_sub = self._y_stride2(p, nxt, dual, t2, False)
                 if dual:
                     x, t1 = ops.conv1x1_chain(t2, self.dual_w[p], self.dual_b[p], w1n, b1n, a2=x,
-                                              stride2=self.specs[p + ".down"].stride)
+                                              stride2=ds, y_stride2=x_sub)
                 else:
                     w3 = self.w[p + ".conv3"]
                     x, t1 = ops.conv1x1_chain(t2, w3.reshape(w3.shape[0], -1), self.b[p + ".conv3"], w1n, b1n,
-                                              residual=x)
+                                              residual=x, y_stride2=x_sub)
                 continue
             if dual:
                 cfg, sk = self.tuning.get(p + ".dual", (0, 0))
-                x = ops.conv1x1_dual(t2, x, self.dual_w[p], self.dual_b[p], stride2=self.specs[p + ".down"].stride,
-                                     act=ops.ACT_RELU, workspace=self.workspace, cfg=cfg, splitk=sk)
+                x = ops.conv1x1_dual(t2, x, self.dual_w[p], self.dual_b[p], stride2=ds, act=ops.ACT_RELU,
+                                     workspace=self.workspace, cfg=cfg, splitk=sk)
             else:
                 identity = self._conv(x, p + ".down", ops.ACT_NONE) if bi == 0 else x
                 if nxt is None and pool:  # the network's last conv: average pool in its epilogue

@@ -81,7 +81,9 @@ from .vision import (  # noqa: F401
     CFG_PIPE,
     CHAIN_CONV2_MAX_W,
     CHAIN_CONV2_SHAPES,
+    CHAIN_CONV2_Y_STRIDE2_SHAPES,
     CHAIN_SHAPES,
+    CHAIN_Y_STRIDE2_SHAPES,
     HALO_CFGS,
     PIPE_CFGS,
     PIPE_VARIANTS,

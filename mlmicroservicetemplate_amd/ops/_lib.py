@@ -36,6 +36,8 @@ _SIGS = {
     "mls_conv2d_dual": [P, P, P, P, P, P, SZ, I, I, I, I, I, I, I, I, I, I, I, I, P],
     "mls_conv_chain": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     "mls_conv_chain_conv2": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
+    "mls_conv_chain_y2": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
+    "mls_conv_chain_conv2_y2": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     "mls_gemm": [P, P, P, P, P, P, P, SZ, I, I, I, I, I, I, P],
     "mls_gemm_heuristic": [I, I, I, _c.POINTER(I), _c.POINTER(I)],
     "mls_gemm_tile": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P, _c.c_longlong, P, I, P],

@@ -96,6 +96,19 @@ MLS_DEV int row_swz(int r) {
   else return (r & 1) | ((r >> 1) & 2);
 }
 
+// Y2 (template parameter of both kernels): y feeds only a stride-2 1x1 projection (the last block of
+// a stage whose successor is a dual block), so only the pixels with even oh and even ow are kept,
+// compactly as [B][Hc][Wc][N1], Hc = (Ho + 1) / 2, Wc = (Wo + 1) / 2.  Element offset of output
+// row m's y row in that tensor, or -1 for a pixel that is not kept (or a row past M).  The store of
+// such a row is still issued, at the out-of-range offset: every wave keeps issuing Y_ST stores per
+// chunk, which is what the counted vmcnt waits assume.  Branch-free, and computed once per tile.
+MLS_DEV int y2_row_off(const ChainArgs& a, int m, int N1) {
+  const int b = fastdiv(m, a.fd_howo), rem = m - b * (a.Ho * a.Wo);
+  const int oh = fastdiv(rem, a.fd_wo), ow = rem - oh * a.Wo;
+  const int off = ((b * ((a.Ho + 1) >> 1) + (oh >> 1)) * ((a.Wo + 1) >> 1) + (ow >> 1)) * N1;
+  return (m < a.M && !((oh | ow) & 1)) ? off : -1;
+}
+
 // KS = (Ka + Kb) / 64 A1 slabs; KSA = Ka / 64 of them from a1, the rest from a2 (dual).  CW = the
 // output-channel chunk of GEMM1 = the K slab of GEMM2 (64, or 32 where the weights of a 64-wide
 // stage would not fit the LDS next to the A tile: layer2 -> 3 and layer3).  N1 is a template
@@ -103,7 +116,7 @@ MLS_DEV int row_swz(int r) {
 // LDS-DMA: a plain global load consumed beside in-flight DMA makes hipcc wait vmcnt(0) and drain
 // the ring (cdna_hip_programming.md §5, "Projection GEMM" item 4(b)).  OCC = waves per SIMD the
 // register allocation must allow: 4 where the LDS footprint lets two blocks share a CU (<= 80 KB).
-template <int BM, int KS, int N1, int N2, int CW, int OCC, bool SW, bool C2 = false>
+template <int BM, int KS, int N1, int N2, int CW, int OCC, bool SW, bool C2 = false, bool Y2 = false>
 __global__ __launch_bounds__(512, OCC) void conv_chain_kernel(const ChainArgs a) {
   constexpr int NW = 8, NT = 512, WM = 4, WN = 2;
   constexpr int WTM = BM / WM, TM = WTM / 16;  // GEMM1 / GEMM2 wave rows
@@ -345,6 +358,12 @@ __global__ __launch_bounds__(512, OCC) void conv_chain_kernel(const ChainArgs a)
   }
   issue(0, 0);
 
+  int yro[Y2 ? Y_ST : 1];  // (Y2) the compact y row of each of this thread's Y_ST store rows
+  if constexpr (Y2) {
+#pragma unroll
+    for (int it = 0; it < Y_ST; ++it) yro[it] = y2_row_off(a, m0 + (tid + it * NT) / CPR, N1);
+  }
+
   f32x4 acc2[TM][TN2];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -459,8 +478,13 @@ __global__ __launch_bounds__(512, OCC) void conv_chain_kernel(const ChainArgs a)
       const int row = q / CPR, c = q % CPR;
       const uint4 v = *reinterpret_cast<const uint4*>(sR + row * (CW * 2) + ((c ^ row_swz<CPR>(row)) << 4));
       const int m = m0 + row;
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), yr,
-                                             m < a.M ? (m * N1 + j * CW + c * 8) * 2 : OOB, 0, 0);
+      int off;
+      if constexpr (Y2) {
+        off = yro[it] >= 0 ? (yro[it] + j * CW + c * 8) * 2 : OOB;
+      } else {
+        off = m < a.M ? (m * N1 + j * CW + c * 8) * 2 : OOB;
+      }
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), yr, off, 0, 0);
     }
 
     // ---- GEMM2: acc2[BM x N2] += y_j . W1_j^T
@@ -621,7 +645,7 @@ MLS_DEV void lds_st2(uint32_t off, bf16 h) {
 //               + (first tile ? min(j, S - 1) * Y_ST : (S - 1) * Y_ST + [j <= S - 2] * T_ST)
 // The DMA splits are strided over the waves (piece q = i * 8 + wave) and a piece type with fewer
 // than 8 pieces is issued by the first waves only, so n_st and n_a1 are per-wave values.
-template <int BM, int KS, int N1, int N2, int CW, int S, int OCC, bool SW, bool PERS>
+template <int BM, int KS, int N1, int N2, int CW, int S, int OCC, bool SW, bool PERS, bool Y2 = false>
 __global__ __launch_bounds__(512, OCC) void conv_chain_ring_kernel(const ChainArgs a, const int ntiles) {
   constexpr int NW = 8, NT = 512, WM = 4, WN = 2;
   constexpr int WTM = BM / WM, TM = WTM / 16;
@@ -780,6 +804,11 @@ __global__ __launch_bounds__(512, OCC) void conv_chain_ring_kernel(const ChainAr
       if (next < ntiles) m0n = next * BM;
     }
     char* const sA1 = smem + abuf * A1_BYTES;
+    int yro[Y2 ? Y_ST : 1];  // (Y2) the compact y row of each of this thread's Y_ST store rows
+    if constexpr (Y2) {
+#pragma unroll
+      for (int it = 0; it < Y_ST; ++it) yro[it] = y2_row_off(a, m0 + (tid + it * NT) / CPR, N1);
+    }
 
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -928,8 +957,13 @@ __global__ __launch_bounds__(512, OCC) void conv_chain_ring_kernel(const ChainAr
         const int row = q / CPR, c = q % CPR;
         const uint4 v = lds_ld16(lds_off(sR + row * (CW * 2) + ((c ^ row_swz<CPR>(row)) << 4)));
         const int m = m0 + row;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), yr,
-                                               m < a.M ? (m * N1 + j * CW + c * 8) * 2 : OOB, 0, 0);
+        int off;
+        if constexpr (Y2) {
+          off = yro[it] >= 0 ? (yro[it] + j * CW + c * 8) * 2 : OOB;
+        } else {
+          off = m < a.M ? (m * N1 + j * CW + c * 8) * 2 : OOB;
+        }
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), yr, off, 0, 0);
       }
 
       // ---- GEMM2: acc2[BM x N2] += y_j . W1_j^T
@@ -1030,7 +1064,7 @@ __global__ __launch_bounds__(512, OCC) void conv_chain_ring_kernel(const ChainAr
 //   layer2.1 -> 2.2, 2.2 -> 2.3                  2   512  128  64 (or 32: 80 KB, two blocks per CU)
 //   layer2.3 -> layer3.0                         2   512  256  32
 //   layer3.1 -> 3.2 ... layer3.4 -> 3.5          4  1024  256  32
-template <int KS, int N1, int N2, int CW, int BM = 128, bool C2 = false>
+template <int KS, int N1, int N2, int CW, int BM = 128, bool C2 = false, bool Y2 = false>
 int launch_chain(const ChainArgs& a, hipStream_t st) {
   constexpr int LDS = BM * KS * 128 + 2 * (CW * KS * 128 + N2 * CW * 2 + BM * CW * 2);
   constexpr int OCC = LDS <= 80 * 1024 ? 4 : 2;
@@ -1039,7 +1073,7 @@ int launch_chain(const ChainArgs& a, hipStream_t st) {
 #else
   constexpr bool SW = KS == 1;
 #endif
-  hipLaunchKernelGGL((conv_chain_kernel<BM, KS, N1, N2, CW, OCC, SW, C2>), dim3((unsigned)((a.M + BM - 1) / BM)),
+  hipLaunchKernelGGL((conv_chain_kernel<BM, KS, N1, N2, CW, OCC, SW, C2, Y2>), dim3((unsigned)((a.M + BM - 1) / BM)),
                      dim3(512), 0, st, a);
   return (int)hipGetLastError();
 }
@@ -1058,7 +1092,7 @@ int g_chain_grid = 0;  // persistent form's block count (0 = one per CU; mls_cha
 // the engine normally runs, but faster alone (36.9 -> 29.0 us and 29.0 -> 27.5 us): they are kept
 // for one-batch-at-a-time serving (bench.py --serial, an engine with inflight = 1), which selects
 // them with MLS_CHAIN_VARIANT=2.
-template <int BM, int KS, int N1, int N2, int CW, int S, bool PERS>
+template <int BM, int KS, int N1, int N2, int CW, int S, bool PERS, bool Y2 = false>
 int launch_ring(const ChainArgs& a, hipStream_t st) {
 #ifdef MLS_CHAIN_SWAP
   constexpr bool SW = MLS_CHAIN_SWAP;
@@ -1074,7 +1108,7 @@ int launch_ring(const ChainArgs& a, hipStream_t st) {
     const int cus = mls_num_cus();
     grid = g_chain_grid > 0 ? g_chain_grid : (ntiles < cus ? ntiles : cus);
   }
-  hipLaunchKernelGGL((conv_chain_ring_kernel<BM, KS, N1, N2, CW, S, OCC, SW, PERS>), dim3((unsigned)grid), dim3(512), 0,
+  hipLaunchKernelGGL((conv_chain_ring_kernel<BM, KS, N1, N2, CW, S, OCC, SW, PERS, Y2>), dim3((unsigned)grid), dim3(512), 0,
                      st, a, ntiles);
   return (int)hipGetLastError();
 }
@@ -1089,21 +1123,24 @@ constexpr bool RING_L1_DUAL = false, RING_L2 = true, RING_L2_OUT = false;
 
 bool use_ring(bool shape_default) { return g_chain_variant == 2 || (g_chain_variant == 0 && shape_default); }
 
-}  // namespace
+// bytes of y: [M][N1], or with y2 (the Y2 store, even Ho and Wo) [B][Ho / 2][Wo / 2][N1]
+long y_size(int B, int Ho, int Wo, int N1, bool y2) {
+  return y2 ? (long)B * (Ho / 2) * (Wo / 2) * N1 * 2 : (long)B * Ho * Wo * N1 * 2;
+}
 
-extern "C" {
-
+// mls_conv_chain (y2 = false) and mls_conv_chain_y2 (y2 = true: the Y2 store, below):
 // y = relu(conv1x1([a1 | a2 strided]) + b3 (+ res)); t1 = relu(conv1x1(y, w1) + b1).
 // a1 [M][Ka] (M = B*Ho*Wo), a2 [B][H2][W2][Kb] sampled at stride2 (Kb = 0: none), w3 [N1][Ka+Kb],
 // res [M][N1] or null, w1 [N2][N1]; y [M][N1], t1 [M][N2].  (KS = (Ka + Kb) / 64, N1, N2) one of
 // (1, 256, 64), (2, 256, 64), (1, 256, 128), (2, 512, 128), (2, 512, 256), (4, 1024, 256);
 // anything else MLS_UNSUPPORTED.
-int mls_conv_chain(const void* a1, const void* a2, const void* w3, const float* b3, const void* res, void* y,
-                   const void* w1, const float* b1, void* t1, int B, int Ho, int Wo, int Ka, int H2, int W2, int Kb,
-                   int stride2, int N1, int N2, void* stream) {
+int chain_impl(const void* a1, const void* a2, const void* w3, const float* b3, const void* res, void* y,
+               const void* w1, const float* b1, void* t1, int B, int Ho, int Wo, int Ka, int H2, int W2, int Kb,
+               int stride2, int N1, int N2, bool y2, void* stream) {
   if (B <= 0 || Ho <= 0 || Wo <= 0 || Ka <= 0 || Ka % 64 || Kb < 0 || Kb % 64 || N1 <= 0 || N1 % 64 || N2 <= 0)
     return MLS_BAD_ARG;
   if (Kb > 0 && (stride2 < 1 || (Ho - 1) * stride2 >= H2 || (Wo - 1) * stride2 >= W2 || res)) return MLS_BAD_ARG;
+  if (y2 && (Ho % 2 || Wo % 2)) return MLS_UNSUPPORTED;
   ChainArgs a{};
   a.a1 = (const bf16*)a1;
   a.a2 = (const bf16*)a2;
@@ -1124,7 +1161,7 @@ int mls_conv_chain(const void* a1, const void* a2, const void* w3, const float* 
   a.fd_wo = fastdiv_make((uint32_t)Wo);
   const long M = a.M;
   const long sizes[7] = {M * Ka * 2, (long)B * H2 * W2 * Kb * 2, (long)N1 * (Ka + Kb) * 2, res ? M * N1 * 2 : 0,
-                         M * N1 * 2, (long)N2 * N1 * 2, M * N2 * 2};
+                         y_size(B, Ho, Wo, N1, y2), (long)N2 * N1 * 2, M * N2 * 2};
   for (long s : sizes)
     if (s >= 0x7fffffffL) return MLS_UNSUPPORTED;
   a.a1_bytes = (uint32_t)sizes[0];
@@ -1136,6 +1173,13 @@ int mls_conv_chain(const void* a1, const void* a2, const void* w3, const float* 
   a.t1_bytes = (uint32_t)sizes[6];
   const hipStream_t st = (hipStream_t)stream;
   const int ks = (Ka + Kb) / 64;
+  if (y2) {  // the stride-2 stage boundaries; the layer2 A/B overrides do not apply
+    if (ks == 1 && N1 == 256 && N2 == 128) return launch_chain<1, 256, 128, 64, 128, false, true>(a, st);
+    if (ks == 2 && N1 == 512 && N2 == 256)
+      return use_ring(RING_L2_OUT) ? launch_ring<128, 2, 512, 256, 32, 3, false, true>(a, st)
+                                   : launch_chain<2, 512, 256, 32, 128, false, true>(a, st);
+    return MLS_UNSUPPORTED;
+  }
   if (ks == 1 && N1 == 256 && N2 == 64) return launch_chain<1, 256, 64, 64>(a, st);
   if (ks == 2 && N1 == 256 && N2 == 64)
     return use_ring(RING_L1_DUAL) ? launch_ring<64, 2, 256, 64, 64, 2, true>(a, st)
@@ -1156,19 +1200,21 @@ int mls_conv_chain(const void* a1, const void* a2, const void* w3, const float* 
   return MLS_UNSUPPORTED;
 }
 
-// mls_conv_chain with the bottleneck's conv2 in the same kernel:
+// mls_conv_chain_conv2 / mls_conv_chain_conv2_y2: mls_conv_chain with the bottleneck's conv2 in the
+// same kernel:
 //   t2 = relu(conv3x3(t1_in, w2) + b2)   (stride 1, pad 1; never written to memory)
 //   y  = relu(conv1x1([t2 | a2 strided]) + b3 (+ res)); t1 = relu(conv1x1(y, w1) + b1).
 // t1_in [B][H][W][64], w2 [64][3][3][64] (the packed conv weight), b2 [64] or null; the rest as
 // mls_conv_chain with a1 = t2 (Ka = 64, Ho = H, Wo = W).  (KS, N1, N2) one of the layer1 boundaries
 // (1, 256, 64), (2, 256, 64), (1, 256, 128) and W <= 63 (the tile's pixel strip with its halo of
 // W + 1 on both sides is staged as 256 LDS rows); anything else MLS_UNSUPPORTED.
-int mls_conv_chain_conv2(const void* t1_in, const void* w2, const float* b2, const void* a2, const void* w3,
-                         const float* b3, const void* res, void* y, const void* w1, const float* b1, void* t1, int B,
-                         int H, int W, int Ka, int H2, int W2, int Kb, int stride2, int N1, int N2, void* stream) {
+int chain_conv2_impl(const void* t1_in, const void* w2, const float* b2, const void* a2, const void* w3,
+                     const float* b3, const void* res, void* y, const void* w1, const float* b1, void* t1, int B, int H,
+                     int W, int Ka, int H2, int W2, int Kb, int stride2, int N1, int N2, bool y2, void* stream) {
   if (B <= 0 || H <= 0 || W <= 0 || Ka <= 0 || Kb < 0 || Kb % 64 || N1 <= 0 || N1 % 64 || N2 <= 0) return MLS_BAD_ARG;
   if (Kb > 0 && (stride2 < 1 || (H - 1) * stride2 >= H2 || (W - 1) * stride2 >= W2 || res)) return MLS_BAD_ARG;
   if (Ka != 64 || 2 * (W + 1) + 128 > 256) return MLS_UNSUPPORTED;
+  if (y2 && (H % 2 || W % 2)) return MLS_UNSUPPORTED;
   ChainArgs a{};
   a.t1in = (const bf16*)t1_in;
   a.w2 = (const bf16*)w2;
@@ -1190,7 +1236,7 @@ int mls_conv_chain_conv2(const void* t1_in, const void* w2, const float* b2, con
   a.fd_wo = fastdiv_make((uint32_t)W);
   const long M = (long)B * H * W;
   const long sizes[7] = {M * Ka * 2, (long)B * H2 * W2 * Kb * 2, (long)N1 * (Ka + Kb) * 2, res ? M * N1 * 2 : 0,
-                         M * N1 * 2, (long)N2 * N1 * 2, M * N2 * 2};
+                         y_size(B, H, W, N1, y2), (long)N2 * N1 * 2, M * N2 * 2};
   for (long s : sizes)
     if (s >= 0x7fffffffL) return MLS_UNSUPPORTED;
   a.M = (int)M;
@@ -1204,10 +1250,47 @@ int mls_conv_chain_conv2(const void* t1_in, const void* w2, const float* b2, con
   a.w2_bytes = 64 * 9 * 64 * 2;
   const hipStream_t st = (hipStream_t)stream;
   const int ks = (Ka + Kb) / 64;
+  if (y2) return ks == 1 && N1 == 256 && N2 == 128 ? launch_chain<1, 256, 128, 64, 128, true, true>(a, st) : MLS_UNSUPPORTED;
   if (ks == 1 && N1 == 256 && N2 == 64) return launch_chain<1, 256, 64, 64, 128, true>(a, st);
   if (ks == 2 && N1 == 256 && N2 == 64) return launch_chain<2, 256, 64, 64, 128, true>(a, st);
   if (ks == 1 && N1 == 256 && N2 == 128) return launch_chain<1, 256, 128, 64, 128, true>(a, st);
   return MLS_UNSUPPORTED;
+}
+
+}  // namespace
+
+extern "C" {
+
+// chain_impl / chain_conv2_impl above, y stored in full
+int mls_conv_chain(const void* a1, const void* a2, const void* w3, const float* b3, const void* res, void* y,
+                   const void* w1, const float* b1, void* t1, int B, int Ho, int Wo, int Ka, int H2, int W2, int Kb,
+                   int stride2, int N1, int N2, void* stream) {
+  return chain_impl(a1, a2, w3, b3, res, y, w1, b1, t1, B, Ho, Wo, Ka, H2, W2, Kb, stride2, N1, N2, false, stream);
+}
+
+int mls_conv_chain_conv2(const void* t1_in, const void* w2, const float* b2, const void* a2, const void* w3,
+                         const float* b3, const void* res, void* y, const void* w1, const float* b1, void* t1, int B,
+                         int H, int W, int Ka, int H2, int W2, int Kb, int stride2, int N1, int N2, void* stream) {
+  return chain_conv2_impl(t1_in, w2, b2, a2, w3, b3, res, y, w1, b1, t1, B, H, W, Ka, H2, W2, Kb, stride2, N1, N2,
+                          false, stream);
+}
+
+// The same two with the Y2 store: y is [B][Ho / 2][Wo / 2][N1], the pixels (2i, 2j) of the block
+// output -- all that a stride-2 downsample projection reads of it.  t1 is unchanged.  Ho and Wo
+// even and (KS, N1, N2) one of the stride-2 stage boundaries, (1, 256, 128) (both entry points) and
+// (2, 512, 256) (mls_conv_chain_y2); anything else MLS_UNSUPPORTED, nothing launched.
+int mls_conv_chain_y2(const void* a1, const void* a2, const void* w3, const float* b3, const void* res, void* y,
+                      const void* w1, const float* b1, void* t1, int B, int Ho, int Wo, int Ka, int H2, int W2, int Kb,
+                      int stride2, int N1, int N2, void* stream) {
+  return chain_impl(a1, a2, w3, b3, res, y, w1, b1, t1, B, Ho, Wo, Ka, H2, W2, Kb, stride2, N1, N2, true, stream);
+}
+
+int mls_conv_chain_conv2_y2(const void* t1_in, const void* w2, const float* b2, const void* a2, const void* w3,
+                            const float* b3, const void* res, void* y, const void* w1, const float* b1, void* t1,
+                            int B, int H, int W, int Ka, int H2, int W2, int Kb, int stride2, int N1, int N2,
+                            void* stream) {
+  return chain_conv2_impl(t1_in, w2, b2, a2, w3, b3, res, y, w1, b1, t1, B, H, W, Ka, H2, W2, Kb, stride2, N1, N2,
+                          true, stream);
 }
 
 // A/B switch for the layer2 boundaries' chunk width (64 = 128 KB of LDS, one block per CU; 32 =

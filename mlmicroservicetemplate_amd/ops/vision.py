@@ -145,6 +145,26 @@ def conv1x1_dual(y: torch.Tensor, x: torch.Tensor, w_cat: torch.Tensor, bias: Op
 CHAIN_SHAPES = ((64, 256, 64), (128, 256, 64), (64, 256, 128), (128, 512, 128), (128, 512, 256), (256, 1024, 256))
 
 
+# (K of the conv3 GEMM, N1, N2) with a ``y_stride2`` form: the boundaries in front of a stride-2 stage
+CHAIN_Y_STRIDE2_SHAPES = ((64, 256, 128), (128, 512, 256))
+# (Kb, N1, N2) of the conv2-fused chain with one
+CHAIN_CONV2_Y_STRIDE2_SHAPES = ((0, 256, 128),)
+
+
+def _chain_y(B: int, Ho: int, Wo: int, N1: int, y_stride2: bool, supported: bool, y_out, dev, what: str):
+    """The chain ops' ``y``: ``[B,Ho,Wo,N1]``, or with ``y_stride2`` ``[B,Ho/2,Wo/2,N1]``."""
+    if y_stride2 and (not supported or Ho % 2 or Wo % 2):
+        raise ValueError(f"{what}: y_stride2 needs even Ho, Wo and a stride-2 stage boundary shape")
+    shape = (B, Ho // 2, Wo // 2, N1) if y_stride2 else (B, Ho, Wo, N1)
+    if y_out is None:
+        return torch.empty(shape, device=dev, dtype=torch.bfloat16)
+    if y_stride2:  # the kernel's range check is sized by this shape
+        _need(y_out, "y_out", torch.bfloat16, dev)
+        if tuple(y_out.shape) != shape:
+            raise ValueError(f"{what}: y_out must be {shape}")
+    return y_out
+
+
 def set_chain_l2_cw(cw: int) -> None:
     """A/B: output-channel chunk width of the layer2 chain boundaries (64 default, or 32)."""
     lib().mls_chain_set_l2_cw(int(cw))
@@ -153,13 +173,16 @@ def set_chain_l2_cw(cw: int) -> None:
 def conv1x1_chain(a1: torch.Tensor, w3: torch.Tensor, b3: Optional[torch.Tensor], w1: torch.Tensor,
                   b1: Optional[torch.Tensor], *, residual: Optional[torch.Tensor] = None,
                   a2: Optional[torch.Tensor] = None, stride2: int = 1,
-                  y_out: Optional[torch.Tensor] = None, t1_out: Optional[torch.Tensor] = None):
+                  y_out: Optional[torch.Tensor] = None, t1_out: Optional[torch.Tensor] = None,
+                  y_stride2: bool = False):
     """One bottleneck boundary in one kernel (csrc/conv_chain.hip):
     ``y = relu(conv1x1([a1 | a2 at stride2], w3) + b3 (+ residual))`` and
     ``t1 = relu(conv1x1(y, w1) + b1)``; y never makes an HBM round trip.  Returns ``(y, t1)``.
     ``w3`` is ``[N1][Ka (+ Kb)]`` (the dual concatenation when ``a2`` is given; no residual then),
     ``w1`` ``[N2][N1]``.  Supported (Ka + Kb, N1, N2): CHAIN_SHAPES -- the ResNet-50 layer1,
-    layer2 and layer3 boundaries."""
+    layer2 and layer3 boundaries.  ``y_stride2``: store and return only ``y[:, ::2, ::2, :]``
+    (contiguous ``[B,Ho/2,Wo/2,N1]``), all that a stride-2 downsample projection reads of it;
+    CHAIN_Y_STRIDE2_SHAPES with even Ho and Wo, anything else raises before a launch."""
     dev = a1.device
     _need(a1, "a1", torch.bfloat16, dev)
     _need(w3, "w3", torch.bfloat16, dev)
@@ -188,11 +211,11 @@ def conv1x1_chain(a1: torch.Tensor, w3: torch.Tensor, b3: Optional[torch.Tensor]
         _need(residual, "residual", torch.bfloat16, dev)
         if tuple(residual.shape) != (B, Ho, Wo, N1):
             raise ValueError("residual shape mismatch")
-    y = torch.empty(B, Ho, Wo, N1, device=dev, dtype=torch.bfloat16) if y_out is None else y_out
+    y = _chain_y(B, Ho, Wo, N1, y_stride2, (Ka + Kb, N1, N2) in CHAIN_Y_STRIDE2_SHAPES, y_out, dev, "conv1x1_chain")
     t1 = torch.empty(B, Ho, Wo, N2, device=dev, dtype=torch.bfloat16) if t1_out is None else t1_out
-    rc = lib().mls_conv_chain(a1.data_ptr(), _ptr(a2), w3.data_ptr(), _ptr(b3), _ptr(residual), y.data_ptr(),
-                              w1.data_ptr(), _ptr(b1), t1.data_ptr(), B, Ho, Wo, Ka, H2, W2, Kb, stride2, N1, N2,
-                              stream_ptr(dev))
+    fn = lib().mls_conv_chain_y2 if y_stride2 else lib().mls_conv_chain
+    rc = fn(a1.data_ptr(), _ptr(a2), w3.data_ptr(), _ptr(b3), _ptr(residual), y.data_ptr(), w1.data_ptr(), _ptr(b1),
+            t1.data_ptr(), B, Ho, Wo, Ka, H2, W2, Kb, stride2, N1, N2, stream_ptr(dev))
     check(rc, "mls_conv_chain")
     return y, t1
 
@@ -205,13 +228,15 @@ CHAIN_CONV2_MAX_W = 63  # the tile's pixel strip with its halo (128 + 2 * (W + 1
 def conv3x3_chain(t1_in: torch.Tensor, w2: torch.Tensor, b2: Optional[torch.Tensor], w3: torch.Tensor,
                   b3: Optional[torch.Tensor], w1: torch.Tensor, b1: Optional[torch.Tensor], *,
                   residual: Optional[torch.Tensor] = None, a2: Optional[torch.Tensor] = None, stride2: int = 1,
-                  y_out: Optional[torch.Tensor] = None, t1_out: Optional[torch.Tensor] = None):
+                  y_out: Optional[torch.Tensor] = None, t1_out: Optional[torch.Tensor] = None,
+                  y_stride2: bool = False):
     """A bottleneck's 3x3 conv2, its conv3 (+ residual / + downsample) and the next block's conv1 in
     one kernel (csrc/conv_chain.hip, the C2 form):
     ``t2 = relu(conv3x3(t1_in, w2) + b2)`` (stride 1, pad 1; rounded to bf16, never written to HBM),
     then ``conv1x1_chain(t2, w3, b3, w1, b1, ...)``.  Returns ``(y, t1)``.
     ``t1_in`` is ``[B,H,W,64]``, ``w2`` the packed ``[64,3,3,64]`` weight.  Supported
-    (Kb, N1, N2): CHAIN_CONV2_SHAPES with W <= CHAIN_CONV2_MAX_W -- the ResNet-50 layer1 boundaries."""
+    (Kb, N1, N2): CHAIN_CONV2_SHAPES with W <= CHAIN_CONV2_MAX_W -- the ResNet-50 layer1 boundaries.
+    ``y_stride2`` as in :func:`conv1x1_chain` (CHAIN_CONV2_Y_STRIDE2_SHAPES)."""
     dev = t1_in.device
     for name, t in (("t1_in", t1_in), ("w2", w2), ("w3", w3), ("w1", w1)):
         _need(t, name, torch.bfloat16, dev)
@@ -242,11 +267,11 @@ def conv3x3_chain(t1_in: torch.Tensor, w2: torch.Tensor, b2: Optional[torch.Tens
         _need(residual, "residual", torch.bfloat16, dev)
         if tuple(residual.shape) != (B, H, W, N1):
             raise ValueError("residual shape mismatch")
-    y = torch.empty(B, H, W, N1, device=dev, dtype=torch.bfloat16) if y_out is None else y_out
+    y = _chain_y(B, H, W, N1, y_stride2, (Kb, N1, N2) in CHAIN_CONV2_Y_STRIDE2_SHAPES, y_out, dev, "conv3x3_chain")
     t1 = torch.empty(B, H, W, N2, device=dev, dtype=torch.bfloat16) if t1_out is None else t1_out
-    rc = lib().mls_conv_chain_conv2(t1_in.data_ptr(), w2.data_ptr(), _ptr(b2), _ptr(a2), w3.data_ptr(), _ptr(b3),
-                                    _ptr(residual), y.data_ptr(), w1.data_ptr(), _ptr(b1), t1.data_ptr(), B, H, W,
-                                    Ka, H2, W2, Kb, stride2, N1, N2, stream_ptr(dev))
+    fn = lib().mls_conv_chain_conv2_y2 if y_stride2 else lib().mls_conv_chain_conv2
+    rc = fn(t1_in.data_ptr(), w2.data_ptr(), _ptr(b2), _ptr(a2), w3.data_ptr(), _ptr(b3), _ptr(residual), y.data_ptr(),
+            w1.data_ptr(), _ptr(b1), t1.data_ptr(), B, H, W, Ka, H2, W2, Kb, stride2, N1, N2, stream_ptr(dev))
     check(rc, "mls_conv_chain_conv2")
     return y, t1
 
