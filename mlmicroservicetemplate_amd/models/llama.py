@@ -35,6 +35,7 @@ import torch.nn.functional as F
 
 from ..ops import reference as R
 from ..utils import tracing
+from .llama_route import ProjTiers, StepRoute, proj_tiers, step_route
 
 # int32 words of the serving loop's control row (op, admissions, longest prompt, iteration check):
 # rank 0's next-iteration header, carried by the decode step's X4 gather (serve_graph)
@@ -418,6 +419,36 @@ class TPCommError(RuntimeError):
     tokens of the affected generation are not trustworthy and the request fails."""
 
 
+@dataclass
+class _Forward:
+    """What the pieces of one fused forward share: the step's route and inputs, and the residual
+    stream as the layers advance it."""
+
+    rt: StepRoute
+    B: int
+    S: int
+    decode: bool
+    pos: torch.Tensor  # [B * S] positions (clamped to the RoPE table)
+    lens: torch.Tensor
+    past: Optional[torch.Tensor]
+    slots: Optional[torch.Tensor]  # prefill: explicit cache slot of every row (ops.prefill_slots)
+    r: torch.Tensor  # residual stream (bf16)
+    delta: Optional[torch.Tensor] = None  # the last row-parallel output, not yet added to r
+    xn: Optional[torch.Tensor] = None  # RMSNorm(r) staged by _proj_add_norm for the next projection
+    attn_kw: Optional[dict] = None  # LlamaTP._attention_kw
+    # the layer tail's o-projection and gate_up outputs, held until the next layer's replace them: the
+    # caching allocator then hands the next layer's temporaries other blocks than these, as it did when
+    # the forward was one function whose locals lived that long.  Freed on return from the tail instead,
+    # the captured batch-8 decode step measured 8 us (0.25 %) slower (docs/PERF_NOTES.md, "LlamaTP routing
+    # refactor"; profiles/llama_route_keepalive_ab.jsonl)
+    o: Optional[torch.Tensor] = None
+    gu: Optional[torch.Tensor] = None
+
+    def take_xn(self) -> Optional[torch.Tensor]:
+        xn, self.xn = self.xn, None
+        return xn
+
+
 class LlamaTP:
     """One rank of a tensor-parallel Llama with a KV cache ``[layers][max_batch, max_seq, hkv, D]``
     (or, paged, ``[layers][pages, 64, hkv, D]`` pools addressed through a page table)."""
@@ -451,8 +482,7 @@ class LlamaTP:
         self.sd = shard_dims(cfg, tp, rank)
         self.tp, self.rank = tp, rank
         self.comm = comm or TPComm(None, tp)
-        # TP prefill: two batch halves interleaved so each o / down all-reduce overlaps the other
-        # half's compute (_prefill_overlapped); MLS_TP_OVERLAP=0 runs the plain layer loop
+        # TP prefill as two interleaved batch halves (_prefill_overlapped); MLS_TP_OVERLAP=0: the plain layer loop
         self.tp_overlap = os.environ.get("MLS_TP_OVERLAP", "1") == "1"
         self.backend = backend
         self.device = torch.device(device)
@@ -464,134 +494,37 @@ class LlamaTP:
         self.w4: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
         self.w4_max_rows = self.w4_variant = 0
         if weight_dtype == "int4":
-            for i in range(cfg.layers):
-                for n in ("qkv", "o", "gate", "up", "down"):
-                    N_, K_ = self.p[f"l{i}.{n}"].shape
-                    if K_ % R.W4_GROUP or (backend == "fused" and N_ % (8 if n in ("gate", "up") else 16)):
-                        raise ValueError(f"weight_dtype='int4': l{i}.{n} is [{N_}, {K_}] on this rank (tp {tp}); "
-                                         f"needs K % {R.W4_GROUP} == 0" + (", N % 16 == 0" if backend == "fused" else ""))
-        if weight_dtype == "int4" and backend != "fused":
-            # the CPU oracle: gains folded as ops.fold_norm (fp32 product, one bf16 rounding), then the
-            # exact dequantised product as the weights; the folded norms become ones
-            for i in range(cfg.layers):
-                for n, gain in (("qkv", "attn_norm"), ("gate", "mlp_norm"), ("up", "mlp_norm"), ("o", None), ("down", None)):
-                    w = self.p[f"l{i}.{n}"]
-                    if gain is not None:
-                        w = (w.float() * self.p[f"l{i}.{gain}"].float().view(1, -1)).to(w.dtype)
-                    self.p[f"l{i}.{n}"] = R.w4_dequant(*R.w4_quant(w))
-                for gain in ("attn_norm", "mlp_norm"):
-                    self.p[f"l{i}.{gain}"] = torch.ones_like(self.p[f"l{i}.{gain}"])
+            self._check_int4_shapes()
+            if backend != "fused":
+                self._quantise_reference()
+        # the fused forward's switches and copies of the weights (name -> tensors), set on both backends
+        # so that whatever reads them needs no default; models/llama_route.py holds the rules they feed
+        self.packed: Dict[str, torch.Tensor] = {}  # granule-packed bf16 copies (_pack_decode_copies)
+        self.fp8: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}  # W8A8 e4m3 copies + scales
+        self.pk_variant = int(os.environ.get("MLS_PACKED_VARIANT", "9"))
+        self.pk_fold = os.environ.get("MLS_PACKED_FOLD", "1") == "1"  # residual adds in the o / down epilogues
+        self.prefill_fold = os.environ.get("MLS_PREFILL_FOLD", "0") == "1"  # ... in prefill at TP = 1 too
+        self.ar_fuse = os.environ.get("MLS_AR_FUSE", "1") == "1"  # GEMM-fused TP all-reduce (decode)
+        self.ar_fused_calls = 0  # projections issued with the fused all-reduce (eager + captured)
+        self.fuse_combine = os.environ.get("MLS_FUSE_COMBINE", "1") == "1"  # split-KV combine in the o prologue
+        self.fuse_add_norm = True  # o / down through ops.linear_add_rmsnorm above 24 rows at TP = 1
+        self.add_norm_fused = 0  # projections that took it
+        self.dec_chunk = int(os.environ.get("MLS_DEC_CHUNK", "0"))  # decode split rows; 0: auto (llama_route)
+        self.verify_attn = os.environ.get("MLS_VERIFY_ATTN", "multi")  # "ctx": verify through flash_attention_ctx
         if backend == "fused":
             from .. import ops
 
             self.ops = ops
-            # RMSNorm gains folded into the projections that consume the normalised activations
-            for i in range(cfg.layers):
-                gu = ops.interleave_gate_up(self.p.pop(f"l{i}.gate"), self.p.pop(f"l{i}.up"))
-                mlp_g = self.p.pop(f"l{i}.mlp_norm")
-                self.p[f"l{i}.gate_up"] = ops.fold_norm(gu, mlp_g)
-                self.p[f"l{i}.qkv"] = ops.fold_norm(self.p[f"l{i}.qkv"], self.p.pop(f"l{i}.attn_norm"))
-            self.p["lm_head"] = ops.fold_norm(self.p["lm_head"], self.p.pop("final_norm"))
-            if weight_dtype == "int4":
-                # quantised as held here (gain folded, gate / up interleaved: a row permutation).  p
-                # keeps the bf16 rounding of the dequantised matrix for the > w4_max_rows GEMMs
-                # (prefill, chunked prefill), w4 the packed codes the decode steps stream; no
-                # granule-packed bf16 copy of these names below
-                for i in range(cfg.layers):
-                    for n in ("qkv", "o", "gate_up", "down"):
-                        q, sc = R.w4_quant(self.p[f"l{i}.{n}"])
-                        self.p[f"l{i}.{n}"] = R.w4_dequant(q, sc).to(torch.bfloat16)
-                        self.w4[f"l{i}.{n}"] = ops.pack_skinny_w4_codes(q, sc)
-                        del q, sc
-                # decode steps up to this many rows stream the int4 codes: the kernel's own limit, it was
-                # ahead of the bf16 routes at every row count measured, 1 to 32 (Llama-3-8B, batch 32:
-                # 4.13 vs 4.50 ms/step; profiles/w4_decode_ab.jsonl, docs/PERF_NOTES.md "W4A16 decode")
-                self.w4_max_rows = min(32, int(os.environ.get("MLS_W4_MAX_ROWS", "32")))
-                self.w4_variant = int(os.environ.get("MLS_W4_VARIANT", "0"))  # probe knob: the launch shape
-            # Decode (<= 24 tokens per step) streams a second, granule-packed copy of every projection
-            # (ops.pack_skinny: each wave reads contiguous 1 KiB granules, non-temporal): 3.4-4.5 ->
-            # 4.6-6.2 TB/s on the Llama-3-8B shapes (profiles/r2_decode_packed_weight_probe.jsonl).
-            # Costs one more copy of the weights in HBM (16 GB at 8B / TP = 1 of 288 GB);
-            # MLS_PACKED_DECODE=0 turns it off, "auto" packs while the copy stays under 1/4 of the card.
-            self.packed: Dict[str, torch.Tensor] = {}
-            self.pk_variant = int(os.environ.get("MLS_PACKED_VARIANT", "9"))
-            self.pk_fold = os.environ.get("MLS_PACKED_FOLD", "1") == "1"
-            # prefill at TP = 1 with the residual add in the o / down GEMM epilogues too (the
-            # following RMSNorm then reads one stream and writes one: 64 instead of 128 B per element)
-            self.prefill_fold = os.environ.get("MLS_PREFILL_FOLD", "0") == "1"
-            self.ar_fuse = os.environ.get("MLS_AR_FUSE", "1") == "1"  # GEMM-fused TP all-reduce (decode)
-            self.ar_fused_calls = 0  # projections issued with the fused all-reduce (eager + captured)
-            self.fuse_combine = os.environ.get("MLS_FUSE_COMBINE", "1") == "1"
-            mode = os.environ.get("MLS_PACKED_DECODE", "auto")
-            if self.device.type == "cuda" and mode != "0":
-                names = [f"l{i}.{n}" for i in range(cfg.layers) for n in ("qkv", "o", "gate_up", "down")]
-                names.append("lm_head")
-                names = [n for n in names if self.p[n].shape[0] % 16 == 0 and self.p[n].shape[1] % 32 == 0
-                         and self.p[n].numel() * 2 < (1 << 31) and n not in self.w4]
-                total = sum(self.p[n].numel() * 2 for n in names)
-                cap = torch.cuda.get_device_properties(self.device).total_memory
-                if mode == "1" or total <= cap // 4:
-                    self.packed = {n: ops.pack_skinny(self.p[n]) for n in names}
-            # Opt-in FP8 decode (MLS_DECODE_FP8=1): W8A8 e4m3 copies of the projections, per-channel
-            # weight scales and per-row activation scales (ops.skinny_fp8), for <= 4 tokens per step --
-            # half the weight stream (profiles/r2_decode_fp8_weight_probe.jsonl).  Changes numerics
-            # (e4m3 has a 3-bit mantissa), so bf16 stays the default.
-            self.fp8: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
-            if self.device.type == "cuda" and os.environ.get("MLS_DECODE_FP8", "0") == "1":
-                names = [f"l{i}.{n}" for i in range(cfg.layers) for n in ("qkv", "o", "gate_up", "down")]
-                names.append("lm_head")
-                # only matrices of >= 16M weights: below that a decode GEMM is latency-bound and the
-                # fp8 prologue (row |max| reduction + requantisation) costs more than the bytes saved
-                # -- one emulated TP = 8 rank was 1.13 -> 1.18 ms/token with every projection in fp8
-                min_el = int(os.environ.get("MLS_DECODE_FP8_MIN", str(1 << 24)))
-                self.fp8 = {n: ops.pack_skinny_fp8(self.p[n]) for n in names
-                            if self.p[n].shape[0] % 16 == 0 and self.p[n].shape[1] % 64 == 0
-                            and min_el <= self.p[n].numel() < (1 << 31) and n not in self.w4}  # int4 wins
+            self._fold_and_quantise(weight_dtype)
+            self._pack_decode_copies()
             self.ones = torch.ones(cfg.hidden, device=self.device, dtype=torch.bfloat16)
             self.workspace = torch.empty(32 << 20, device=self.device, dtype=torch.float32)
-            self.dec_chunk = int(os.environ.get("MLS_DEC_CHUNK", "0"))  # 0: auto (see _fused_forward)
             self.dec_ws = torch.empty(max_batch * self.sd.hq * (-(-max_seq // 64)) * (D + 2) + 16,
                                       device=self.device, dtype=torch.float32)
             self.dec_cnt = torch.zeros(max_batch * self.sd.hkv, device=self.device, dtype=torch.int32)
             self.ver_ws: Optional[torch.Tensor] = None  # split-KV partials of the uncaptured verify steps
             self._ver_ws_graph: Optional[torch.Tensor] = None  # ... of the verify graph being warmed up / captured
-            self.verify_attn = os.environ.get("MLS_VERIFY_ATTN", "multi")  # "ctx": verify through flash_attention_ctx
-        cdt = torch.bfloat16 if backend == "fused" else torch.float32
-        # fused: head-major caches ([.., Hkv, rows, D]) -- one head's rows contiguous, so a decode split
-        # block streams one 16 KiB run instead of 64 slices of 256 B (MLS_KV_HEAD_MAJOR=0: row-major)
-        self.kv_hm = backend == "fused" and os.environ.get("MLS_KV_HEAD_MAJOR", "1") == "1"
-        self.pages = None
-        if kv_pages > 0:
-            from .kv_pages import PageTable
-
-            self.page_rows = 64  # = the decode split: one page per split block
-            self.pages = PageTable(kv_pages, self.page_rows, max_batch, -(-max_seq // self.page_rows), self.device)
-            shape = ((kv_pages, self.sd.hkv, self.page_rows, D) if self.kv_hm
-                     else (kv_pages, self.page_rows, self.sd.hkv, D))
-        else:
-            shape = (max_batch, self.sd.hkv, max_seq, D) if self.kv_hm else (max_batch, max_seq, self.sd.hkv, D)
-        self.kv_hm_rows = 0 if not self.kv_hm else (self.page_rows if kv_pages > 0 else max_seq)
-        self.kv_fp8 = backend == "fused" and kv_dtype == "fp8"
-        self.k_scale: List[torch.Tensor] = []
-        self.v_scale: List[torch.Tensor] = []
-        if self.kv_fp8:
-            # the matrix-core decode kernel's own limits; no fallback to bf16 rows
-            G = self.sd.hq // max(self.sd.hkv, 1)
-            bad = [why for ok, why in (
-                (self.kv_hm, "the head-major cache layout (MLS_KV_HEAD_MAJOR=0 is set)"),
-                (D == 128, f"head_dim 128 (got {D})"),
-                (self.sd.hq % self.sd.hkv == 0 and G in (1, 2, 4, 8),
-                 f"Hq / Hkv in 1, 2, 4, 8 (got {self.sd.hq} / {self.sd.hkv})"),
-                (self.dec_chunk in (0, 64, 128), f"decode splits of 64 or 128 rows (MLS_DEC_CHUNK={self.dec_chunk})"),
-                (kv_pages > 0 or max_seq % 4 == 0, f"max_seq a multiple of 4 (got {max_seq})"),
-            ) if not ok]
-            if bad:
-                raise ValueError("kv_dtype='fp8' on the fused backend needs " + "; ".join(bad))
-            cdt = torch.uint8
-            self.k_scale = [torch.zeros(shape[:3], device=self.device, dtype=torch.float32) for _ in range(cfg.layers)]
-            self.v_scale = [torch.zeros_like(self.k_scale[0]) for _ in range(cfg.layers)]
-        self.k_cache = [torch.zeros(shape, device=self.device, dtype=cdt) for _ in range(cfg.layers)]
-        self.v_cache = [torch.zeros_like(self.k_cache[0]) for _ in range(cfg.layers)]
+        self._alloc_kv_cache(kv_pages)
         self.cos, self.sin = R.rope_tables(max_seq, D, cfg.rope_theta, self.device)
         # hipGraph capture of the decode step (P4): removes ~300 host launches per token.  With
         # tp > 1 the step's collectives are captured too: the one-shot IPC all-reduce is graph-safe
@@ -621,6 +554,129 @@ class LlamaTP:
         self.keep_logits = False
         self.last_logits: Optional[torch.Tensor] = None
         self.health_every = int(os.environ.get("MLS_TP_HEALTH_EVERY", "32"))
+
+    def _check_int4_shapes(self) -> None:
+        cfg, fused = self.cfg, self.backend == "fused"
+        for i in range(cfg.layers):
+            for n in ("qkv", "o", "gate", "up", "down"):
+                N_, K_ = self.p[f"l{i}.{n}"].shape
+                if K_ % R.W4_GROUP or (fused and N_ % (8 if n in ("gate", "up") else 16)):
+                    raise ValueError(f"weight_dtype='int4': l{i}.{n} is [{N_}, {K_}] on this rank (tp {self.tp}); "
+                                     f"needs K % {R.W4_GROUP} == 0" + (", N % 16 == 0" if fused else ""))
+
+    def _quantise_reference(self) -> None:
+        """``weight_dtype="int4"`` on the reference backend, the CPU oracle: gains folded as ops.fold_norm
+        (fp32 product, one bf16 rounding), then the exact dequantised product as the weights; the folded
+        norms become ones."""
+        for i in range(self.cfg.layers):
+            for n, gain in (("qkv", "attn_norm"), ("gate", "mlp_norm"), ("up", "mlp_norm"), ("o", None), ("down", None)):
+                w = self.p[f"l{i}.{n}"]
+                if gain is not None:
+                    w = (w.float() * self.p[f"l{i}.{gain}"].float().view(1, -1)).to(w.dtype)
+                self.p[f"l{i}.{n}"] = R.w4_dequant(*R.w4_quant(w))
+            for gain in ("attn_norm", "mlp_norm"):
+                self.p[f"l{i}.{gain}"] = torch.ones_like(self.p[f"l{i}.{gain}"])
+
+    def _alloc_kv_cache(self, kv_pages: int) -> None:
+        """The per-layer K / V caches (paged pools with ``kv_pages > 0``), their layout flags and, for an
+        e4m3 cache on the fused backend, the scale tensors."""
+        cfg, sd, D = self.cfg, self.sd, self.cfg.head_dim
+        max_batch, max_seq, fused = self.max_batch, self.max_seq, self.backend == "fused"
+        cdt = torch.bfloat16 if fused else torch.float32
+        # fused: head-major caches ([.., Hkv, rows, D]) -- one head's rows contiguous, so a decode split
+        # block streams one 16 KiB run instead of 64 slices of 256 B (MLS_KV_HEAD_MAJOR=0: row-major)
+        self.kv_hm = fused and os.environ.get("MLS_KV_HEAD_MAJOR", "1") == "1"
+        self.pages = None
+        if kv_pages > 0:
+            from .kv_pages import PageTable
+
+            self.page_rows = 64  # = the decode split: one page per split block
+            self.pages = PageTable(kv_pages, self.page_rows, max_batch, -(-max_seq // self.page_rows), self.device)
+            shape = (kv_pages, sd.hkv, self.page_rows, D) if self.kv_hm else (kv_pages, self.page_rows, sd.hkv, D)
+        else:
+            shape = (max_batch, sd.hkv, max_seq, D) if self.kv_hm else (max_batch, max_seq, sd.hkv, D)
+        self.kv_hm_rows = 0 if not self.kv_hm else (self.page_rows if kv_pages > 0 else max_seq)
+        self.kv_fp8 = fused and self.kv_dtype == "fp8"
+        self.k_scale: List[torch.Tensor] = []
+        self.v_scale: List[torch.Tensor] = []
+        if self.kv_fp8:
+            # the matrix-core decode kernel's own limits; no fallback to bf16 rows
+            G = sd.hq // max(sd.hkv, 1)
+            bad = [why for ok, why in (
+                (self.kv_hm, "the head-major cache layout (MLS_KV_HEAD_MAJOR=0 is set)"),
+                (D == 128, f"head_dim 128 (got {D})"),
+                (sd.hq % sd.hkv == 0 and G in (1, 2, 4, 8), f"Hq / Hkv in 1, 2, 4, 8 (got {sd.hq} / {sd.hkv})"),
+                (self.dec_chunk in (0, 64, 128), f"decode splits of 64 or 128 rows (MLS_DEC_CHUNK={self.dec_chunk})"),
+                (kv_pages > 0 or max_seq % 4 == 0, f"max_seq a multiple of 4 (got {max_seq})"),
+            ) if not ok]
+            if bad:
+                raise ValueError("kv_dtype='fp8' on the fused backend needs " + "; ".join(bad))
+            cdt = torch.uint8
+            self.k_scale = [torch.zeros(shape[:3], device=self.device, dtype=torch.float32) for _ in range(cfg.layers)]
+            self.v_scale = [torch.zeros_like(self.k_scale[0]) for _ in range(cfg.layers)]
+        self.k_cache = [torch.zeros(shape, device=self.device, dtype=cdt) for _ in range(cfg.layers)]
+        self.v_cache = [torch.zeros_like(self.k_cache[0]) for _ in range(cfg.layers)]
+
+    def _fold_and_quantise(self, weight_dtype: str) -> None:
+        """The fused backend's weights as its kernels read them: gate / up interleaved, the RMSNorm gains
+        folded into the projections that consume the normalised activations, and with
+        ``weight_dtype="int4"`` the layer projections quantised as held then."""
+        ops, cfg = self.ops, self.cfg
+        for i in range(cfg.layers):
+            gu = ops.interleave_gate_up(self.p.pop(f"l{i}.gate"), self.p.pop(f"l{i}.up"))
+            mlp_g = self.p.pop(f"l{i}.mlp_norm")
+            self.p[f"l{i}.gate_up"] = ops.fold_norm(gu, mlp_g)
+            self.p[f"l{i}.qkv"] = ops.fold_norm(self.p[f"l{i}.qkv"], self.p.pop(f"l{i}.attn_norm"))
+        self.p["lm_head"] = ops.fold_norm(self.p["lm_head"], self.p.pop("final_norm"))
+        if weight_dtype != "int4":
+            return
+        # quantised as held here (gain folded, gate / up interleaved: a row permutation).  p
+        # keeps the bf16 rounding of the dequantised matrix for the > w4_max_rows GEMMs
+        # (prefill, chunked prefill), w4 the packed codes the decode steps stream; no
+        # granule-packed bf16 copy of these names (_pack_decode_copies)
+        for i in range(cfg.layers):
+            for n in ("qkv", "o", "gate_up", "down"):
+                q, sc = R.w4_quant(self.p[f"l{i}.{n}"])
+                self.p[f"l{i}.{n}"] = R.w4_dequant(q, sc).to(torch.bfloat16)
+                self.w4[f"l{i}.{n}"] = ops.pack_skinny_w4_codes(q, sc)
+                del q, sc
+        # decode steps up to this many rows stream the int4 codes: the kernel's own limit (the
+        # measurements behind it: llama_route.proj_tiers)
+        self.w4_max_rows = min(32, int(os.environ.get("MLS_W4_MAX_ROWS", "32")))
+        self.w4_variant = int(os.environ.get("MLS_W4_VARIANT", "0"))  # probe knob: the launch shape
+
+    def _pack_decode_copies(self) -> None:
+        """The second copies of the projections that decode-shaped steps stream (``self.packed``,
+        ``self.fp8``); a matrix held as int4 codes gets neither."""
+        ops, cfg = self.ops, self.cfg
+        if self.device.type != "cuda":
+            return
+        names = [f"l{i}.{n}" for i in range(cfg.layers) for n in ("qkv", "o", "gate_up", "down")] + ["lm_head"]
+        # Decode (<= 24 tokens per step) streams a second, granule-packed copy of every projection
+        # (ops.pack_skinny: each wave reads contiguous 1 KiB granules, non-temporal): 3.4-4.5 ->
+        # 4.6-6.2 TB/s on the Llama-3-8B shapes (profiles/r2_decode_packed_weight_probe.jsonl).
+        # Costs one more copy of the weights in HBM (16 GB at 8B / TP = 1 of 288 GB);
+        # MLS_PACKED_DECODE=0 turns it off, "auto" packs while the copy stays under 1/4 of the card.
+        mode = os.environ.get("MLS_PACKED_DECODE", "auto")
+        if mode != "0":
+            fit = [n for n in names if self.p[n].shape[0] % 16 == 0 and self.p[n].shape[1] % 32 == 0
+                   and self.p[n].numel() * 2 < (1 << 31) and n not in self.w4]
+            total = sum(self.p[n].numel() * 2 for n in fit)
+            cap = torch.cuda.get_device_properties(self.device).total_memory
+            if mode == "1" or total <= cap // 4:
+                self.packed = {n: ops.pack_skinny(self.p[n]) for n in fit}
+        # Opt-in FP8 decode (MLS_DECODE_FP8=1): W8A8 e4m3 copies of the projections, per-channel
+        # weight scales and per-row activation scales (ops.skinny_fp8), for <= 4 tokens per step --
+        # half the weight stream (profiles/r2_decode_fp8_weight_probe.jsonl).  Changes numerics
+        # (e4m3 has a 3-bit mantissa), so bf16 stays the default.
+        if os.environ.get("MLS_DECODE_FP8", "0") == "1":
+            # only matrices of >= 16M weights: below that a decode GEMM is latency-bound and the
+            # fp8 prologue (row |max| reduction + requantisation) costs more than the bytes saved
+            # -- one emulated TP = 8 rank was 1.13 -> 1.18 ms/token with every projection in fp8
+            min_el = int(os.environ.get("MLS_DECODE_FP8_MIN", str(1 << 24)))
+            self.fp8 = {n: ops.pack_skinny_fp8(self.p[n]) for n in names
+                        if self.p[n].shape[0] % 16 == 0 and self.p[n].shape[1] % 64 == 0
+                        and min_el <= self.p[n].numel() < (1 << 31) and n not in self.w4}  # int4 wins
 
     # ---------------------------------------------------------------- shared pieces
     @property
@@ -735,270 +791,285 @@ class LlamaTP:
         return self._local_topk(logits, k)
 
     # ---------------------------------------------------------------- fused backend
+    def _route(self, B: int, S: int, decode: bool, has_past: bool, all_rows: bool) -> StepRoute:
+        """The kernels this forward runs (models/llama_route.py), from host values alone: nothing here
+        reads a device tensor, so it is safe inside graph capture."""
+        sd, cfg = self.sd, self.cfg
+        car = getattr(self.comm, "car", None) if self.tp > 1 else None  # both questions below arise at TP > 1 only
+        return step_route(
+            B=B, S=S, decode=decode, has_past=has_past, all_rows=all_rows, tp=self.tp, hq=sd.hq, hkv=sd.hkv,
+            head_dim=cfg.head_dim, hidden=cfg.hidden, have_packed=bool(self.packed), have_w4=bool(self.w4),
+            have_fp8=bool(self.fp8), o_packed="l0.o" in self.packed, o_fp8="l0.o" in self.fp8,
+            w4_max_rows=self.w4_max_rows, pk_fold=self.pk_fold, prefill_fold=self.prefill_fold,
+            fuse_combine=self.fuse_combine, fuse_add_norm=self.fuse_add_norm, ar_fuse=self.ar_fuse,
+            tp_overlap=self.tp_overlap, verify_attn=self.verify_attn, spec_max_tokens=self.spec_max_tokens,
+            dec_chunk=self.dec_chunk, ar_fusable=car is not None and car.fusable(B * S * cfg.hidden),
+            capturing=self.tp > 1 and self.device.type == "cuda" and torch.cuda.is_current_stream_capturing())
+
+    # -- projections: one walk down the ladder of weight copies (llama_route.ProjTiers)
+    def _skinny(self, tr: ProjTiers, name: str, K: int):
+        """The decode kernel over the copy of W_name that ``tr``'s row count streams -- int4 codes, e4m3,
+        granule-packed bf16, in that order -- as ``f(x, **kw)``; None: the model holds no such copy (or
+        the rows are too many), the caller runs the row-major matrix."""
+        ops, N = self.ops, self.p[name].shape[0]
+        if tr.w4 and name in self.w4:
+            return lambda x, **kw: ops.skinny_w4(x, *self.w4[name], N, variant=self.w4_variant, **kw)
+        if tr.fp8_for(K) and name in self.fp8:
+            return lambda x, **kw: ops.skinny_fp8(x, *self.fp8[name], N, **kw)
+        if tr.packed and name in self.packed:
+            return lambda x, **kw: ops.skinny_packed(x, self.packed[name], N, variant=self.pk_variant, **kw)
+        return None
+
+    def _proj(self, tr: ProjTiers, x: torch.Tensor, name: str, residual: Optional[torch.Tensor] = None):
+        """``x @ W_name^T (+ residual)``."""
+        skinny = self._skinny(tr, name, x.shape[1])
+        if skinny is not None:
+            return skinny(x, residual=residual)
+        return self.ops.linear(x, self.p[name], residual=residual, workspace=self.workspace)
+
+    def _norm_proj(self, tr: ProjTiers, x: torch.Tensor, name: str, d: Optional[torch.Tensor] = None,
+                   act=None, xn: Optional[torch.Tensor] = None, resid_out: bool = True, impl: str = "auto"):
+        """``(act(RMSNorm(x + d) @ W_name^T), residual)`` with the gain folded into W.  The residual
+        stream after the add is ``x`` itself without ``d``, else a new tensor (the one-launch kernels)
+        or ``x`` updated in place (RMSNorm + GEMM) -- unless ``resid_out`` is off: then ``x + d`` is
+        written nowhere.  ``xn``: RMSNorm(x) as a preceding :meth:`_proj_add_norm` staged it (``d`` is
+        None then); ``impl``: ``ops.linear``'s, above 16 rows."""
+        ops, eps, ws = self.ops, self.cfg.eps, self.workspace
+        w = self.p[name]
+        act = ops.ACT_NONE if act is None else act
+        if xn is not None:
+            return ops.linear(xn, w, act=act, workspace=ws), x
+        skinny = self._skinny(tr, name, x.shape[1])
+        if skinny is None and not tr.fuse:
+            if d is None:
+                xn = ops.rmsnorm(x, self.ones, eps=eps)
+            else:
+                xn = ops.rmsnorm(d, self.ones, residual=x, residual_out=x if resid_out else None, eps=eps)
+            return ops.linear(xn, w, act=act, workspace=ws, impl=impl), x
+        r_new = torch.empty_like(x) if d is not None and resid_out else None
+        if skinny is not None:
+            y = skinny(x, delta=d, resid_out=r_new, norm=True, act=act, eps=eps)
+        else:
+            y = ops.gemm_rmsnorm(x, w, d, r_new, act=act, eps=eps, workspace=ws)
+        return y, (x if r_new is None else r_new)
+
+    def _row_parallel(self, rt: StepRoute, x: torch.Tensor, name: str) -> torch.Tensor:
+        """sum over the TP ranks of x @ W_name^T (W row-parallel: each rank holds a K slice)."""
+        if rt.ar_fuse and name in self.packed and not (rt.proj.fp8_for(x.shape[1]) and name in self.fp8):
+            self.ar_fused_calls += 1
+            with tracing.range("tp.gemm_all_reduce"):
+                return self.ops.skinny_packed_ar(x, self.packed[name], self.p[name].shape[0], self.comm.car,
+                                                 variant=self.pk_variant)
+        return self.comm.all_reduce_(self._proj(rt.proj, x, name))
+
+    def _proj_add_norm(self, x: torch.Tensor, name: str, r: torch.Tensor) -> Optional[torch.Tensor]:
+        """``r += x @ W_name^T`` in place and RMSNorm(r) for the next projection
+        (``ops.linear_add_rmsnorm``); None, with nothing launched, where that op has no route."""
+        xn = self.ops.linear_add_rmsnorm(x, self.p[name], r, self.ones, self.cfg.eps, self.workspace)
+        if xn is not None:
+            self.add_norm_fused += 1
+        return xn
+
+    # -- attention
+    def _verify_workspace(self, T: int, chunk: int) -> torch.Tensor:
+        """Split-KV partials of a verify step (``ops.decode_attention_multi``) of T rows."""
+        sd, D = self.sd, self.cfg.head_dim
+        cap = self.pages.pages_per_seq * self.page_rows if self.pages is not None else self.max_seq
+        need = T * sd.hq * (-(-min(self._dec_ctx or cap, cap) // chunk)) * (D + 2)
+        # a captured step owns its workspace (_verify_graph keeps it alive with the graph, whose launches
+        # hold its address); only the uncaptured steps share one, which may therefore be regrown
+        ws = self._ver_ws_graph
+        if ws is None:
+            if self.ver_ws is None or self.ver_ws.numel() < need:
+                self.ver_ws = torch.empty(need, device=self.device, dtype=torch.float32)
+            ws = self.ver_ws
+        elif ws.numel() < need:
+            ws = self._ver_ws_graph = torch.empty(need, device=self.device, dtype=torch.float32)
+        return ws
+
+    def _ctx_split_kw(self, B: int, S: int, max_ctx: Optional[int]) -> dict:
+        """Prefix caching on: a prefill chunk (not a verify step, whose graphs own their workspaces) of few
+        queries against a long cached context runs split-KV where :meth:`ctx_splits` says so."""
+        sd, D = self.sd, self.cfg.head_dim
+        cap = self.pages.pages_per_seq * self.page_rows if self.pages is not None else self.max_seq
+        ctx_max = min(int(max_ctx) if max_ctx else cap, cap)  # no host bound given: what a slot holds
+        n_split = self.ctx_splits(B, S, sd.hq, ctx_max)
+        if n_split <= 1:
+            return {}
+        need = self.ops.flash_ctx_workspace_elems(B, S, sd.hq, D, n_split)
+        if self.ctx_ws is None or self.ctx_ws.numel() < need:
+            self.ctx_ws = torch.empty(need, device=self.device, dtype=torch.float32)
+        return dict(splits=n_split, max_ctx=ctx_max, workspace=self.ctx_ws)
+
+    def _attention_kw(self, rt: StepRoute, B: int, S: int, decode: bool, pos: torch.Tensor, sid, past, all_rows: bool,
+                      max_ctx: Optional[int]) -> dict:
+        """What every layer's attention call of one step has in common, built once."""
+        table = self.pages.dev if self.pages is not None else None
+        if decode:  # RoPE + KV append ride inside the decode-attention launch
+            kw = dict(workspace=self.dec_ws, counters=self.dec_cnt, positions=pos, cos=self.cos, sin=self.sin,
+                      max_len=self._dec_ctx, combine=not rt.fuse_combine,
+                      chunk=rt.dec_chunk if table is None else self.page_rows,
+                      page_table=None if table is None else table[:B])
+            if not self.kv_fp8:
+                kw["head_major"] = self.kv_hm
+            return kw
+        if rt.multi:
+            chunk = self.page_rows if table is not None else (rt.dec_chunk if rt.dec_chunk in (64, 128) else 64)
+            return dict(slot_ids=sid, chunk=chunk, max_len=self._dec_ctx, page_table=table,
+                        workspace=self._verify_workspace(B * S, chunk))
+        if past is not None:  # chunked prefill: the chunk's queries against the cache rows just written
+            split = self._ctx_split_kw(B, S, max_ctx) if self.ctx_split and not all_rows else {}
+            return dict(slot_ids=sid, page_table=table, **split)
+        return {}
+
+    def _rope_kv(self, i: int, qkv: torch.Tensor, pos, slots, lens, S: int, flat_off: Optional[int] = None) -> None:
+        """RoPE on the Q / K heads of ``qkv`` in place + the append of its K / V rows to layer i's cache
+        (an e4m3 cache: quantised; qkv keeps the unquantised bf16 K / V that prefill attention reads).
+        ``flat_off``: the bf16 caches from that element on, flattened (implicit slots of a batch half)."""
+        sd = self.sd
+        args = (qkv, pos, self.cos, self.sin, sd.hq, sd.hkv, self.cfg.head_dim, slots)
+        kw = dict(lens=lens, seq=S, max_seq=self.max_seq, hm_rows=self.kv_hm_rows)
+        if self.kv_fp8:
+            self.ops.rope_kv_fp8_(*args, self.k_cache[i], self.v_cache[i], self.k_scale[i], self.v_scale[i], **kw)
+        elif flat_off is None:
+            self.ops.rope_kv_(*args, self.k_cache[i], self.v_cache[i], **kw)
+        else:
+            self.ops.rope_kv_(*args, self.k_cache[i].reshape(-1)[flat_off:], self.v_cache[i].reshape(-1)[flat_off:], **kw)
+
+    def _fused_attention(self, i: int, qkv: torch.Tensor, st: "_Forward"):
+        """Layer i's attention for the step's ``qkv`` rows, RoPE and the KV append included: ``(a, parts)``,
+        ``parts`` the split-KV partials where their combine rides in the o-projection, else None."""
+        ops, sd, D = self.ops, self.sd, self.cfg.head_dim
+        kc, vc = self.k_cache[i], self.v_cache[i]
+        if st.decode:
+            caches = (kc, vc, self.k_scale[i], self.v_scale[i]) if self.kv_fp8 else (kc, vc)  # e4m3: same partials
+            if self.pages is None:
+                caches = [c[:st.B] for c in caches]
+            attend = ops.decode_attention_fp8 if self.kv_fp8 else ops.decode_attention
+            a = attend(qkv, *caches, st.lens, sd.hq, sd.hkv, D, **st.attn_kw)
+            return a if st.rt.fuse_combine else (a, None)
+        self._rope_kv(i, qkv, st.pos, st.slots, st.lens, st.S)
+        if st.rt.multi:
+            return ops.decode_attention_multi(qkv, kc, vc, st.past, st.lens, st.B, st.S, sd.hq, sd.hkv, D,
+                                              **st.attn_kw), None
+        if st.past is not None:
+            return ops.flash_attention_ctx(qkv, kc, vc, st.past, st.lens, st.B, st.S, sd.hq, sd.hkv, D,
+                                           **st.attn_kw), None
+        return ops.flash_attention(qkv, st.B, st.S, sd.hq, sd.hkv, D, kv_lens=st.lens, causal=True), None
+
+    # -- after attention: o-projection -> gate_up -> down, in the shape the route names
+    def _layer_tail(self, i: int, st: "_Forward", a: torch.Tensor, parts) -> None:
+        rt = st.rt
+        if rt.fold:
+            self._tail_folded(i, st, a, parts)
+            return
+        # o (and, if it can, down) through ops.linear_add_rmsnorm; where o_proj has no such route, or an
+        # earlier layer left a delta, the all-reduce pair
+        staged = rt.fuse_rn and st.delta is None and self._tail_staged(i, st, a)
+        if not staged:
+            self._tail_reduced(i, st, a, parts)
+
+    def _o_combine(self, rt: StepRoute, name: str, a: torch.Tensor, parts, residual=None) -> torch.Tensor:
+        """The o-projection with the split-KV combine in its prologue (one launch, not two) and, at
+        TP > 1 where it can, the all-reduce in its epilogue; otherwise this rank's partial sum."""
+        N = self.p[name].shape[0]
+        if rt.ar_fuse:
+            self.ar_fused_calls += 1
+            with tracing.range("tp.gemm_all_reduce"):
+                return self.ops.skinny_packed_combine_ar(a, parts, self.packed[name], N, self.comm.car,
+                                                         variant=self.pk_variant)
+        return self.ops.skinny_packed_combine(a, parts, self.packed[name], N, residual=residual, variant=self.pk_variant)
+
+    def _tail_folded(self, i: int, st: "_Forward", a: torch.Tensor, parts) -> None:
+        """TP = 1: h = r + a Wo^T, r' = h + g Wd^T, both adds in the GEMM epilogues; no delta."""
+        tr = st.rt.proj
+        if parts is not None:
+            h = self._o_combine(st.rt, f"l{i}.o", a, parts, residual=st.r)
+        else:
+            h = self._proj(tr, a, f"l{i}.o", residual=st.r)
+        st.o = h
+        gu, _ = self._norm_proj(tr, h, f"l{i}.gate_up", act=self.ops.ACT_SILU_MUL)
+        st.gu = gu
+        st.r = self._proj(tr, gu, f"l{i}.down", residual=h)
+
+    def _tail_staged(self, i: int, st: "_Forward", a: torch.Tensor) -> bool:
+        """o_proj, and down_proj where it can (never the last layer's: the lm_head reads r and delta),
+        add into r in place and stage RMSNorm(r) for the next projection.  False, with nothing
+        launched, if o_proj has no such route."""
+        xn = self._proj_add_norm(a, f"l{i}.o", st.r)
+        if xn is None:
+            return False
+        gu, st.r = self._norm_proj(st.rt.proj, st.r, f"l{i}.gate_up", act=self.ops.ACT_SILU_MUL, xn=xn)
+        st.gu = gu
+        if i + 1 < self.cfg.layers:
+            st.xn = self._proj_add_norm(gu, f"l{i}.down", st.r)  # delta stays None: the down output is in r
+        if st.xn is None:
+            st.delta = self._row_parallel(st.rt, gu, f"l{i}.down")
+        return True
+
+    def _tail_reduced(self, i: int, st: "_Forward", a: torch.Tensor, parts) -> None:
+        """The all-reduce pair: o and down each summed over the ranks, each added to r by the pre-norm
+        of the projection after it (delta)."""
+        rt = st.rt
+        if parts is None:
+            o = self._row_parallel(rt, a, f"l{i}.o")
+        else:
+            o = self._o_combine(rt, f"l{i}.o", a, parts)
+            if not rt.ar_fuse:
+                o = self.comm.all_reduce_(o)
+        st.o = o
+        gu, st.r = self._norm_proj(rt.proj, st.r, f"l{i}.gate_up", o, act=self.ops.ACT_SILU_MUL)
+        st.gu = gu
+        st.delta = self._row_parallel(rt, gu, f"l{i}.down")
+
     def _fused_forward(self, ids: torch.Tensor, positions: torch.Tensor, lens: torch.Tensor, B: int, S: int,
                        decode: bool, k: int, slot_ids: Optional[torch.Tensor] = None,
                        past: Optional[torch.Tensor] = None, all_rows: bool = False, max_ctx: Optional[int] = None):
         """Native-kernel forward.  The RMSNorm gains are folded into the following projections, so
         for decode-shaped token counts (<= 16) each pre-norm + residual add rides inside the skinny
         GEMM (``ops.gemm_rmsnorm``: 7 launches per layer); larger counts run a gain-free RMSNorm and
-        the library / native GEMM (``ops.linear``)."""
-        ops, cfg, sd, p = self.ops, self.cfg, self.sd, self.p
-        D, eps = cfg.head_dim, cfg.eps
-        ws = self.workspace
-        fuse = B * S <= 16
+        the library / native GEMM (``ops.linear``).  Which kernels: :meth:`_route`."""
+        ops, cfg = self.ops, self.cfg
+        rt = self._route(B, S, decode, past is not None, all_rows)
         pos = positions.reshape(-1)
-        explicit_slots = None
-        sid = None
+        slots = sid = None
         if (slot_ids is not None or self.pages is not None or past is not None) and not decode:
             # prefill into arbitrary cache rows (continuous batching) / through the page table: one
             # native launch (ops.prefill_slots), -1 past each sequence's length
             sid = None if slot_ids is None else slot_ids.to(torch.int32)
             if self.pages is not None:
-                explicit_slots = ops.prefill_slots(pos, lens, B, S, sid, table=self.pages.device_table(),
-                                                   page_rows=self.pages.page_rows)
+                slots = ops.prefill_slots(pos, lens, B, S, sid, table=self.pages.device_table(),
+                                          page_rows=self.pages.page_rows)
             else:
-                explicit_slots = ops.prefill_slots(pos, lens, B, S, sid, max_seq=self.max_seq)
+                slots = ops.prefill_slots(pos, lens, B, S, sid, max_seq=self.max_seq)
         if past is not None:  # a padding row's position may lie past the RoPE table (its slot is -1 already)
             pos = pos.clamp(max=self.max_seq - 1)
-        # decode split size: 64 rows measured best from batch 1 to 32, at TP = 1 and on an emulated
-        # TP = 8 rank (one KV head).  A single 256-row split per KV head (no combine launch) was
-        # 1.6 % slower at batch 1, and one 8-wave block walking a whole <= 1024 context in passes
-        # was 26 % slower at TP = 8 (latency-bound on one CU) -- profiles/r1_llama_decode_sweep.jsonl.
-        # From batch 32 up the grid is already >= 4k blocks and 128-row splits halve the combine
-        # traffic: -3 % step time at batch 128 (profiles/r2_llama8b_decode_chunk_sweep.jsonl).
-        dec_chunk = self.dec_chunk if self.dec_chunk > 0 else (128 if B >= 32 else 64)
-        r = self._embed(ids.reshape(-1))  # residual stream (bf16)
-        delta = None
-
-        T = B * S
-        # packed decode GEMMs up to 24 rows: at 25-32 (two 16-row A fragments per weight granule)
-        # every column-tile block re-reads A, and the row-major split-K kernel is ahead (batch 24:
-        # 4.99 vs 5.36 ms/step, batch 32: 5.75 vs 5.64; profiles/r2_llama8b_decode_packed_ab.jsonl)
-        packed = self.packed if T <= 24 else {}
-        # weight_dtype="int4": the layer projections stream their 4-bit codes (ops.skinny_w4) instead;
-        # no all-reduce tail / combine prologue there, so those run as separate launches
-        w4 = self.w4 if T <= self.w4_max_rows else {}
-
-        # TP = 1: the residual add rides in the o / down epilogues (h = r + a Wo^T, r' = h + g Wd^T), so
-        # the next pre-norm GEMM reads one activation stream instead of two (r + delta) and writes no
-        # residual copy.  With TP > 1 the add has to wait for the all-reduce.
-        fold = self.tp == 1 and (((bool(packed) or bool(w4)) and self.pk_fold) or (not decode and getattr(self, "prefill_fold", False)))
-        # decode: the o-projection merges the split-KV partials in its prologue (one launch instead of
-        # two) while every block's share of partials is small -- B x local q heads <= 32: one emulated
-        # TP = 8 rank 1.166 -> 1.125 ms/token at batch 1, 1.294 -> 1.254 at 4; TP = 1 batch 1 level,
-        # batch 4 (128 head rows per block) 3.17 -> 3.37, so off there (profiles/r2_llama8b_fused_combine_ab.jsonl)
-        fuse_combine = (decode and self.fuse_combine and "l0.o" in packed and "l0.o" not in self.fp8 and B <= 4
-                        and B * sd.hq <= 32 and B * sd.hq * D * 2 <= 65536)
-
-        fp8 = self.fp8 if T <= 4 else {}
-        # a verify step (all_rows: every row's candidates) of a few positions per sequence: its attention
-        # runs split-KV on the matrix cores with the T positions x G heads of a KV head on one MFMA's lane
-        # columns (ops.decode_attention_multi); MLS_VERIFY_ATTN=ctx keeps the chunk kernel (the A/B arm).
-        # Chunked prefill (all_rows False) stays on flash_attention_ctx.
-        multi = (past is not None and all_rows and self.verify_attn != "ctx" and S <= self.spec_max_tokens
-                 and S * (sd.hq // max(sd.hkv, 1)) <= 16)
-        if multi:
-            chunk_v = self.page_rows if self.pages is not None else (dec_chunk if dec_chunk in (64, 128) else 64)
-            cap_v = self.pages.pages_per_seq * self.page_rows if self.pages is not None else self.max_seq
-            need = T * sd.hq * (-(-min(self._dec_ctx or cap_v, cap_v) // chunk_v)) * (D + 2)
-            # a captured step owns its workspace (_verify_graph keeps it alive with the graph, whose launches
-            # hold its address); only the uncaptured steps share one, which may therefore be regrown
-            ws_v = self._ver_ws_graph
-            if ws_v is None:
-                if self.ver_ws is None or self.ver_ws.numel() < need:
-                    self.ver_ws = torch.empty(need, device=self.device, dtype=torch.float32)
-                ws_v = self.ver_ws
-            elif ws_v.numel() < need:
-                ws_v = self._ver_ws_graph = torch.empty(need, device=self.device, dtype=torch.float32)
-
-        # prefix caching on: a prefill chunk (not a verify step, whose graphs own their workspaces) of few
-        # queries against a long cached context runs split-KV where ctx_splits says so
-        ctx_kw = {}
-        if self.ctx_split and past is not None and not all_rows and not multi:
-            cap_c = self.pages.pages_per_seq * self.page_rows if self.pages is not None else self.max_seq
-            ctx_max = min(int(max_ctx) if max_ctx else cap_c, cap_c)  # no host bound given: what a slot holds
-            n_split = self.ctx_splits(B, S, sd.hq, ctx_max)
-            if n_split > 1:
-                need = ops.flash_ctx_workspace_elems(B, S, sd.hq, D, n_split)
-                if self.ctx_ws is None or self.ctx_ws.numel() < need:
-                    self.ctx_ws = torch.empty(need, device=self.device, dtype=torch.float32)
-                ctx_kw = dict(splits=n_split, max_ctx=ctx_max, workspace=self.ctx_ws)
-
-        def use_fp8(name, K):
-            return name in fp8 and T * K * 2 <= 65536
-
-        # TP > 1 decode: the row-parallel o / down projections run their all-reduce in their own
-        # epilogue (ops.skinny_packed_ar / skinny_packed_combine_ar, csrc/ar_protocol.h): one launch
-        # per projection + all-reduce instead of two, and each 2048-element chunk of the output is
-        # reduced as soon as the blocks producing it finish.  MLS_AR_FUSE=0: separate kernels.
-        car = getattr(self.comm, "car", None)
-        ar_fuse = (self.tp > 1 and car is not None and getattr(self, "ar_fuse", False) and bool(packed)
-                   and car.fusable(T * self.cfg.hidden))
-
-        def row_parallel(x, name):
-            """sum over the TP ranks of x @ W_name^T (W row-parallel: each rank holds a K slice)."""
-            if ar_fuse and name in packed and not use_fp8(name, x.shape[1]):
-                self.ar_fused_calls += 1
-                with tracing.range("tp.gemm_all_reduce"):
-                    return ops.skinny_packed_ar(x, packed[name], p[name].shape[0], car, variant=self.pk_variant)
-            return self.comm.all_reduce_(linear(x, name))
-
-        def linear(x, name, residual=None):
-            if name in w4:
-                return ops.skinny_w4(x, *w4[name], p[name].shape[0], residual=residual, variant=self.w4_variant)
-            if use_fp8(name, x.shape[1]):
-                q, sc = fp8[name]
-                return ops.skinny_fp8(x, q, sc, p[name].shape[0], residual=residual)
-            if name in packed:
-                return ops.skinny_packed(x, packed[name], p[name].shape[0], residual=residual, variant=self.pk_variant)
-            return ops.linear(x, p[name], residual=residual, workspace=ws)
-
-        # TP = 1 above 24 tokens (no packed / fused-norm GEMMs): o_proj and down_proj leave their split-K
-        # slabs to one kernel that adds them to the residual stream and normalises it for the next
-        # projection (ops.linear_add_rmsnorm) -- one launch instead of reduce + RMSNorm, bit-identical.
-        # A projection it cannot take (no split on that shape) runs the plain pair.
-        fuse_rn = self.tp == 1 and not packed and not fuse and not fold and getattr(self, "fuse_add_norm", True)
-        xn_pending = [None]  # RMSNorm(r) computed by the previous projection's fused reduce
-
-        def proj_add_norm(x, name):
-            """r += x @ W_name^T in place, and RMSNorm(r) staged for the next pre_norm; False: not taken."""
-            xn = ops.linear_add_rmsnorm(x, p[name], r, self.ones, eps, ws) if fuse_rn else None
-            xn_pending[0] = xn
-            if xn is not None:
-                self.add_norm_fused = getattr(self, "add_norm_fused", 0) + 1
-            return xn is not None
-
-        def pre_norm(x, name, d, act=ops.ACT_NONE):
-            w = p[name]
-            if xn_pending[0] is not None:
-                xn, xn_pending[0] = xn_pending[0], None
-                return ops.linear(xn, w, act=act, workspace=ws), x
-            if name in w4:
-                r_new = None if d is None else torch.empty_like(x)
-                y = ops.skinny_w4(x, *w4[name], w.shape[0], delta=d, resid_out=r_new, norm=True, act=act, eps=eps,
-                                  variant=self.w4_variant)
-                return y, (x if d is None else r_new)
-            if use_fp8(name, x.shape[1]):
-                q, sc = fp8[name]
-                r_new = None if d is None else torch.empty_like(x)
-                y = ops.skinny_fp8(x, q, sc, w.shape[0], delta=d, resid_out=r_new, norm=True, act=act, eps=eps)
-                return y, (x if d is None else r_new)
-            if name in packed:
-                r_new = None if d is None else torch.empty_like(x)
-                y = ops.skinny_packed(x, packed[name], w.shape[0], delta=d, resid_out=r_new, norm=True, act=act,
-                                      eps=eps, variant=self.pk_variant)
-                return y, (x if d is None else r_new)
-            if fuse:
-                r_new = None if d is None else torch.empty_like(x)
-                y = ops.gemm_rmsnorm(x, w, d, r_new, act=act, eps=eps, workspace=ws)
-                return y, (x if d is None else r_new)
-            xn = ops.rmsnorm(x if d is None else d, self.ones, residual=None if d is None else x,
-                             residual_out=None if d is None else x, eps=eps)
-            return ops.linear(xn, w, act=act, workspace=ws), x
-
-        overlap = (not decode and past is None and self.tp > 1 and B >= 2 and T >= 64 and self.tp_overlap
-                   and not torch.cuda.is_current_stream_capturing())
-        if overlap:
-            r, delta = self._prefill_overlapped(r, pos, lens, B, S, explicit_slots, pre_norm, linear)
-        for i in range(0 if not overlap else cfg.layers, cfg.layers):
-            qkv, r = pre_norm(r, f"l{i}.qkv", delta)
-            parts = None
-            if decode:  # RoPE + KV append ride inside the decode-attention launch
-                kw = dict(workspace=self.dec_ws, counters=self.dec_cnt, positions=pos, cos=self.cos, sin=self.sin,
-                          max_len=self._dec_ctx, combine=not fuse_combine)
-                if self.kv_fp8:  # e4m3 cache: same partials, same consumers
-                    if self.pages is not None:
-                        a = ops.decode_attention_fp8(qkv, self.k_cache[i], self.v_cache[i], self.k_scale[i],
-                                                     self.v_scale[i], lens, sd.hq, sd.hkv, D, chunk=self.page_rows,
-                                                     page_table=self.pages.dev[:B], **kw)
-                    else:
-                        a = ops.decode_attention_fp8(qkv, self.k_cache[i][:B], self.v_cache[i][:B],
-                                                     self.k_scale[i][:B], self.v_scale[i][:B], lens, sd.hq, sd.hkv,
-                                                     D, chunk=dec_chunk, **kw)
-                elif self.pages is not None:
-                    a = ops.decode_attention(qkv, self.k_cache[i], self.v_cache[i], lens, sd.hq, sd.hkv, D,
-                                             chunk=self.page_rows, page_table=self.pages.dev[:B],
-                                             head_major=self.kv_hm, **kw)
-                else:
-                    a = ops.decode_attention(qkv, self.k_cache[i][:B], self.v_cache[i][:B], lens, sd.hq, sd.hkv,
-                                             D, chunk=dec_chunk, head_major=self.kv_hm, **kw)
-                if fuse_combine:
-                    a, parts = a
-            else:
-                if self.kv_fp8:  # qkv keeps the unquantised bf16 K / V the flash attention below reads
-                    ops.rope_kv_fp8_(qkv, pos, self.cos, self.sin, sd.hq, sd.hkv, D, explicit_slots, self.k_cache[i],
-                                     self.v_cache[i], self.k_scale[i], self.v_scale[i], lens=lens, seq=S,
-                                     max_seq=self.max_seq, hm_rows=self.kv_hm_rows)
-                else:
-                    ops.rope_kv_(qkv, pos, self.cos, self.sin, sd.hq, sd.hkv, D, explicit_slots, self.k_cache[i],
-                                 self.v_cache[i], lens=lens, seq=S, max_seq=self.max_seq, hm_rows=self.kv_hm_rows)
-                if multi:
-                    a = ops.decode_attention_multi(qkv, self.k_cache[i], self.v_cache[i], past, lens, B, S, sd.hq,
-                                                   sd.hkv, D, slot_ids=sid, chunk=chunk_v, max_len=self._dec_ctx,
-                                                   page_table=self.pages.dev if self.pages is not None else None,
-                                                   workspace=ws_v)
-                elif past is not None:  # chunked prefill: the chunk's queries against the cache rows just written
-                    a = ops.flash_attention_ctx(qkv, self.k_cache[i], self.v_cache[i], past, lens, B, S, sd.hq, sd.hkv,
-                                                D, slot_ids=sid,
-                                                page_table=self.pages.dev if self.pages is not None else None,
-                                                **ctx_kw)
-                else:
-                    a = ops.flash_attention(qkv, B, S, sd.hq, sd.hkv, D, kv_lens=lens, causal=True)
-            if parts is not None:  # split-KV combine in the o-projection's prologue (one launch, not two)
-                o_w = p[f"l{i}.o"]
-                if ar_fuse:  # ... and the all-reduce in its epilogue
-                    self.ar_fused_calls += 1
-                    with tracing.range("tp.gemm_all_reduce"):
-                        o = ops.skinny_packed_combine_ar(a, parts, packed[f"l{i}.o"], o_w.shape[0], car,
-                                                         variant=self.pk_variant)
-                else:
-                    o = ops.skinny_packed_combine(a, parts, packed[f"l{i}.o"], o_w.shape[0],
-                                                  residual=r if fold else None, variant=self.pk_variant)
-                if fold:
-                    gu, _ = pre_norm(o, f"l{i}.gate_up", None, act=ops.ACT_SILU_MUL)
-                    r = linear(gu, f"l{i}.down", residual=o)
-                    continue
-                if not ar_fuse:
-                    o = self.comm.all_reduce_(o)
-                gu, r = pre_norm(r, f"l{i}.gate_up", o, act=ops.ACT_SILU_MUL)
-                delta = row_parallel(gu, f"l{i}.down")
-                continue
-            if fold:
-                h = linear(a, f"l{i}.o", residual=r)
-                gu, _ = pre_norm(h, f"l{i}.gate_up", None, act=ops.ACT_SILU_MUL)
-                r = linear(gu, f"l{i}.down", residual=h)
-                continue
-            if delta is None and proj_add_norm(a, f"l{i}.o"):
-                gu, r = pre_norm(r, f"l{i}.gate_up", None, act=ops.ACT_SILU_MUL)
-                if i + 1 < cfg.layers and proj_add_norm(gu, f"l{i}.down"):
-                    continue  # delta stays None: the down output is in r, its RMSNorm staged for qkv
-                delta = row_parallel(gu, f"l{i}.down")
-                continue
-            o = row_parallel(a, f"l{i}.o")
-            gu, r = pre_norm(r, f"l{i}.gate_up", o, act=ops.ACT_SILU_MUL)
-            delta = row_parallel(gu, f"l{i}.down")
+        st = _Forward(rt, B, S, decode, pos, lens, past, slots, r=self._embed(ids.reshape(-1)))
+        if rt.overlap:
+            st.r, st.delta = self._prefill_overlapped(rt, st.r, pos, lens, B, S, slots)
+        else:
+            st.attn_kw = self._attention_kw(rt, B, S, decode, pos, sid, past, all_rows, max_ctx)
+            for i in range(cfg.layers):
+                qkv, st.r = self._norm_proj(rt.proj, st.r, f"l{i}.qkv", st.delta, xn=st.take_xn())
+                a, parts = self._fused_attention(i, qkv, st)
+                self._layer_tail(i, st, a, parts)
+        r, delta = st.r, st.delta
         if not decode and not all_rows:  # each sequence's last valid token (one native gather of r and delta)
             rows = lens if past is None else lens - past  # valid rows of this forward (on the device)
             if delta is None:
                 r = ops.last_rows(r, rows, B, S)
             else:
                 r, delta = ops.last_rows(r, rows, B, S, delta)
-        nb = r.shape[0]  # rows that reach the lm_head: B, or every row of the step (all_rows)
-        if nb <= 4 and "lm_head" in self.fp8 and nb * r.shape[1] * 2 <= 65536:
-            q, sc = self.fp8["lm_head"]
-            logits = ops.skinny_fp8(r, q, sc, p["lm_head"].shape[0], delta=delta, norm=True, eps=eps)
-        elif nb <= 24 and "lm_head" in self.packed:
-            logits = ops.skinny_packed(r, self.packed["lm_head"], p["lm_head"].shape[0], delta=delta, norm=True,
-                                       eps=eps, variant=self.pk_variant)
-        elif nb <= 16:
-            logits = ops.gemm_rmsnorm(r, p["lm_head"], delta, eps=eps, workspace=ws)
-        else:  # 1 GB of weights: the weight-streaming native tile up to 64 rows, the tile GEMM above
-            # (delta is None when the residual adds rode in the o / down epilogues: int4 steps of 25-32 rows)
-            xn = ops.rmsnorm(r, self.ones, eps=eps) if delta is None else ops.rmsnorm(delta, self.ones, residual=r, eps=eps)
-            logits = ops.linear(xn, p["lm_head"], workspace=ws, impl="native" if nb <= 64 else "auto")
+        # the lm_head down the same ladder at its own row count (B, or every row of the step with all_rows):
+        # never int4; r + delta is not written back; above 16 rows -- 1 GB of weights -- the weight-streaming
+        # native tile up to 64 rows, the tile GEMM above (delta is None there when the residual adds rode
+        # in the o / down epilogues: int4 steps of 25-32 rows)
+        nb = r.shape[0]
+        head = proj_tiers(nb, bool(self.packed), False, bool(self.fp8), 0)
+        logits, _ = self._norm_proj(head, r, "lm_head", delta, resid_out=False, impl="native" if nb <= 64 else "auto")
         return self._local_topk(logits, k)
 
-    def _prefill_overlapped(self, r, pos, lens, B: int, S: int, explicit_slots, pre_norm, linear):
+    def _prefill_overlapped(self, rt: StepRoute, r, pos, lens, B: int, S: int, explicit_slots):
         """TP prefill as two batch halves (micro-batches) interleaved layer by layer so that every
         o / down all-reduce runs while the other half computes:
 
@@ -1010,7 +1081,7 @@ class LlamaTP:
 
         The residual stream rows of each half are updated in place (views of ``r``); returns the
         full residual and the last layer's all-reduced delta."""
-        ops, cfg, sd = self.ops, self.cfg, self.sd
+        ops, cfg, sd, tr = self.ops, self.cfg, self.sd, rt.proj
         D = cfg.head_dim
         half = B // 2
         # plain cache: each half runs rope_kv_'s implicit slot mode (token t -> row (t // S) * max_seq
@@ -1032,29 +1103,20 @@ class LlamaTP:
                 lo, hi = b0 * S, b1 * S
                 if pend_d[m] is not None:
                     dlt[m] = pend_d[m].wait()
-                qkv, res[m] = pre_norm(res[m], f"l{i}.qkv", dlt[m])
+                qkv, res[m] = self._norm_proj(tr, res[m], f"l{i}.qkv", dlt[m])
                 if implicit:
-                    off = b0 * self.max_seq * slot_elems
-                    ops.rope_kv_(qkv, pos[lo:hi], self.cos, self.sin, sd.hq, sd.hkv, D, None,
-                                 self.k_cache[i].reshape(-1)[off:], self.v_cache[i].reshape(-1)[off:],
-                                 lens=lens[b0:b1], seq=S, max_seq=self.max_seq, hm_rows=self.kv_hm_rows)
-                elif self.kv_fp8:
-                    ops.rope_kv_fp8_(qkv, pos[lo:hi], self.cos, self.sin, sd.hq, sd.hkv, D, explicit_slots[lo:hi],
-                                     self.k_cache[i], self.v_cache[i], self.k_scale[i], self.v_scale[i],
-                                     lens=lens[b0:b1], seq=S, max_seq=self.max_seq, hm_rows=self.kv_hm_rows)
+                    self._rope_kv(i, qkv, pos[lo:hi], None, lens[b0:b1], S, flat_off=b0 * self.max_seq * slot_elems)
                 else:
-                    ops.rope_kv_(qkv, pos[lo:hi], self.cos, self.sin, sd.hq, sd.hkv, D, explicit_slots[lo:hi],
-                                 self.k_cache[i], self.v_cache[i], lens=lens[b0:b1], seq=S, max_seq=self.max_seq,
-                                 hm_rows=self.kv_hm_rows)
+                    self._rope_kv(i, qkv, pos[lo:hi], explicit_slots[lo:hi], lens[b0:b1], S)
                 a = ops.flash_attention(qkv, b1 - b0, S, sd.hq, sd.hkv, D, kv_lens=lens[b0:b1], causal=True)
-                pend_o[m] = self.comm.all_reduce_start(linear(a, f"l{i}.o"))
+                pend_o[m] = self.comm.all_reduce_start(self._proj(tr, a, f"l{i}.o"))
             for m in range(2):
                 o = pend_o[m].wait()
-                gu, res[m] = pre_norm(res[m], f"l{i}.gate_up", o, act=ops.ACT_SILU_MUL)
-                pend_d[m] = self.comm.all_reduce_start(linear(gu, f"l{i}.down"))
+                gu, res[m] = self._norm_proj(tr, res[m], f"l{i}.gate_up", o, act=ops.ACT_SILU_MUL)
+                pend_d[m] = self.comm.all_reduce_start(self._proj(tr, gu, f"l{i}.down"))
         dlt = [p.wait() for p in pend_d]
         if any(x.data_ptr() != y.data_ptr() for x, y in zip(res, (r[:half * S], r[half * S:]))):
-            r = torch.cat(res)  # pre_norm handed back new residual tensors instead of the views
+            r = torch.cat(res)  # _norm_proj handed back new residual tensors instead of the views
         return r, torch.cat(dlt)
 
     # ---------------------------------------------------------------- public
@@ -1134,7 +1196,7 @@ class LlamaTP:
         """Captured verify step for B sequences of T positions under the context bound ctx (static id /
         past / lens / slot buffers, as :meth:`_decode_graph`).  Warm-up and capture run with
         ``lens == past``: every row is padding, so no cache row is written."""
-        key = (B, T, k, ctx, getattr(self, "verify_attn", "multi"))  # one graph per attention route (A/B arms)
+        key = (B, T, k, ctx, self.verify_attn)  # one graph per attention route (A/B arms)
         if key in self._ver_graphs:
             return self._ver_graphs[key]
         dev = self.device
@@ -1145,23 +1207,16 @@ class LlamaTP:
         off = torch.arange(T, dtype=torch.int32, device=dev).unsqueeze(0)
         if self.pages is not None:
             self.pages.device_table()
-        self._dec_ctx = ctx
+
+        def run():
+            return self.step(ids, past.unsqueeze(1) + off, lens, decode=False, k=k, slot_ids=slots, past=past,
+                             all_rows=True)
+
         # this graph's own split-KV workspace: the first warm-up step sizes it, the capture bakes its address
         self._ver_ws_graph = torch.empty(0, device=dev, dtype=torch.float32)
         try:
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self.step(ids, past.unsqueeze(1) + off, lens, decode=False, k=k, slot_ids=slots, past=past,
-                              all_rows=True)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                vals, idx = self.step(ids, past.unsqueeze(1) + off, lens, decode=False, k=k, slot_ids=slots,
-                                      past=past, all_rows=True)
+            g, (vals, idx) = self._capture(ctx, run, run)
         finally:
-            self._dec_ctx = None
             ws, self._ver_ws_graph = self._ver_ws_graph, None
         # off and ws stay referenced: the captured launches read / write them at every replay
         self._ver_graphs[key] = (g, ids, past, lens, slots, vals, idx, off, ws)
@@ -1327,6 +1382,39 @@ class LlamaTP:
         probe = torch.empty(B * self.cfg.hidden, dtype=torch.bfloat16, device=car.device)
         return car.eligible(probe)  # one-shot or two-shot: both are in-stream kernels
 
+    def _capture(self, ctx: int, warm, body):
+        """Capture ``body()`` into a graph under the decode context bound ``ctx``, after two runs of
+        ``warm()`` on a side stream (kernel selection, workspaces): ``(graph, body's result)``."""
+        dev = self.device
+        self._dec_ctx = ctx
+        try:
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    warm()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            # thread_local: the RCCL watchdog thread polls its events while this thread captures
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                out = body()
+        finally:
+            self._dec_ctx = None
+        return g, out
+
+    def _warm_decode(self, B: int, k: int, ctx: int):
+        """Warm-up of the device-resident steps' captures: a decode step + X4 gather on scratch inputs
+        at position ctx - 1 (see :meth:`_decode_graph`); the shared per-B state is left alone."""
+        dev = self.device
+        tok = torch.zeros(B, 1, dtype=torch.int32, device=dev)
+        pos = torch.full((B, 1), ctx - 1, dtype=torch.int32, device=dev)
+        lens = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+
+        def warm():
+            self._gather_dev(*self.step(tok, pos, lens, decode=True, k=k))
+
+        return warm
+
     def _decode_graph(self, B: int, k: int, ctx: int):
         """Captured decode step for batch B and context bound ctx (static token / position / length
         buffers).  The warm-up steps run at position ctx - 1: for a sequence being decoded under
@@ -1340,20 +1428,11 @@ class LlamaTP:
         tok = torch.zeros(B, 1, dtype=torch.int32, device=dev)
         pos = torch.full((B, 1), ctx - 1, dtype=torch.int32, device=dev)
         lens = torch.full((B,), ctx, dtype=torch.int32, device=dev)
-        self._dec_ctx = ctx
-        try:
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self.step(tok, pos, lens, decode=True, k=k)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            # thread_local: the RCCL watchdog thread polls its events while this thread captures
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                vals, idx = self.step(tok, pos, lens, decode=True, k=k)
-        finally:
-            self._dec_ctx = None
+
+        def run():
+            return self.step(tok, pos, lens, decode=True, k=k)
+
+        g, (vals, idx) = self._capture(ctx, run, run)
         self._graphs[key] = (g, tok, pos, lens, vals, idx)
         return self._graphs[key]
 
@@ -1549,30 +1628,14 @@ class LlamaTP:
         g = self._dev_graphs.get(key)
         if g is not None:
             return g
-        dev = self.device
         tok, pos, lens, step, topk, temp, seed, hist = self._dev_buffers(B)
-        # warm-up (kernel selection, workspaces) on scratch inputs at position ctx - 1: that cache row
-        # is either the one a replay under this bound writes anyway or a future row rewritten before
-        # it is read (see _decode_graph); the shared state is left alone
-        t_w = torch.zeros(B, 1, dtype=torch.int32, device=dev)
-        p_w = torch.full((B, 1), ctx - 1, dtype=torch.int32, device=dev)
-        l_w = torch.full((B,), ctx, dtype=torch.int32, device=dev)
-        self._dec_ctx = ctx
-        try:
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    v, i = self.step(t_w, p_w, l_w, decode=True, k=k)
-                    self._gather_dev(v, i)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                v, i = self.step(tok.view(B, 1), pos.view(B, 1), lens, decode=True, k=k)
-                cv, ci = self._gather_dev(v, i)
-                self.ops.decode_pick(cv, ci, tok, pos, lens, step, topk=topk, temp=temp, seed=seed, hist=hist)
-        finally:
-            self._dec_ctx = None
+
+        def body():
+            v, i = self.step(tok.view(B, 1), pos.view(B, 1), lens, decode=True, k=k)
+            cv, ci = self._gather_dev(v, i)
+            self.ops.decode_pick(cv, ci, tok, pos, lens, step, topk=topk, temp=temp, seed=seed, hist=hist)
+
+        g, _ = self._capture(ctx, self._warm_decode(B, k, ctx), body)
         self._dev_graphs[key] = g
         return g
 
@@ -1608,33 +1671,19 @@ class LlamaTP:
         g = self._dev_graphs.get(key)
         if g is not None:
             return g
-        dev = self.device
         st = self.serve_state(B)
-        # warm-up on scratch inputs at position ctx - 1 (see _decode_graph): the shared state is not touched
-        t_w = torch.zeros(B, 1, dtype=torch.int32, device=dev)
-        p_w = torch.full((B, 1), ctx - 1, dtype=torch.int32, device=dev)
-        l_w = torch.full((B,), ctx, dtype=torch.int32, device=dev)
-        self._dec_ctx = ctx
-        try:
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    v, i = self.step(t_w, p_w, l_w, decode=True, k=k)
-                    self._gather_dev(v, i)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                v, i = self.step(st["tok"].view(B, 1), st["pos"].view(B, 1), st["lens"], decode=True, k=k)
-                cv, ci, c0 = self._gather_dev(v, i, ctl=st["ctl_in"])
-                st["ctl_out"].copy_(c0)
-                car = getattr(self.comm, "car", None)
-                if car is not None:  # did a peer wait of this step (or an earlier one) time out?
-                    car.error_peek(st["err_out"])
-                self.ops.decode_pick(cv, ci, st["tok"], st["pos"], st["lens"], st["step"], topk=st["topk"],
-                                     temp=st["temp"], seed=st["seed"], active=st["active"])
-        finally:
-            self._dec_ctx = None
+
+        def body():
+            v, i = self.step(st["tok"].view(B, 1), st["pos"].view(B, 1), st["lens"], decode=True, k=k)
+            cv, ci, c0 = self._gather_dev(v, i, ctl=st["ctl_in"])
+            st["ctl_out"].copy_(c0)
+            car = getattr(self.comm, "car", None)
+            if car is not None:  # did a peer wait of this step (or an earlier one) time out?
+                car.error_peek(st["err_out"])
+            self.ops.decode_pick(cv, ci, st["tok"], st["pos"], st["lens"], st["step"], topk=st["topk"],
+                                 temp=st["temp"], seed=st["seed"], active=st["active"])
+
+        g, _ = self._capture(ctx, self._warm_decode(B, k, ctx), body)
         self._dev_graphs[key] = g
         return g
 

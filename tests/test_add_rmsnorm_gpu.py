@@ -66,7 +66,7 @@ def test_llama_forward_fused_equals_unfused():
         tok = i[:, 0].view(B, 1)
         v2, i2 = m.step(tok, lens.view(B, 1), lens + 1, decode=True, k=4)
         torch.cuda.synchronize()
-        outs.append((v, i, v2, i2, getattr(m, "add_norm_fused", 0)))
+        outs.append((v, i, v2, i2, m.add_norm_fused))
         del m
     (fv, fi, fv2, fi2, nf), (uv, ui, uv2, ui2, nu) = outs
     assert nf > 0 and nu == 0
