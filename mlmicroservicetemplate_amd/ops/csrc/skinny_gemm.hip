@@ -15,11 +15,8 @@
 // (a + a2) through registers for the MFMA, so the sum of squares costs nothing extra; blocks of
 // column tile 0 also write the updated residual stream a + a2 to a_out (a separate buffer: other
 // blocks still read a).  This removes the standalone RMSNorm launch (2 per layer) from decode.
-#include <type_traits>
-
-#include "common.h"
+#include "skinny_tiles.h"
 #include "ar_protocol.h"
-#include "fastdiv.h"
 
 namespace {
 
@@ -28,12 +25,12 @@ struct SkArgs {
   const bf16* a2;  // optional [M][lda] added to a (residual-stream update)
   bf16* a_out;     // optional [M][lda] <- a + a2 (written by column-tile-0 blocks)
   const bf16* w;   // [N][K]
-  const float* bias;
-  const bf16* res;  // [M][N]
-  bf16* out;        // [M][ldo]
-  float* ws;        // [nsplit][M][N]
-  int M, N, K, lda, ldo, act, nsplit, ksteps_per_split, norm;
-  float eps;
+  float* ws;       // [nsplit][M][N]
+  // bias, res, out, M, N, K, ldo, act, eps.  Behind ws, so that M, N, K and a_bytes, w_bytes keep the
+  // offsets they had as plain fields: with `e` in front of ws the row-major LDS kernel measured 0.1 us
+  // slower at one row with its own staging and epilogue text unchanged (docs/PERF_NOTES.md)
+  SkEpi e;
+  int lda, nsplit, ksteps_per_split, norm;
   uint32_t a_bytes, w_bytes;
   // FUSE_COMBINE (packed LDS kernel): A = the split-KV decode attention's merged output, combined
   // here from its fp32 partials (o [M][Hq][nsplit][D], (m, l) [M][Hq][nsplit][2]); rows whose
@@ -50,30 +47,6 @@ struct SkArgs {
   FastDiv fd_kch, fd_hd;
 };
 
-// fusion modes of the A prologue (template parameter, so the unrolled k loop has no runtime
-// branches -- a branch there makes hipcc drain vmcnt(0) per k-step, cdna_hip_programming.md item 4c)
-enum { FUSE_NONE = 0, FUSE_NORM = 1, FUSE_ADD_NORM = 2, FUSE_COMBINE = 3 };
-
-MLS_DEV uint4 add_round(uint4 a, uint4 b) {  // bf16 + bf16 -> bf16 (the residual stream's precision)
-  float x[8], y[8];
-  unpack8(a, x);
-  unpack8(b, y);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) x[e] += y[e];
-  return pack8(x);
-}
-
-MLS_DEV float sumsq8(uint4 v) {
-  float x[8];
-  unpack8(v, x);
-  float r = 0.f;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) r += x[e] * x[e];
-  return r;
-}
-
-MLS_DEV float epi(float v, int n, const SkArgs& s) { return v + (s.bias ? s.bias[n] : 0.f); }
-
 // NT 16-column tiles per block: every A fragment a wave loads feeds NT MFMAs, so the activation
 // traffic from L2 (M rows x K per block) is amortised over NT weight tiles -- at M = 16 it equals
 // the weight traffic when NT = 1.
@@ -86,7 +59,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_gemm_kernel(const SkArgs s) {
   const int n0 = blockIdx.x * 16 * NT;
   const int split = blockIdx.y;
   const int ks_beg = split * s.ksteps_per_split;
-  const int ksteps = (s.K + 31) / 32;
+  const int ksteps = (s.e.K + 31) / 32;
   const int ks_end = min(ksteps, ks_beg + s.ksteps_per_split);
   const rsrc_t ar = make_rsrc(s.a, s.a_bytes);
   const rsrc_t wr = make_rsrc(s.w, s.w_bytes);
@@ -94,12 +67,12 @@ __global__ __launch_bounds__(NWV * 64) void skinny_gemm_kernel(const SkArgs s) {
   const bool wr_res = FUSE == FUSE_ADD_NORM && s.a_out && blockIdx.x == 0;
   int wbase[NT];
 #pragma unroll
-  for (int j = 0; j < NT; ++j) wbase[j] = ((n0 + 16 * j + nr) * s.K + 8 * g) * 2;
+  for (int j = 0; j < NT; ++j) wbase[j] = ((n0 + 16 * j + nr) * s.e.K + 8 * g) * 2;
   int abase[TMS];
 #pragma unroll
   for (int t = 0; t < TMS; ++t) {
     const int m = 16 * t + nr;
-    abase[t] = m < s.M ? (m * s.lda + 8 * g) * 2 : OOB;
+    abase[t] = m < s.e.M ? (m * s.lda + 8 * g) * 2 : OOB;
   }
   f32x4 acc[TMS][NT];
   float ssq[TMS];
@@ -119,7 +92,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_gemm_kernel(const SkArgs s) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int k = (ks0 + NWV * u) * 32;
-      const bool kin = k + 8 * g < s.K;
+      const bool kin = k + 8 * g < s.e.K;
 #pragma unroll
       for (int j = 0; j < NT; ++j) wv[u][j] = bload16(wr, kin ? wbase[j] + k * 2 : OOB);
 #pragma unroll
@@ -172,46 +145,28 @@ __global__ __launch_bounds__(NWV * 64) void skinny_gemm_kernel(const SkArgs s) {
     }
   }
   __syncthreads();
-  const bool glu = s.act == ACT_SILU_MUL;
   constexpr int COLS = NT * 16;
-  for (int q = tid; q < TMS * 16 * COLS; q += NWV * 64) {
-    const int m = q / COLS, c = q % COLS;
-    if (m >= s.M) continue;
-    float v = 0.f;
+  if (s.nsplit > 1) {  // fp32 slabs for skinny_finish_kernel; the partial square sums ride after them
+    for (int q = tid; q < TMS * 16 * COLS; q += NWV * 64) {
+      const int m = q / COLS, c = q % COLS;
+      if (m >= s.e.M) continue;
+      float v = 0.f;
 #pragma unroll
-    for (int w = 0; w < NWV; ++w) v += red[w][m][c];
-    const int n = n0 + c;
-    float rs = 1.f;
-    if constexpr (FUSE != FUSE_NONE) {
-      float t2 = 0.f;
+      for (int w = 0; w < NWV; ++w) v += red[w][m][c];
+      s.ws[((size_t)split * s.e.M + m) * s.e.N + n0 + c] = v;
+      if constexpr (FUSE != FUSE_NONE) {
+        if (blockIdx.x == 0 && c == 0) {
+          float t2 = 0.f;
 #pragma unroll
-      for (int w = 0; w < NWV; ++w) t2 += ssq_red[w][m];
-      if (s.nsplit > 1) {  // partial square sums ride after the slabs; the finisher combines them
-        if (blockIdx.x == 0 && c == 0) s.ws[(size_t)s.nsplit * s.M * s.N + split * s.M + m] = t2;
-      } else {
-        rs = rsqrtf(t2 / (float)s.K + s.eps);
+          for (int w = 0; w < NWV; ++w) t2 += ssq_red[w][m];
+          s.ws[(size_t)s.nsplit * s.e.M * s.e.N + split * s.e.M + m] = t2;
+        }
       }
     }
-    if (s.nsplit > 1) {
-      s.ws[((size_t)split * s.M + m) * s.N + n] = v;
-      continue;
-    }
-    v *= rs;
-    if (glu) {
-      if ((c & 15) < 8) {
-        float up = 0.f;
-#pragma unroll
-        for (int w = 0; w < NWV; ++w) up += red[w][m][c + 8];
-        up *= rs;
-        const float gt = epi(v, n, s);
-        s.out[(size_t)m * s.ldo + (n >> 4) * 8 + (n & 7)] = (bf16)(silu(gt) * epi(up, n + 8, s));
-      }
-      continue;
-    }
-    float o = epi(v, n, s);
-    if (s.res) o += (float)s.res[(size_t)m * s.N + n];
-    s.out[(size_t)m * s.ldo + n] = (bf16)apply_act(o, s.act);
+    return;
   }
+  sk_reduce_store<NWV, TMS * 16, COLS, true>(red, s.e, n0,
+                                             [&](int m) { return FUSE != FUSE_NONE ? sk_rstd(ssq_red, m, s.e) : 1.f; });
 }
 
 // Few-row variant (M <= 4, whole K per block): the activation rows -- with the fused prologue,
@@ -229,12 +184,12 @@ __global__ __launch_bounds__(NWV * 64) void skinny_lds_kernel(const SkArgs s) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nr = lane & 15, g = lane >> 4;
   const int n0 = blockIdx.x * 16 * NT;
-  const int ksteps = s.K >> 5;
-  const int kch = s.K >> 3;  // 16-B chunks per row
+  const int ksteps = s.e.K >> 5;
+  const int kch = s.e.K >> 3;  // 16-B chunks per row
   const rsrc_t wr = make_rsrc(s.w, s.w_bytes);
   int wbase[NT];
 #pragma unroll
-  for (int j = 0; j < NT; ++j) wbase[j] = ((n0 + 16 * j + nr) * s.K + 8 * g) * 2;
+  for (int j = 0; j < NT; ++j) wbase[j] = ((n0 + 16 * j + nr) * s.e.K + 8 * g) * 2;
 
   auto load_trip = [&](int ks0, uint4 (&wv)[UNROLL][NT]) {
 #pragma unroll
@@ -254,64 +209,9 @@ __global__ __launch_bounds__(NWV * 64) void skinny_lds_kernel(const SkArgs s) {
   __syncthreads();
   float part[4] = {0.f, 0.f, 0.f, 0.f};
   const bool wr_res = FUSE == FUSE_ADD_NORM && s.a_out && blockIdx.x == 0;
-  int lens4[4] = {0, 0, 0, 0};
-  if constexpr (FUSE == FUSE_COMBINE) {
-    // block-uniform reads (scalar loads): they do not queue behind the weight loads in flight
-#pragma unroll
-    for (int mm = 0; mm < 4; ++mm) lens4[mm] = mm < s.M ? __builtin_nontemporal_load(s.lens + mm) : 0;
-  }
-  for (int q = tid; q < s.M * kch; q += NWV * 64) {
+  for (int q = tid; q < s.e.M * kch; q += NWV * 64) {
     const int m = fastdiv(q, s.fd_kch), c = q - m * kch;
-    uint4 v;
-    if constexpr (FUSE == FUSE_COMBINE) {
-      // the decode_combine_kernel arithmetic for this row's 8 dims of one head
-      const int h = fastdiv(c * 8, s.fd_hd), d0 = c * 8 - h * s.c_hd;
-      const int L = m == 0 ? lens4[0] : m == 1 ? lens4[1] : m == 2 ? lens4[2] : lens4[3];
-      const int ns = min(s.c_nsplit, (L + s.c_chunk - 1) / s.c_chunk);
-      if (ns <= 1) {
-        v = ld16(s.a + (size_t)m * s.lda + c * 8);
-      } else {
-        const long rec = ((long)m * s.c_hq + h) * s.c_nsplit;
-        // online merge in groups of 4 splits: each group's (m, l, o) loads are issued together
-        // (one memory round trip per group, not two per split)
-        float mx = -INFINITY, l = 0.f, o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        for (int s0 = 0; s0 < ns; s0 += 4) {
-          float2 ml[4];
-          float4 x0[4], x1[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const bool in = s0 + j < ns;
-            const long r = rec + (in ? s0 + j : 0);
-            ml[j] = in ? *reinterpret_cast<const float2*>(s.cml + r * 2) : make_float2(-INFINITY, 0.f);
-            x0[j] = in ? *reinterpret_cast<const float4*>(s.cws + r * s.c_hd + d0) : make_float4(0.f, 0.f, 0.f, 0.f);
-            x1[j] = in ? *reinterpret_cast<const float4*>(s.cws + r * s.c_hd + d0 + 4)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
-          }
-          float gm = mx;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) gm = fmaxf(gm, ml[j].x);
-          if (gm == -INFINITY) continue;
-          const float al = __builtin_amdgcn_exp2f(mx - gm);
-          l *= al;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] *= al;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float w = __builtin_amdgcn_exp2f(ml[j].x - gm);
-            l += ml[j].y * w;
-            o[0] += x0[j].x * w; o[1] += x0[j].y * w; o[2] += x0[j].z * w; o[3] += x0[j].w * w;
-            o[4] += x1[j].x * w; o[5] += x1[j].y * w; o[6] += x1[j].z * w; o[7] += x1[j].w * w;
-          }
-          mx = gm;
-        }
-        const float inv = l > 0.f ? 1.f / l : 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] *= inv;
-        v = pack8(o);
-      }
-    } else {
-      v = ld16(s.a + (size_t)m * s.lda + c * 8);
-    }
+    uint4 v = ld16(s.a + (size_t)m * s.lda + c * 8);
     if constexpr (FUSE == FUSE_ADD_NORM) {
       v = add_round(v, ld16(s.a2 + (size_t)m * s.lda + c * 8));
       if (wr_res) st16(s.a_out + (size_t)m * s.lda + c * 8, v);
@@ -327,7 +227,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_lds_kernel(const SkArgs s) {
 #pragma unroll
     for (int mm = 0; mm < 4; ++mm) {
       const float t = wave_sum(part[mm]);
-      if (lane == 0 && mm < s.M) atomicAdd(&ssq_s[mm], t);
+      if (lane == 0 && mm < s.e.M) atomicAdd(&ssq_s[mm], t);
     }
   }
   __syncthreads();
@@ -335,7 +235,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_lds_kernel(const SkArgs s) {
   f32x4 acc[NT];
 #pragma unroll
   for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const bool arow = nr < s.M;
+  const bool arow = nr < s.e.M;
   for (; ks < ksteps; ks += NWV * UNROLL) {
     uint4 wv[UNROLL][NT];
 #pragma unroll
@@ -359,30 +259,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_lds_kernel(const SkArgs s) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) red[wid][4 * g + i][16 * j + nr] = acc[j][i];
   __syncthreads();
-  const bool glu = s.act == ACT_SILU_MUL;
-  constexpr int COLS = NT * 16;
-  for (int q = tid; q < s.M * COLS; q += NWV * 64) {
-    const int m = q / COLS, c = q % COLS;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < NWV; ++w) v += red[w][m][c];
-    const float rs = FUSE != FUSE_NONE ? rsqrtf(ssq_s[m] / (float)s.K + s.eps) : 1.f;
-    const int n = n0 + c;
-    v *= rs;
-    if (glu) {
-      if ((c & 15) < 8) {
-        float up = 0.f;
-#pragma unroll
-        for (int w = 0; w < NWV; ++w) up += red[w][m][c + 8];
-        up *= rs;
-        s.out[(size_t)m * s.ldo + (n >> 4) * 8 + (n & 7)] = (bf16)(silu(epi(v, n, s)) * epi(up, n + 8, s));
-      }
-      continue;
-    }
-    float o = epi(v, n, s);
-    if (s.res) o += (float)s.res[(size_t)m * s.N + n];
-    s.out[(size_t)m * s.ldo + n] = (bf16)apply_act(o, s.act);
-  }
+  sk_reduce_store<NWV, 16, NT * 16>(red, s.e, n0, [&](int m) { return NORM ? sk_rstd(ssq_s[m], s.e) : 1.f; });
 }
 
 // Packed-weight variant of skinny_lds_kernel (M <= 4).  W is re-laid out once at load time
@@ -392,11 +269,6 @@ __global__ __launch_bounds__(NWV * 64) void skinny_lds_kernel(const SkArgs s) {
 // consecutive bytes and consecutive instructions continue the same run -- instead of 16 rows x
 // 64 B scattered K*2 bytes apart per instruction in the row-major layout.  NTL: non-temporal
 // cache policy on the weight stream (read exactly once per call).
-template <int NTL>
-MLS_DEV uint4 bload16_pol(rsrc_t r, int byte_off) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, NTL ? 2 : 0));
-}
-
 template <int UNROLL, int NWV, int FUSE, int NTL>
 __global__ __launch_bounds__(NWV * 64) void skinny_packed_kernel(const SkArgs s) {
   extern __shared__ __attribute__((aligned(16))) uint4 a_lds[];  // [M][K/8]
@@ -407,9 +279,8 @@ __global__ __launch_bounds__(NWV * 64) void skinny_packed_kernel(const SkArgs s)
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nr = lane & 15, g = lane >> 4;
   const int n0 = blockIdx.x * 16;
-  const int ksteps = s.K >> 5;
-  const int kch = s.K >> 3;
-  const int nq = s.M * kch;
+  const int ksteps = s.e.K >> 5;
+  const int kch = s.e.K >> 3;
   const int kpw = (ksteps + NWV - 1) / NWV;
   const int kb = wid * kpw, ke = min(ksteps, kb + kpw);
   const rsrc_t wr = make_rsrc(s.w, s.w_bytes);
@@ -421,6 +292,10 @@ __global__ __launch_bounds__(NWV * 64) void skinny_packed_kernel(const SkArgs s)
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) wv[u] = bload16_pol<NTL>(wr, ks0 + u < ke ? wbase + (ks0 + u) * 1024 : OOB);
   };
+  const int nq = s.e.M * kch;
+  // The staging below (early loads, stage step, tail loop) is repeated in skinny_fp8_kernel and
+  // skinny_w4_kernel<ALDS>: shared as a closure it cost each of the three 0.05-0.1 us per launch
+  // (docs/PERF_NOTES.md, "csrc/skinny_tiles.h"), so a fix to one has to be made in the others.
   // The first QPT A (+ A2) chunks per thread -- all of A up to 2048 chunks, e.g. 4 rows at K = 4096
   // -- are loaded BEFORE the first weight trip: the vector memory counter retires in order, so
   // consuming them then does not wait for the weights, and the barriers below are LDS-only (a
@@ -447,7 +322,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_packed_kernel(const SkArgs s)
   if constexpr (FUSE == FUSE_COMBINE) {
     // block-uniform reads (scalar loads): they do not queue behind the weight loads in flight
 #pragma unroll
-    for (int mm = 0; mm < 4; ++mm) lens4[mm] = mm < s.M ? __builtin_nontemporal_load(s.lens + mm) : 0;
+    for (int mm = 0; mm < 4; ++mm) lens4[mm] = mm < s.e.M ? __builtin_nontemporal_load(s.lens + mm) : 0;
   }
   auto stage = [&](int q, uint4 v, uint4 v2) {
     const int m = fastdiv(q, s.fd_kch), c = q - m * kch;
@@ -456,44 +331,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_packed_kernel(const SkArgs s)
       const int h = fastdiv(c * 8, s.fd_hd), d0 = c * 8 - h * s.c_hd;
       const int L = m == 0 ? lens4[0] : m == 1 ? lens4[1] : m == 2 ? lens4[2] : lens4[3];
       const int ns = min(s.c_nsplit, (L + s.c_chunk - 1) / s.c_chunk);
-      if (ns > 1) {
-        const long rec = ((long)m * s.c_hq + h) * s.c_nsplit;
-        // online merge in groups of 4 splits: each group's (m, l, o) loads are issued together
-        float mx = -INFINITY, l = 0.f, o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        for (int s0 = 0; s0 < ns; s0 += 4) {
-          float2 ml[4];
-          float4 x0[4], x1[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const bool in = s0 + j < ns;
-            const long r = rec + (in ? s0 + j : 0);
-            ml[j] = in ? *reinterpret_cast<const float2*>(s.cml + r * 2) : make_float2(-INFINITY, 0.f);
-            x0[j] = in ? *reinterpret_cast<const float4*>(s.cws + r * s.c_hd + d0) : make_float4(0.f, 0.f, 0.f, 0.f);
-            x1[j] = in ? *reinterpret_cast<const float4*>(s.cws + r * s.c_hd + d0 + 4)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
-          }
-          float gm = mx;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) gm = fmaxf(gm, ml[j].x);
-          if (gm == -INFINITY) continue;
-          const float al = __builtin_amdgcn_exp2f(mx - gm);
-          l *= al;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] *= al;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float w = __builtin_amdgcn_exp2f(ml[j].x - gm);
-            l += ml[j].y * w;
-            o[0] += x0[j].x * w; o[1] += x0[j].y * w; o[2] += x0[j].z * w; o[3] += x0[j].w * w;
-            o[4] += x1[j].x * w; o[5] += x1[j].y * w; o[6] += x1[j].z * w; o[7] += x1[j].w * w;
-          }
-          mx = gm;
-        }
-        const float inv = l > 0.f ? 1.f / l : 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] *= inv;
-        v = pack8(o);
-      }
+      if (ns > 1) v = splitkv_merge(m, h, d0, ns, s.cws, s.cml, s.c_hq, s.c_nsplit, s.c_hd);
     }
     if constexpr (FUSE == FUSE_ADD_NORM) {
       v = add_round(v, v2);
@@ -518,14 +356,14 @@ __global__ __launch_bounds__(NWV * 64) void skinny_packed_kernel(const SkArgs s)
 #pragma unroll
     for (int mm = 0; mm < 4; ++mm) {
       const float t = wave_sum(part[mm]);
-      if (lane == 0 && mm < s.M) atomicAdd(&ssq_s[mm], t);
+      if (lane == 0 && mm < s.e.M) atomicAdd(&ssq_s[mm], t);
     }
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
   f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-  const bool arow = nr < s.M;
+  const bool arow = nr < s.e.M;
   for (int ks = kb; ks < ke; ks += UNROLL) {
     uint4 wv[UNROLL];
 #pragma unroll
@@ -542,30 +380,8 @@ __global__ __launch_bounds__(NWV * 64) void skinny_packed_kernel(const SkArgs s)
 #pragma unroll
   for (int i = 0; i < 4; ++i) red[wid][4 * g + i][nr] = acc[i];
   __syncthreads();
-  const bool glu = s.act == ACT_SILU_MUL;
-  for (int q = tid; q < s.M * 16; q += NWV * 64) {
-    const int m = q >> 4, c = q & 15;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < NWV; ++w) v += red[w][m][c];
-    const float rs = NORM ? rsqrtf(ssq_s[m] / (float)s.K + s.eps) : 1.f;
-    const int n = n0 + c;
-    v *= rs;
-    if (glu) {
-      if (c < 8) {
-        float up = 0.f;
-#pragma unroll
-        for (int w = 0; w < NWV; ++w) up += red[w][m][c + 8];
-        up *= rs;
-        s.out[(size_t)m * s.ldo + (n >> 4) * 8 + (n & 7)] = (bf16)(silu(epi(v, n, s)) * epi(up, n + 8, s));
-      }
-      continue;
-    }
-    float o = epi(v, n, s);
-    if (s.res) o += (float)s.res[(size_t)m * s.N + n];
-    s.out[(size_t)m * s.ldo + n] = (bf16)apply_act(o, s.act);
-  }
-  if (s.arf.world) ar_fused_tail(s.arf, s.out, s.M, s.N, n0, 16);
+  sk_reduce_store<NWV, 16, 16>(red, s.e, n0, [&](int m) { return NORM ? sk_rstd(ssq_s[m], s.e) : 1.f; });
+  if (s.arf.world) ar_fused_tail(s.arf, s.e.out, s.e.M, s.e.N, n0, 16);
 }
 
 // Packed weights, M <= 16 (or A too large for LDS): the A fragments (+ A2) ride beside the weight
@@ -579,7 +395,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_packed_reg_kernel(const SkArg
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nr = lane & 15, g = lane >> 4;
   const int n0 = blockIdx.x * 16 * NT;
-  const int ksteps = s.K >> 5;
+  const int ksteps = s.e.K >> 5;
   const int kpw = (ksteps + NWV - 1) / NWV;
   const int kb = wid * kpw, ke = min(ksteps, kb + kpw);
   const rsrc_t wr = make_rsrc(s.w, s.w_bytes);
@@ -588,7 +404,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_packed_reg_kernel(const SkArg
   const int wbase = blockIdx.x * NT * ksteps * 1024 + lane * 16;  // tile j: + j * ksteps * 1024
   int abase[TMS];
 #pragma unroll
-  for (int t = 0; t < TMS; ++t) abase[t] = 16 * t + nr < s.M ? ((16 * t + nr) * s.lda + 8 * g) * 2 : OOB;
+  for (int t = 0; t < TMS; ++t) abase[t] = 16 * t + nr < s.e.M ? ((16 * t + nr) * s.lda + 8 * g) * 2 : OOB;
   const bool wr_res = FUSE == FUSE_ADD_NORM && s.a_out && blockIdx.x == 0;
 
   struct Trip {
@@ -655,36 +471,10 @@ __global__ __launch_bounds__(NWV * 64) void skinny_packed_reg_kernel(const SkArg
     }
   }
   __syncthreads();
-  const bool glu = s.act == ACT_SILU_MUL;
   constexpr int COLS = NT * 16;
-  for (int q = tid; q < s.M * COLS; q += NWV * 64) {
-    const int m = q / COLS, c = q % COLS;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < NWV; ++w) v += red[w][m][c];
-    float rs = 1.f;
-    if constexpr (FUSE != FUSE_NONE) {
-      float t2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < NWV; ++w) t2 += ssq_red[w][m];
-      rs = rsqrtf(t2 / (float)s.K + s.eps);
-    }
-    const int n = n0 + c;
-    v *= rs;
-    if (glu) {
-      if ((c & 15) < 8) {
-        float up = 0.f;
-#pragma unroll
-        for (int w = 0; w < NWV; ++w) up += red[w][m][c + 8];
-        up *= rs;
-        s.out[(size_t)m * s.ldo + (n >> 4) * 8 + (n & 7)] = (bf16)(silu(epi(v, n, s)) * epi(up, n + 8, s));
-      }
-      continue;
-    }
-    float o = epi(v, n, s);
-    if (s.res) o += (float)s.res[(size_t)m * s.N + n];
-    s.out[(size_t)m * s.ldo + n] = (bf16)apply_act(o, s.act);
-  }  if (s.arf.world) ar_fused_tail(s.arf, s.out, s.M, s.N, n0, COLS);
+  sk_reduce_store<NWV, 16 * TMS, COLS>(red, s.e, n0,
+                                       [&](int m) { return FUSE != FUSE_NONE ? sk_rstd(ssq_red, m, s.e) : 1.f; });
+  if (s.arf.world) ar_fused_tail(s.arf, s.e.out, s.e.M, s.e.N, n0, COLS);
 }
 
 
@@ -705,9 +495,9 @@ __global__ __launch_bounds__(NWV * 64) void skinny_fp8_kernel(const SkArgs s) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nr = lane & 15, g = lane >> 4;
   const int n0 = blockIdx.x * 16;
-  const int kgs = s.K >> 6;  // 64-wide granules per row
-  const int kch = s.K >> 3;
-  const int nq = s.M * kch;
+  const int kgs = s.e.K >> 6;  // 64-wide granules per row
+  const int kch = s.e.K >> 3;
+  const int nq = s.e.M * kch;
   const int kpw = (kgs + NWV - 1) / NWV;
   const int kb = wid * kpw, ke = min(kgs, kb + kpw);
   const rsrc_t wr = make_rsrc(s.w, s.w_bytes);
@@ -773,7 +563,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_fp8_kernel(const SkArgs s) {
   for (int mm = 0; mm < 4; ++mm) {
     const float t = wave_sum(part[mm]);
     const float mxw = wave_max(amx[mm]);
-    if (lane == 0 && mm < s.M) {
+    if (lane == 0 && mm < s.e.M) {
       if constexpr (NORM) atomicAdd(&ssq_s[mm], t);
       atomicMax(&amax_s[mm], __float_as_int(mxw));  // non-negative floats order as their bits
     }
@@ -816,8 +606,8 @@ __global__ __launch_bounds__(NWV * 64) void skinny_fp8_kernel(const SkArgs s) {
   __builtin_amdgcn_s_barrier();
 
   f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-  const bool arow = nr < s.M;
-  const char* a8b = reinterpret_cast<const char*>(a_lds) + nr * s.K + 8 * g;
+  const bool arow = nr < s.e.M;
+  const char* a8b = reinterpret_cast<const char*>(a_lds) + nr * s.e.K + 8 * g;
   for (int kg = kb; kg < ke; kg += UNROLL) {
     uint4 wv[UNROLL];
 #pragma unroll
@@ -838,30 +628,11 @@ __global__ __launch_bounds__(NWV * 64) void skinny_fp8_kernel(const SkArgs s) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) red[wid][4 * g + i][nr] = acc[i];
   __syncthreads();
-  const bool glu = s.act == ACT_SILU_MUL;
-  for (int q = tid; q < s.M * 16; q += T) {
-    const int m = q >> 4, c = q & 15;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < NWV; ++w) v += red[w][m][c];
-    const float sa = __int_as_float(amax_s[m]) * (1.f / 448.f);
-    const float rs = (NORM ? rsqrtf(ssq_s[m] / (float)s.K + s.eps) : 1.f) * sa;
-    const int n = n0 + c;
-    v *= rs * s.wscale[n];
-    if (glu) {
-      if (c < 8) {
-        float up = 0.f;
-#pragma unroll
-        for (int w = 0; w < NWV; ++w) up += red[w][m][c + 8];
-        up *= rs * s.wscale[n + 8];
-        s.out[(size_t)m * s.ldo + (n >> 4) * 8 + (n & 7)] = (bf16)(silu(epi(v, n, s)) * epi(up, n + 8, s));
-      }
-      continue;
-    }
-    float o = epi(v, n, s);
-    if (s.res) o += (float)s.res[(size_t)m * s.N + n];
-    s.out[(size_t)m * s.ldo + n] = (bf16)apply_act(o, s.act);
-  }
+  // acc * s_a[m] * s_w[n] (* rstd[m])
+  sk_reduce_store<NWV, 16, 16>(
+      red, s.e, n0,
+      [&](int m) { return (NORM ? sk_rstd(ssq_s[m], s.e) : 1.f) * (__int_as_float(amax_s[m]) * (1.f / 448.f)); },
+      [&](int n) { return s.wscale[n]; });
 }
 
 // [N][K] row-major -> [N/16][K/32][4][16][8] (the packed granule layout above)
@@ -879,33 +650,87 @@ __global__ __launch_bounds__(256) void pack_skinny_kernel(const bf16* __restrict
 }
 
 __global__ __launch_bounds__(256) void skinny_finish_kernel(const SkArgs s) {
-  const bool glu = s.act == ACT_SILU_MUL;
-  const int ncols = glu ? s.N / 2 : s.N;
-  const long total = (long)s.M * ncols;
+  const bool glu = s.e.act == ACT_SILU_MUL;
+  const int ncols = glu ? s.e.N / 2 : s.e.N;
+  const long total = (long)s.e.M * ncols;
   for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
     const int m = (int)(q / ncols), c = (int)(q % ncols);
     const int n = glu ? (c / 8) * 16 + (c % 8) : c;
     float v = 0.f, u = 0.f;
     for (int sp = 0; sp < s.nsplit; ++sp) {
-      const float* row = s.ws + ((size_t)sp * s.M + m) * s.N;
+      const float* row = s.ws + ((size_t)sp * s.e.M + m) * s.e.N;
       v += row[n];
       if (glu) u += row[n + 8];
     }
     if (s.norm) {
       float t2 = 0.f;
-      for (int sp = 0; sp < s.nsplit; ++sp) t2 += s.ws[(size_t)s.nsplit * s.M * s.N + sp * s.M + m];
-      const float rs = rsqrtf(t2 / (float)s.K + s.eps);
+      for (int sp = 0; sp < s.nsplit; ++sp) t2 += s.ws[(size_t)s.nsplit * s.e.M * s.e.N + sp * s.e.M + m];
+      const float rs = sk_rstd(t2, s.e);
       v *= rs;
       u *= rs;
     }
-    if (glu) {
-      s.out[(size_t)m * s.ldo + c] = (bf16)(silu(epi(v, n, s)) * epi(u, n + 8, s));
-    } else {
-      float o = epi(v, n, s);
-      if (s.res) o += (float)s.res[(size_t)m * s.N + n];
-      s.out[(size_t)m * s.ldo + n] = (bf16)apply_act(o, s.act);
-    }
+    sk_emit(s.e, glu, m, n, v, u);
   }
+}
+
+// what every launcher fills: A (+ A2, A_out) [M][K], the weights (wb bytes), the epilogue, no K split
+SkArgs sk_args(const void* A, const void* A2, void* A_out, const void* W, size_t wb, const float* bias, const void* res,
+               void* out, int M, int N, int K, int act, int norm, float eps, const ArFuse* arf = nullptr) {
+  SkArgs s{};
+  s.e = sk_epi(bias, res, out, M, N, K, act, eps);
+  s.a = (const bf16*)A;
+  s.a2 = (const bf16*)A2;
+  s.a_out = (bf16*)A_out;
+  s.w = (const bf16*)W;
+  s.lda = K;
+  s.nsplit = 1;
+  s.norm = norm;
+  s.a_bytes = (uint32_t)((size_t)M * K * 2);
+  s.w_bytes = (uint32_t)wb;
+  s.fd_kch = fastdiv_make((uint32_t)(K >> 3));
+  if (arf) s.arf = *arf;
+  return s;
+}
+
+// one launch per kernel family: the shape from the caller, the fusion mode at run time (with_fuse)
+template <int TMS, int UN, int NT>
+void launch_gemm(const SkArgs& s, int mode, dim3 grid, hipStream_t st) {
+  with_fuse(mode, [&](auto F) {
+    hipLaunchKernelGGL((skinny_gemm_kernel<TMS, UN, 8, decltype(F)::value, NT>), grid, dim3(512), 0, st, s);
+  });
+}
+template <int TMS, int UN>
+void launch_gemm_nt(const SkArgs& s, int mode, int nt, dim3 grid, hipStream_t st) {
+  if (nt == 4) launch_gemm<TMS, (UN > 4 ? 4 : UN), 4>(s, mode, grid, st);
+  else if (nt == 2) launch_gemm<TMS, UN, 2>(s, mode, grid, st);
+  else launch_gemm<TMS, UN, 1>(s, mode, grid, st);
+}
+template <int UN, int NT>
+void launch_lds(const SkArgs& s, int mode, dim3 grid, hipStream_t st) {
+  with_fuse(mode, [&](auto F) {
+    hipLaunchKernelGGL((skinny_lds_kernel<UN, 8, decltype(F)::value, NT>), grid, dim3(512), s.a_bytes, st, s);
+  });
+}
+template <int UN, int NW, int NT, int TM = 1>
+void launch_reg(const SkArgs& s, int mode, hipStream_t st) {
+  with_fuse(mode, [&](auto F) {
+    hipLaunchKernelGGL((skinny_packed_reg_kernel<UN, NW, decltype(F)::value, 1, NT, TM>), dim3(s.e.N / (16 * NT)),
+                       dim3(NW * 64), 0, st, s);
+  });
+}
+template <int UN, int NW, int NTL>
+void launch_packed(const SkArgs& s, int mode, hipStream_t st) {
+  with_fuse(mode, [&](auto F) {
+    hipLaunchKernelGGL((skinny_packed_kernel<UN, NW, decltype(F)::value, NTL>), dim3(s.e.N / 16), dim3(NW * 64),
+                       s.a_bytes, st, s);
+  });
+}
+template <int UN, int NW>
+void launch_fp8(const SkArgs& s, int mode, hipStream_t st) {
+  with_fuse(mode, [&](auto F) {
+    hipLaunchKernelGGL((skinny_fp8_kernel<UN, NW, decltype(F)::value>), dim3(s.e.N / 16), dim3(NW * 64), s.a_bytes, st,
+                       s);
+  });
 }
 
 }  // namespace
@@ -933,26 +758,11 @@ int mls_skinny_gemm_norm(const void* A, const void* A2, void* A_out, const void*
                          void* out, void* ws, size_t ws_bytes, int M, int N, int K, int act, int nsplit, int norm,
                          float eps, void* stream) {
   if (M <= 0 || M > 32 || N % 16 || K % 8 || K <= 0) return MLS_BAD_ARG;
-  if (A_out && (A_out == A || A_out == A2)) return MLS_BAD_ARG;
-  SkArgs s{};
-  s.a = (const bf16*)A;
-  s.a2 = (const bf16*)A2;
-  s.a_out = (bf16*)A_out;
-  s.norm = norm;
-  s.eps = eps;
-  s.w = (const bf16*)W;
-  s.bias = bias;
-  s.res = (const bf16*)res;
-  s.out = (bf16*)out;
-  s.ws = (float*)ws;
-  s.M = M; s.N = N; s.K = K; s.lda = K;
-  s.fd_kch = fastdiv_make((uint32_t)(K >> 3));
-  s.act = act;
-  s.ldo = act == ACT_SILU_MUL ? N / 2 : N;
+  if (const int rc = sk_check_fuse(A, A2, A_out, norm)) return rc;
   const size_t ab = (size_t)M * K * 2, wb = (size_t)N * K * 2;
   if (ab >= 0x7FFFFFFFull || wb >= 0x7FFFFFFFull) return MLS_UNSUPPORTED;
-  s.a_bytes = (uint32_t)ab;
-  s.w_bytes = (uint32_t)wb;
+  SkArgs s = sk_args(A, A2, A_out, W, wb, bias, res, out, M, N, K, act, norm, eps);
+  s.ws = (float*)ws;
   // M > 2: NT tiles per block while that still leaves >= 384 blocks (1.5 per CU) -- measured: NT = 4
   // halves gate_up at M = 16 but costs ~10 % at M = 1, where the activation traffic is negligible
   // and the deeper single-tile unroll wins (profiles/r1_decode_probe.jsonl).  K is split across
@@ -975,54 +785,15 @@ int mls_skinny_gemm_norm(const void* A, const void* A2, void* A_out, const void*
   s.ksteps_per_split = (ksteps + nsplit - 1) / nsplit;
   dim3 grid(tiles, nsplit);
   hipStream_t st = (hipStream_t)stream;
-  if ((A2 || A_out) && !norm) return MLS_UNSUPPORTED;  // the residual add exists only as the norm prologue
-  const int mode = A2 ? FUSE_ADD_NORM : norm ? FUSE_NORM : FUSE_NONE;
-  const size_t a_lds_bytes = (size_t)M * K * 2;
-  if (M <= 4 && nsplit == 1 && K % 32 == 0 && a_lds_bytes <= 65536 && !g_skinny_no_lds) {
-#define MLS_SKL(UN, NT_)                                                                                        \
-  switch (mode) {                                                                                               \
-    case FUSE_NONE:                                                                                             \
-      hipLaunchKernelGGL((skinny_lds_kernel<UN, 8, FUSE_NONE, NT_>), grid, dim3(512), a_lds_bytes, st, s); break; \
-    case FUSE_NORM:                                                                                             \
-      hipLaunchKernelGGL((skinny_lds_kernel<UN, 8, FUSE_NORM, NT_>), grid, dim3(512), a_lds_bytes, st, s); break; \
-    default:                                                                                                    \
-      hipLaunchKernelGGL((skinny_lds_kernel<UN, 8, FUSE_ADD_NORM, NT_>), grid, dim3(512), a_lds_bytes, st, s);    \
-      break;                                                                                                    \
-  }
-    if (nt == 4) {
-      MLS_SKL(4, 4)
-    } else if (nt == 2) {
-      MLS_SKL(4, 2)
-    } else {
-      MLS_SKL(8, 1)
-    }
-#undef MLS_SKL
+  const int mode = sk_fuse_mode(A2, norm);
+  if (M <= 4 && nsplit == 1 && K % 32 == 0 && ab <= 65536 && !g_skinny_no_lds) {
+    if (nt == 4) launch_lds<4, 4>(s, mode, grid, st);
+    else if (nt == 2) launch_lds<4, 2>(s, mode, grid, st);
+    else launch_lds<8, 1>(s, mode, grid, st);
     return (int)hipGetLastError();
   }
-#define MLS_SKINNY_F(TMS, UN, NT_)                                                                             \
-  switch (mode) {                                                                                              \
-    case FUSE_NONE:                                                                                            \
-      hipLaunchKernelGGL((skinny_gemm_kernel<TMS, UN, 8, FUSE_NONE, NT_>), grid, dim3(512), 0, st, s); break;   \
-    case FUSE_NORM:                                                                                            \
-      hipLaunchKernelGGL((skinny_gemm_kernel<TMS, UN, 8, FUSE_NORM, NT_>), grid, dim3(512), 0, st, s); break;   \
-    default:                                                                                                   \
-      hipLaunchKernelGGL((skinny_gemm_kernel<TMS, UN, 8, FUSE_ADD_NORM, NT_>), grid, dim3(512), 0, st, s); break; \
-  }
-#define MLS_SKINNY(TMS, UN)                      \
-  if (nt == 4) {                                 \
-    MLS_SKINNY_F(TMS, (UN > 4 ? 4 : UN), 4)      \
-  } else if (nt == 2) {                          \
-    MLS_SKINNY_F(TMS, UN, 2)                     \
-  } else {                                       \
-    MLS_SKINNY_F(TMS, UN, 1)                     \
-  }
-  if (M <= 16) {
-    MLS_SKINNY(1, 8)
-  } else {
-    MLS_SKINNY(2, 4)
-  }
-#undef MLS_SKINNY
-#undef MLS_SKINNY_F
+  if (M <= 16) launch_gemm_nt<1, 8>(s, mode, nt, grid, st);
+  else launch_gemm_nt<2, 4>(s, mode, nt, grid, st);
   if (nsplit > 1) {
     const long total = (long)M * (act == ACT_SILU_MUL ? N / 2 : N);
     int blocks = (int)((total + 255) / 256);
@@ -1053,56 +824,21 @@ static int skinny_packed_impl(const void* A, const void* A2, void* A_out, const 
                               const void* res, void* out, int M, int N, int K, int act, int norm, float eps, int variant,
                               void* stream, const ArFuse* arf) {
   if (M <= 0 || M > 32 || N % 16 || K % 32 || K <= 0) return MLS_BAD_ARG;
-  if (A_out && (A_out == A || A_out == A2)) return MLS_BAD_ARG;
-  if ((A2 || A_out) && !norm) return MLS_UNSUPPORTED;
+  if (const int rc = sk_check_fuse(A, A2, A_out, norm)) return rc;
   const size_t ab = (size_t)M * K * 2, wb = (size_t)N * K * 2;
   if (wb >= 0x7FFFFFFFull) return MLS_UNSUPPORTED;
-  SkArgs s{};
-  s.a = (const bf16*)A;
-  s.a2 = (const bf16*)A2;
-  s.a_out = (bf16*)A_out;
-  s.norm = norm;
-  s.eps = eps;
-  s.w = (const bf16*)Wp;
-  s.bias = bias;
-  s.res = (const bf16*)res;
-  s.out = (bf16*)out;
-  s.M = M; s.N = N; s.K = K; s.lda = K;
-  s.fd_kch = fastdiv_make((uint32_t)(K >> 3));
-  s.act = act;
-  s.ldo = act == ACT_SILU_MUL ? N / 2 : N;
-  s.a_bytes = (uint32_t)ab;
-  s.w_bytes = (uint32_t)wb;
-  s.nsplit = 1;
-  if (arf) s.arf = *arf;
-  const int mode = A2 ? FUSE_ADD_NORM : norm ? FUSE_NORM : FUSE_NONE;
+  const SkArgs s = sk_args(A, A2, A_out, Wp, wb, bias, res, out, M, N, K, act, norm, eps, arf);
+  const int mode = sk_fuse_mode(A2, norm);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(N / 16);
   if (M > 4 || ab > 65536 || (variant & 16)) {  // A fragments from L2 in registers (16: forced)
-#define MLS_SKR3(UN, NW, NT_, TM)                                                                               \
-  switch (mode) {                                                                                                 \
-    case FUSE_NONE:                                                                                               \
-      hipLaunchKernelGGL((skinny_packed_reg_kernel<UN, NW, FUSE_NONE, 1, NT_, TM>), dim3(N / (16 * NT_)),          \
-                         dim3(NW * 64), 0, st, s);                                                                \
-      break;                                                                                                      \
-    case FUSE_NORM:                                                                                               \
-      hipLaunchKernelGGL((skinny_packed_reg_kernel<UN, NW, FUSE_NORM, 1, NT_, TM>), dim3(N / (16 * NT_)),          \
-                         dim3(NW * 64), 0, st, s);                                                                \
-      break;                                                                                                      \
-    default:                                                                                                      \
-      hipLaunchKernelGGL((skinny_packed_reg_kernel<UN, NW, FUSE_ADD_NORM, 1, NT_, TM>), dim3(N / (16 * NT_)),      \
-                         dim3(NW * 64), 0, st, s);                                                                \
-      break;                                                                                                      \
-  }
-#define MLS_SKR(UN, NW, NT_) MLS_SKR3(UN, NW, NT_, 1)
     int v = variant & 15;
     if (M > 16) {  // two 16-row A fragments per granule
       if (N / 16 >= 384 && N % 32 == 0 && v != 10) {
-        MLS_SKR3(4, 8, 2, 2)  // 8 waves: the double-buffered 2-tile trip needs > 128 VGPRs
+        launch_reg<4, 8, 2, 2>(s, mode, st);  // 8 waves: the double-buffered 2-tile trip needs > 128 VGPRs
       } else if (v == 10) {
-        MLS_SKR3(4, 8, 1, 2)
+        launch_reg<4, 8, 1, 2>(s, mode, st);
       } else {
-        MLS_SKR3(4, 16, 1, 2)
+        launch_reg<4, 16, 1, 2>(s, mode, st);
       }
       return (int)hipGetLastError();
     }
@@ -1113,41 +849,28 @@ static int skinny_packed_impl(const void* A, const void* A2, void* A_out, const 
     if ((v == 11 || v == 13) && N % 32) v = 9;
     if (v == 12 && N % 64) v = 9;
     switch (v) {
-      case 1: MLS_SKR(8, 8, 1) break;
-      case 10: MLS_SKR(4, 8, 1) break;
-      case 11: MLS_SKR(4, 8, 2) break;
-      case 12: MLS_SKR(4, 8, 4) break;
-      case 13: MLS_SKR(4, 16, 2) break;
-      default: MLS_SKR(4, 16, 1) break;
+      case 1: launch_reg<8, 8, 1>(s, mode, st); break;
+      case 10: launch_reg<4, 8, 1>(s, mode, st); break;
+      case 11: launch_reg<4, 8, 2>(s, mode, st); break;
+      case 12: launch_reg<4, 8, 4>(s, mode, st); break;
+      case 13: launch_reg<4, 16, 2>(s, mode, st); break;
+      default: launch_reg<4, 16, 1>(s, mode, st); break;
     }
-#undef MLS_SKR
-#undef MLS_SKR3
     return (int)hipGetLastError();
   }
-#define MLS_SKP(UN, NW, NTL_)                                                                                 \
-  switch (mode) {                                                                                               \
-    case FUSE_NONE:                                                                                             \
-      hipLaunchKernelGGL((skinny_packed_kernel<UN, NW, FUSE_NONE, NTL_>), grid, dim3(NW * 64), ab, st, s); break; \
-    case FUSE_NORM:                                                                                             \
-      hipLaunchKernelGGL((skinny_packed_kernel<UN, NW, FUSE_NORM, NTL_>), grid, dim3(NW * 64), ab, st, s); break; \
-    default:                                                                                                    \
-      hipLaunchKernelGGL((skinny_packed_kernel<UN, NW, FUSE_ADD_NORM, NTL_>), grid, dim3(NW * 64), ab, st, s);    \
-      break;                                                                                                    \
-  }
   switch (variant) {
-    case 0: MLS_SKP(8, 8, 0) break;
-    case 2: MLS_SKP(8, 4, 0) break;
-    case 3: MLS_SKP(8, 4, 1) break;
-    case 4: MLS_SKP(16, 8, 0) break;
-    case 5: MLS_SKP(16, 8, 1) break;
-    case 6: MLS_SKP(16, 4, 0) break;
-    case 7: MLS_SKP(16, 4, 1) break;
-    case 8: MLS_SKP(8, 16, 1) break;
-    case 9: MLS_SKP(4, 16, 1) break;
-    case 10: MLS_SKP(4, 8, 1) break;
-    default: MLS_SKP(8, 8, 1) break;  // 1: the measured default
+    case 0: launch_packed<8, 8, 0>(s, mode, st); break;
+    case 2: launch_packed<8, 4, 0>(s, mode, st); break;
+    case 3: launch_packed<8, 4, 1>(s, mode, st); break;
+    case 4: launch_packed<16, 8, 0>(s, mode, st); break;
+    case 5: launch_packed<16, 8, 1>(s, mode, st); break;
+    case 6: launch_packed<16, 4, 0>(s, mode, st); break;
+    case 7: launch_packed<16, 4, 1>(s, mode, st); break;
+    case 8: launch_packed<8, 16, 1>(s, mode, st); break;
+    case 9: launch_packed<4, 16, 1>(s, mode, st); break;
+    case 10: launch_packed<4, 8, 1>(s, mode, st); break;
+    default: launch_packed<8, 8, 1>(s, mode, st); break;  // 1: the measured default
   }
-#undef MLS_SKP
   return (int)hipGetLastError();
 }
 
@@ -1161,19 +884,7 @@ static int skinny_packed_combine_impl(const void* A, const float* cws, const flo
   if (M <= 0 || M > 4 || N % 16 || K % 32 || K != Hq * D || D % 8 || nsplit <= 0 || chunk <= 0) return MLS_BAD_ARG;
   const size_t ab = (size_t)M * K * 2, wb = (size_t)N * K * 2;
   if (wb >= 0x7FFFFFFFull || ab > 65536) return MLS_UNSUPPORTED;
-  SkArgs s{};
-  s.a = (const bf16*)A;
-  s.w = (const bf16*)Wp;
-  s.bias = bias;
-  s.res = (const bf16*)res;
-  s.out = (bf16*)out;
-  s.M = M; s.N = N; s.K = K; s.lda = K;
-  s.fd_kch = fastdiv_make((uint32_t)(K >> 3));
-  s.act = act;
-  s.ldo = act == ACT_SILU_MUL ? N / 2 : N;
-  s.a_bytes = (uint32_t)ab;
-  s.w_bytes = (uint32_t)wb;
-  s.nsplit = 1;
+  SkArgs s = sk_args(A, nullptr, nullptr, Wp, wb, bias, res, out, M, N, K, act, 0, 0.f, arf);
   s.cws = cws;
   s.cml = cml;
   s.lens = lens;
@@ -1182,7 +893,6 @@ static int skinny_packed_combine_impl(const void* A, const float* cws, const flo
   s.c_hq = Hq;
   s.c_hd = D;
   s.fd_hd = fastdiv_make((uint32_t)D);
-  if (arf) s.arf = *arf;
   hipStream_t st = (hipStream_t)stream;
   if (variant == 1)
     hipLaunchKernelGGL((skinny_packed_kernel<8, 8, FUSE_COMBINE, 1>), dim3(N / 16), dim3(512), ab, st, s);
@@ -1237,47 +947,18 @@ int mls_skinny_fp8(const void* A, const void* A2, void* A_out, const void* Wq, c
                    const void* res, void* out, int M, int N, int K, int act, int norm, float eps, int variant,
                    void* stream) {
   if (M <= 0 || M > 4 || N % 16 || K % 64 || K <= 0 || !wscale) return MLS_BAD_ARG;
-  if (A_out && (A_out == A || A_out == A2)) return MLS_BAD_ARG;
-  if ((A2 || A_out) && !norm) return MLS_UNSUPPORTED;
+  if (const int rc = sk_check_fuse(A, A2, A_out, norm)) return rc;
   const size_t ab = (size_t)M * K * 2, wb = (size_t)N * K;
   if (wb >= 0x7FFFFFFFull || ab > 65536) return MLS_UNSUPPORTED;
-  SkArgs s{};
-  s.a = (const bf16*)A;
-  s.a2 = (const bf16*)A2;
-  s.a_out = (bf16*)A_out;
-  s.norm = norm;
-  s.eps = eps;
-  s.w = (const bf16*)Wq;
+  SkArgs s = sk_args(A, A2, A_out, Wq, wb, bias, res, out, M, N, K, act, norm, eps);
   s.wscale = wscale;
-  s.bias = bias;
-  s.res = (const bf16*)res;
-  s.out = (bf16*)out;
-  s.M = M; s.N = N; s.K = K; s.lda = K;
-  s.fd_kch = fastdiv_make((uint32_t)(K >> 3));
-  s.act = act;
-  s.ldo = act == ACT_SILU_MUL ? N / 2 : N;
-  s.a_bytes = (uint32_t)ab;
-  s.w_bytes = (uint32_t)wb;
-  s.nsplit = 1;
-  const int mode = A2 ? FUSE_ADD_NORM : norm ? FUSE_NORM : FUSE_NONE;
+  const int mode = sk_fuse_mode(A2, norm);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(N / 16);
-#define MLS_SK8(UN, NW)                                                                                     \
-  switch (mode) {                                                                                           \
-    case FUSE_NONE: hipLaunchKernelGGL((skinny_fp8_kernel<UN, NW, FUSE_NONE>), grid, dim3(NW * 64), ab, st, s); break; \
-    case FUSE_NORM: hipLaunchKernelGGL((skinny_fp8_kernel<UN, NW, FUSE_NORM>), grid, dim3(NW * 64), ab, st, s); break; \
-    default: hipLaunchKernelGGL((skinny_fp8_kernel<UN, NW, FUSE_ADD_NORM>), grid, dim3(NW * 64), ab, st, s); break;    \
-  }
   // variant: 1 (default) 4 granules per trip x 8 waves; 0: 4 x 16; 2: 2 x 16
   // (profiles/r2_decode_fp8_weight_probe.jsonl: 1 is fastest on every Llama-3-8B shape)
-  if (variant == 0) {
-    MLS_SK8(4, 16)
-  } else if (variant == 2) {
-    MLS_SK8(2, 16)
-  } else {
-    MLS_SK8(4, 8)
-  }
-#undef MLS_SK8
+  if (variant == 0) launch_fp8<4, 16>(s, mode, st);
+  else if (variant == 2) launch_fp8<2, 16>(s, mode, st);
+  else launch_fp8<4, 8>(s, mode, st);
   return (int)hipGetLastError();
 }
 

@@ -15,8 +15,7 @@
 // 136 |a|: ~2^-18 of a product), and the group's scale, lane-local because the accumulator column is
 // nr, folds it in: acc += s[n] * acc_group.  The loop body is branch-free (cdna_hip_programming.md
 // item 4c: a runtime branch there drains vmcnt).
-#include "common.h"
-#include "fastdiv.h"
+#include "skinny_tiles.h"
 
 namespace {
 
@@ -26,48 +25,11 @@ struct W4Args {
   bf16* a_out;     // optional [M][K] <- a + a2 (written by the block of column tile 0)
   const uint8_t* w;  // packed nibbles, N K / 2 bytes
   const bf16* sc;    // [N/16][K/128][16]
-  const float* bias;
-  const bf16* res;  // [M][N]
-  bf16* out;        // [M][ldo]
-  int M, N, K, ldo, act;
-  float eps;
+  SkEpi e;           // bias, res, out, M, N, K, ldo, act, eps
   uint32_t a_bytes, w_bytes, s_bytes;
   FastDiv fd_kch;  // K / 8 chunks per row (LDS staging)
 };
 
-enum { FUSE_NONE = 0, FUSE_NORM = 1, FUSE_ADD_NORM = 2 };
-
-MLS_DEV uint4 add_round(uint4 a, uint4 b) {  // bf16 + bf16 -> bf16 (the residual stream's precision)
-  float x[8], y[8];
-  unpack8(a, x);
-  unpack8(b, y);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) x[e] += y[e];
-  return pack8(x);
-}
-
-MLS_DEV float sumsq8(uint4 v) {
-  float x[8];
-  unpack8(v, x);
-  float r = 0.f;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) r += x[e] * x[e];
-  return r;
-}
-
-// wave64 sum on the VALU (DPP + permlane swaps): the staging prologue is a latency chain every block
-// pays before its first MFMA, and four ds_bpermute reductions there cost more than the weight stream
-MLS_DEV float wave_sum_valu(float v) {
-  v = group_sum<16>(v);
-  v += xor16_f(v);
-  return v + xor32_f(v);
-}
-
-MLS_DEV float epi(float v, int n, const W4Args& s) { return v + (s.bias ? s.bias[n] : 0.f); }
-
-MLS_DEV uint4 bload16_nt(rsrc_t r, int byte_off) {  // the weight stream is read exactly once per call
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 2));
-}
 MLS_DEV uint32_t bload2(rsrc_t r, int byte_off) { return __builtin_amdgcn_raw_buffer_load_b16(r, byte_off, 0, 0); }
 
 // one k-step's word -> the B fragment 136 + q (k order)
@@ -100,8 +62,8 @@ __global__ __launch_bounds__(NWV * 64) void skinny_w4_kernel(const W4Args s) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nr = lane & 15, g = lane >> 4;
   const int tile0 = blockIdx.x * NT, n0 = tile0 * 16;
-  const int G = s.K >> 7;  // granules (= scale groups) per tile
-  const int kch = s.K >> 3;
+  const int G = s.e.K >> 7;  // granules (= scale groups) per tile
+  const int kch = s.e.K >> 3;
   const int gpw = (G + NWV - 1) / NWV;
   const int gb = wid * gpw, ge = min(G, gb + gpw);
   const rsrc_t wr = make_rsrc(s.w, s.w_bytes);
@@ -112,7 +74,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_w4_kernel(const W4Args s) {
   const int sbase = (tile0 * G * 16 + nr) * 2;     //                    + (j G + q) 32
   int abase[TMS];
 #pragma unroll
-  for (int t = 0; t < TMS; ++t) abase[t] = 16 * t + nr < s.M ? ((16 * t + nr) * s.K + 8 * g) * 2 : OOB;
+  for (int t = 0; t < TMS; ++t) abase[t] = 16 * t + nr < s.e.M ? ((16 * t + nr) * s.e.K + 8 * g) * 2 : OOB;
   const bool wr_res = FUSE == FUSE_ADD_NORM && s.a_out && blockIdx.x == 0;
 
   constexpr int AU = ALDS ? 1 : UN, AK = ALDS ? 1 : 4;  // register A fragments: none with LDS staging
@@ -127,7 +89,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_w4_kernel(const W4Args s) {
       const bool in = q0 + u < ge;
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
-        tr.w[u][j] = bload16_nt(wr, in ? wbase + (j * G + q0 + u) * 1024 : OOB);
+        tr.w[u][j] = bload16_pol<1>(wr, in ? wbase + (j * G + q0 + u) * 1024 : OOB);
         tr.sc[u][j] = bload2(sr, in ? sbase + (j * G + q0 + u) * 32 : OOB);
       }
       if constexpr (!ALDS) {
@@ -156,13 +118,13 @@ __global__ __launch_bounds__(NWV * 64) void skinny_w4_kernel(const W4Args s) {
     // weight trip (the vector memory counter retires in order, so consuming them does not wait for
     // the weights) and the barrier below is LDS-only.
     constexpr int QPT = 2048 / T;
-    const int nq = s.M * kch;
+    const int nq = s.e.M * kch;
     uint4 a0[QPT], a20[QPT];
 #pragma unroll
     for (int j = 0; j < QPT; ++j) {
       const int q = tid + j * T;
       const int m = fastdiv(q, s.fd_kch), c = q - m * kch;
-      const int off = q < nq ? (m * s.K + c * 8) * 2 : OOB;
+      const int off = q < nq ? (m * s.e.K + c * 8) * 2 : OOB;
       a0[j] = bload16(ar, off);
       if constexpr (FUSE == FUSE_ADD_NORM) a20[j] = bload16(a2r, off);
     }
@@ -172,7 +134,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_w4_kernel(const W4Args s) {
       const int m = fastdiv(q, s.fd_kch), c = q - m * kch;
       if constexpr (FUSE == FUSE_ADD_NORM) {
         v = add_round(v, v2);
-        if (wr_res) st16(s.a_out + (size_t)m * s.K + c * 8, v);
+        if (wr_res) st16(s.a_out + (size_t)m * s.e.K + c * 8, v);
       }
       a_lds[q] = v;
       if constexpr (FUSE != FUSE_NONE) {
@@ -186,8 +148,8 @@ __global__ __launch_bounds__(NWV * 64) void skinny_w4_kernel(const W4Args s) {
       if (tid + j * T < nq) stage(tid + j * T, a0[j], a20[j]);
     for (int q = tid + QPT * T; q < nq; q += T) {
       const int m = fastdiv(q, s.fd_kch), c = q - m * kch;
-      stage(q, ld16(s.a + (size_t)m * s.K + c * 8),
-            FUSE == FUSE_ADD_NORM ? ld16(s.a2 + (size_t)m * s.K + c * 8) : make_uint4(0, 0, 0, 0));
+      stage(q, ld16(s.a + (size_t)m * s.e.K + c * 8),
+            FUSE == FUSE_ADD_NORM ? ld16(s.a2 + (size_t)m * s.e.K + c * 8) : make_uint4(0, 0, 0, 0));
     }
     if constexpr (FUSE != FUSE_NONE) {
 #pragma unroll
@@ -208,7 +170,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_w4_kernel(const W4Args s) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const bf16x8 neg136 = __builtin_bit_cast(bf16x8, make_uint4(0xC308C308u, 0xC308C308u, 0xC308C308u, 0xC308C308u));
-  const bool arow = nr < s.M;
+  const bool arow = nr < s.e.M;
 
   for (int q = gb; q < ge; q += UN) {
     Trip cur = nxt;
@@ -227,7 +189,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_w4_kernel(const W4Args s) {
             uint4 v = cur.a[u][ks][t];
             if constexpr (FUSE == FUSE_ADD_NORM) {
               v = add_round(v, cur.a2[u][ks][t]);
-              if (wr_res && abase[t] != OOB && q + u < ge) st16(s.a_out + (16 * t + nr) * s.K + kstep * 32 + 8 * g, v);
+              if (wr_res && abase[t] != OOB && q + u < ge) st16(s.a_out + (16 * t + nr) * s.e.K + kstep * 32 + 8 * g, v);
             }
             if constexpr (FUSE != FUSE_NONE)
               aat[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, v), __builtin_bit_cast(bf16x8, v),
@@ -293,36 +255,8 @@ __global__ __launch_bounds__(NWV * 64) void skinny_w4_kernel(const W4Args s) {
     }
   }
   __syncthreads();
-  const bool glu = s.act == ACT_SILU_MUL;
-  constexpr int COLS = NT * 16;
-  for (int q = tid; q < s.M * COLS; q += T) {
-    const int m = q / COLS, c = q % COLS;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < NWV; ++w) v += red[w][m][c];
-    float rs = 1.f;
-    if constexpr (FUSE != FUSE_NONE) {
-      float t2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < NWV; ++w) t2 += ssq_red[w][m];
-      rs = rsqrtf(t2 / (float)s.K + s.eps);
-    }
-    const int n = n0 + c;
-    v *= rs;
-    if (glu) {
-      if ((c & 15) < 8) {
-        float up = 0.f;
-#pragma unroll
-        for (int w = 0; w < NWV; ++w) up += red[w][m][c + 8];
-        up *= rs;
-        s.out[(size_t)m * s.ldo + (n >> 4) * 8 + (n & 7)] = (bf16)(silu(epi(v, n, s)) * epi(up, n + 8, s));
-      }
-      continue;
-    }
-    float o = epi(v, n, s);
-    if (s.res) o += (float)s.res[(size_t)m * s.N + n];
-    s.out[(size_t)m * s.ldo + n] = (bf16)apply_act(o, s.act);
-  }
+  sk_reduce_store<NWV, 16 * TMS, NT * 16>(red, s.e, n0,
+                                          [&](int m) { return FUSE != FUSE_NONE ? sk_rstd(ssq_red, m, s.e) : 1.f; });
 }
 
 // launch shapes: (A in LDS, column tiles per block, granules per trip, waves)
@@ -348,18 +282,10 @@ constexpr int W4_NVARIANTS = sizeof(W4_SHAPES) / sizeof(W4_SHAPES[0]);
 
 template <int TMS, int NT, int UN, int NWV, bool ALDS, bool SCALED = false>
 void w4_launch(const W4Args& s, int mode, size_t lds, hipStream_t st) {
-  const dim3 grid(s.N / (16 * NT)), block(NWV * 64);
-  switch (mode) {
-    case FUSE_NONE:
-      hipLaunchKernelGGL((skinny_w4_kernel<TMS, NT, UN, NWV, FUSE_NONE, ALDS, SCALED>), grid, block, lds, st, s);
-      break;
-    case FUSE_NORM:
-      hipLaunchKernelGGL((skinny_w4_kernel<TMS, NT, UN, NWV, FUSE_NORM, ALDS, SCALED>), grid, block, lds, st, s);
-      break;
-    default:
-      hipLaunchKernelGGL((skinny_w4_kernel<TMS, NT, UN, NWV, FUSE_ADD_NORM, ALDS, SCALED>), grid, block, lds, st, s);
-      break;
-  }
+  const dim3 grid(s.e.N / (16 * NT)), block(NWV * 64);
+  with_fuse(mode, [&](auto F) {
+    hipLaunchKernelGGL((skinny_w4_kernel<TMS, NT, UN, NWV, decltype(F)::value, ALDS, SCALED>), grid, block, lds, st, s);
+  });
 }
 
 }  // namespace
@@ -378,28 +304,21 @@ int mls_skinny_w4(const void* A, const void* A2, void* A_out, const void* Wq, co
   if (M <= 0 || M > 32 || N <= 0 || N % 16 || K <= 0 || K % 128) return MLS_BAD_ARG;
   if (!A || !Wq || !scales || !out) return MLS_BAD_ARG;
   if (variant < 0 || variant >= W4_NVARIANTS) return MLS_BAD_ARG;
-  if (A_out && (A_out == A || A_out == A2)) return MLS_BAD_ARG;
-  if ((A2 || A_out) && !norm) return MLS_UNSUPPORTED;
+  if (const int rc = sk_check_fuse(A, A2, A_out, norm)) return rc;
   const size_t ab = (size_t)M * K * 2, wb = (size_t)N * K / 2;
   if (wb >= 0x7FFFFFFFull) return MLS_UNSUPPORTED;
   W4Args s{};
+  s.e = sk_epi(bias, res, out, M, N, K, act, eps);
   s.a = (const bf16*)A;
   s.a2 = (const bf16*)A2;
   s.a_out = (bf16*)A_out;
   s.w = (const uint8_t*)Wq;
   s.sc = (const bf16*)scales;
-  s.bias = bias;
-  s.res = (const bf16*)res;
-  s.out = (bf16*)out;
-  s.M = M; s.N = N; s.K = K;
-  s.act = act;
-  s.ldo = act == ACT_SILU_MUL ? N / 2 : N;
-  s.eps = eps;
   s.a_bytes = (uint32_t)ab;
   s.w_bytes = (uint32_t)wb;
   s.s_bytes = (uint32_t)((size_t)N * K / 128 * 2);
   s.fd_kch = fastdiv_make((uint32_t)(K >> 3));
-  const int mode = A2 ? FUSE_ADD_NORM : norm ? FUSE_NORM : FUSE_NONE;
+  const int mode = sk_fuse_mode(A2, norm);
   hipStream_t st = (hipStream_t)stream;
   const bool can_lds = M <= 4 && ab <= 65536;
   W4Shape sh = W4_SHAPES[variant];

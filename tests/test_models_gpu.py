@@ -81,6 +81,43 @@ def test_gemm_rmsnorm_fused(M, nsplit):
     assert out.shape == (M, 384) and rel(out, ref) < 2e-2
 
 
+@pytest.mark.parametrize("M", [3, 16])
+def test_skinny_gemm_ragged_k(M):
+    """K % 32 == 8: the row-major kernel's k tail (the last k-step holds one 8-wide slice), which K % 32
+    also keeps off the LDS kernel at M <= 4."""
+    from mlmicroservicetemplate_amd import ops
+
+    torch.manual_seed(30 + M)
+    N, K = 48, 104
+    a = torch.randn(M, K, device=DEV).to(torch.bfloat16)
+    w = (torch.randn(N, K, device=DEV) / K**0.5).to(torch.bfloat16)
+    b = torch.randn(N, device=DEV)
+    r = torch.randn(M, N, device=DEV).to(torch.bfloat16)
+    out = ops.gemm(a, w, b, residual=r, splitk=1)
+    assert rel(out, a.float() @ w.float().T + b + r.float()) < 2e-2
+
+
+@pytest.mark.parametrize("nsplit", [1, 2])
+def test_gemm_rmsnorm_two_row_tiles_ragged_k(nsplit):
+    """M = 17: two 16-row A fragments per k-step, with the ragged K and, at nsplit = 2, the partial
+    square sums that ride behind the slabs to the finishing kernel."""
+    from mlmicroservicetemplate_amd import ops
+    from mlmicroservicetemplate_amd.ops import reference as R
+
+    torch.manual_seed(40 + nsplit)
+    M, N, K = 17, 48, 104
+    x = torch.randn(M, K, device=DEV).to(torch.bfloat16)
+    d = torch.randn(M, K, device=DEV).to(torch.bfloat16)
+    gain = (torch.rand(K, device=DEV) + 0.5).to(torch.bfloat16)
+    w = (torch.randn(N, K, device=DEV) / K**0.5).to(torch.bfloat16)
+    ws = torch.empty(nsplit * M * (N + 1), device=DEV, dtype=torch.float32)
+    r_out = torch.empty_like(x)
+    y = ops.gemm_rmsnorm(x, ops.fold_norm(w, gain), d, r_out, eps=1e-5, workspace=ws, splitk=nsplit)
+    assert torch.equal(r_out, (x.float() + d.float()).to(torch.bfloat16))
+    xn = R.layernorm(x, gain, None, residual=d, eps=1e-5, rms=True)[0]
+    assert rel(y, xn.float() @ w.float().T) < 2e-2
+
+
 @pytest.mark.parametrize("M", [1, 3, 4])
 @pytest.mark.parametrize("fused", [False, True])
 def test_skinny_lds_wide_n(M, fused):
