@@ -456,14 +456,23 @@ class LlamaTP:
     def __init__(self, params: Dict[str, torch.Tensor], cfg: LlamaConfig, tp: int = 1, rank: int = 0,
                  comm: Optional[TPComm] = None, backend: str = "reference", device="cpu", max_batch: int = 8,
                  max_seq: int = 1024, top_k_max: int = 50, kv_pages: int = 0, kv_dtype: str = "bf16",
-                 weight_dtype: str = "bf16"):
+                 weight_dtype: str = "bf16", kv_prefill: str = "rows"):
         """``kv_pages > 0``: paged KV cache -- per layer a pool of ``kv_pages`` pages of 64 rows
         shared by all sequences (:class:`~.kv_pages.PageTable`), instead of ``max_batch x max_seq``.
         ``kv_dtype="fp8"``: e4m3 KV rows with one fp32 scale per (row, KV head)
         (``ops.reference.kv_quant_fp8``) -- 132 instead of 256 bytes per head row.  Fused backend: uint8
         caches + scale tensors, written and read by ``ops.rope_kv_fp8_`` / ``ops.decode_attention_fp8``
         (head-major layout, head_dim 128, Hq / Hkv in 1, 2, 4, 8 only); reference backend: the fp32
-        caches hold the round-tripped rows (the CPU oracle).  Prefill attention stays unquantised.
+        caches hold the round-tripped rows (the CPU oracle).  Prefill attention stays unquantised, unless
+        ``kv_prefill="cache"`` (with ``kv_dtype="fp8"`` only; default ``"rows"``): every prefill attention
+        then reads K / V from the cache, as decode does -- a forward appends its own rows first and reads
+        them back quantised (reference: ``R.attention_ctx``, fused: ``ops.flash_attention_ctx_fp8``), the
+        first chunk and a one-shot ``step(past=None)`` included, which run as ``past = 0``.  A token's
+        logits then do not depend on how its prompt was chunked, on whether its prefix came from shared
+        pages or on whether it was verified in a speculation step, so chunked prefill, prefix caching and
+        speculative decoding are served with the e4m3 cache; prefill logits move from unquantised to e4m3
+        rows.  The two-half TP-overlap prefill (``_prefill_overlapped``) attends the forward's own bf16
+        rows, so it is not taken in this mode: the plain layer loop runs instead.
         ``weight_dtype="int4"``: W4A16 layer projections (qkv, o, gate / up, down) -- symmetric 4-bit
         codes with one bf16 scale per (row, 128 k) (``ops.reference.w4_quant``), quantised with the
         RMSNorm gains folded in; ``lm_head`` and the embedding stay bf16 (the usual quality choice).
@@ -476,7 +485,13 @@ class LlamaTP:
             raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
         if weight_dtype not in ("bf16", "int4"):
             raise ValueError(f"weight_dtype must be 'bf16' or 'int4', got {weight_dtype!r}")
+        if kv_prefill not in ("rows", "cache"):
+            raise ValueError(f"kv_prefill must be 'rows' or 'cache', got {kv_prefill!r}")
+        if kv_prefill == "cache" and kv_dtype != "fp8":
+            raise ValueError("kv_prefill='cache' is for kv_dtype='fp8' only: a bf16 cache already holds the very "
+                             "rows prefill attends")
         self.kv_dtype = kv_dtype
+        self.kv_prefill = kv_prefill
         self.weight_dtype = weight_dtype
         self.cfg = cfg
         self.sd = shard_dims(cfg, tp, rank)
@@ -743,7 +758,9 @@ class LlamaTP:
         rows = b_of if slots_b is None else slots_b.long()[b_of]  # batch row -> cache row
         bi, pi = rows[valid], positions[valid].long()
         k_st, v_st = k[valid], v[valid]
-        if self.kv_dtype == "fp8":  # the cache holds what an e4m3 row + scale gives back (prefill stays unquantised)
+        # the cache holds what an e4m3 row + scale gives back (kv_prefill="rows": prefill stays unquantised;
+        # "cache": every prefill comes with past and attends these rows below)
+        if self.kv_dtype == "fp8":
             k_st = R.kv_dequant_fp8(*R.kv_quant_fp8(k_st))
             v_st = R.kv_dequant_fp8(*R.kv_quant_fp8(v_st))
         if self.pages is not None:  # paged: flat pool rows through the page table
@@ -799,7 +816,7 @@ class LlamaTP:
         return step_route(
             B=B, S=S, decode=decode, has_past=has_past, all_rows=all_rows, tp=self.tp, hq=sd.hq, hkv=sd.hkv,
             head_dim=cfg.head_dim, hidden=cfg.hidden, have_packed=bool(self.packed), have_w4=bool(self.w4),
-            have_fp8=bool(self.fp8), o_packed="l0.o" in self.packed, o_fp8="l0.o" in self.fp8,
+            have_fp8=bool(self.fp8), o_packed="l0.o" in self.packed, o_fp8="l0.o" in self.fp8, kv_fp8=self.kv_fp8,
             w4_max_rows=self.w4_max_rows, pk_fold=self.pk_fold, prefill_fold=self.prefill_fold,
             fuse_combine=self.fuse_combine, fuse_add_norm=self.fuse_add_norm, ar_fuse=self.ar_fuse,
             tp_overlap=self.tp_overlap, verify_attn=self.verify_attn, spec_max_tokens=self.spec_max_tokens,
@@ -875,7 +892,10 @@ class LlamaTP:
         """Split-KV partials of a verify step (``ops.decode_attention_multi``) of T rows."""
         sd, D = self.sd, self.cfg.head_dim
         cap = self.pages.pages_per_seq * self.page_rows if self.pages is not None else self.max_seq
-        need = T * sd.hq * (-(-min(self._dec_ctx or cap, cap) // chunk)) * (D + 2)
+        return self._verify_ws(T * sd.hq * (-(-min(self._dec_ctx or cap, cap) // chunk)) * (D + 2))
+
+    def _verify_ws(self, need: int) -> torch.Tensor:
+        """``need`` fp32 elements of split-KV partials for a verify step, captured or not."""
         # a captured step owns its workspace (_verify_graph keeps it alive with the graph, whose launches
         # hold its address); only the uncaptured steps share one, which may therefore be regrown
         ws = self._ver_ws_graph
@@ -887,9 +907,11 @@ class LlamaTP:
             ws = self._ver_ws_graph = torch.empty(need, device=self.device, dtype=torch.float32)
         return ws
 
-    def _ctx_split_kw(self, B: int, S: int, max_ctx: Optional[int]) -> dict:
-        """Prefix caching on: a prefill chunk (not a verify step, whose graphs own their workspaces) of few
-        queries against a long cached context runs split-KV where :meth:`ctx_splits` says so."""
+    def _ctx_split_kw(self, B: int, S: int, max_ctx: Optional[int], verify: bool = False) -> dict:
+        """Prefix caching on: a prefill chunk of few queries against a long cached context runs split-KV
+        where :meth:`ctx_splits` says so.  ``verify``: a verify step on the context kernel (the e4m3
+        cache) -- the same rule under the step's own context bound, its partials in the verify
+        workspace (a captured step's graph owns it)."""
         sd, D = self.sd, self.cfg.head_dim
         cap = self.pages.pages_per_seq * self.page_rows if self.pages is not None else self.max_seq
         ctx_max = min(int(max_ctx) if max_ctx else cap, cap)  # no host bound given: what a slot holds
@@ -897,6 +919,8 @@ class LlamaTP:
         if n_split <= 1:
             return {}
         need = self.ops.flash_ctx_workspace_elems(B, S, sd.hq, D, n_split)
+        if verify:
+            return dict(splits=n_split, max_ctx=ctx_max, workspace=self._verify_ws(need))
         if self.ctx_ws is None or self.ctx_ws.numel() < need:
             self.ctx_ws = torch.empty(need, device=self.device, dtype=torch.float32)
         return dict(splits=n_split, max_ctx=ctx_max, workspace=self.ctx_ws)
@@ -918,13 +942,16 @@ class LlamaTP:
             return dict(slot_ids=sid, chunk=chunk, max_len=self._dec_ctx, page_table=table,
                         workspace=self._verify_workspace(B * S, chunk))
         if past is not None:  # chunked prefill: the chunk's queries against the cache rows just written
-            split = self._ctx_split_kw(B, S, max_ctx) if self.ctx_split and not all_rows else {}
+            if all_rows and self.kv_fp8:  # a verify step, <= 8 queries against the whole context: always routed
+                split = self._ctx_split_kw(B, S, self._dec_ctx, verify=True)
+            else:
+                split = self._ctx_split_kw(B, S, max_ctx) if self.ctx_split and not all_rows else {}
             return dict(slot_ids=sid, page_table=table, **split)
         return {}
 
     def _rope_kv(self, i: int, qkv: torch.Tensor, pos, slots, lens, S: int, flat_off: Optional[int] = None) -> None:
         """RoPE on the Q / K heads of ``qkv`` in place + the append of its K / V rows to layer i's cache
-        (an e4m3 cache: quantised; qkv keeps the unquantised bf16 K / V that prefill attention reads).
+        (an e4m3 cache: quantised; qkv keeps the unquantised bf16 K / V that kv_prefill="rows" attends).
         ``flat_off``: the bf16 caches from that element on, flattened (implicit slots of a batch half)."""
         sd = self.sd
         args = (qkv, pos, self.cos, self.sin, sd.hq, sd.hkv, self.cfg.head_dim, slots)
@@ -952,6 +979,9 @@ class LlamaTP:
         if st.rt.multi:
             return ops.decode_attention_multi(qkv, kc, vc, st.past, st.lens, st.B, st.S, sd.hq, sd.hkv, D,
                                               **st.attn_kw), None
+        if st.past is not None and self.kv_fp8:
+            return ops.flash_attention_ctx_fp8(qkv, kc, vc, self.k_scale[i], self.v_scale[i], st.past, st.lens, st.B,
+                                               st.S, sd.hq, sd.hkv, D, **st.attn_kw), None
         if st.past is not None:
             return ops.flash_attention_ctx(qkv, kc, vc, st.past, st.lens, st.B, st.S, sd.hq, sd.hkv, D,
                                            **st.attn_kw), None
@@ -1123,7 +1153,7 @@ class LlamaTP:
     def check_prefill_chunk(self) -> None:
         """Chunked prefill (``step(past=...)``) reads its context from the KV cache: raises
         ``ValueError`` for the configurations it does not serve (nothing falls back to one shot)."""
-        if self.kv_dtype == "fp8":
+        if self.kv_dtype == "fp8" and self.kv_prefill != "cache":
             raise ValueError("chunked prefill is not available with kv_dtype='fp8': one-shot prefill attends the "
                              "unquantised rows, a chunk reading e4m3 context would change the numerics")
         if self.backend == "fused":
@@ -1276,6 +1306,8 @@ class LlamaTP:
         if all_rows and past is None:
             raise ValueError("all_rows needs past (a verify step reads its context from the cache)")
         ids, positions, lens = ids.contiguous(), positions.contiguous(), lens.contiguous()
+        if past is None and not decode and self.kv_prefill == "cache":
+            past = torch.zeros(B, dtype=torch.int32, device=self.device)  # one shot = the chunk at past 0
         if past is not None:
             if decode:
                 raise ValueError("past is a prefill argument")

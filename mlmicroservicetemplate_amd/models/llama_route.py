@@ -80,11 +80,11 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
                head_dim: int, hidden: int, have_packed: bool, have_w4: bool, have_fp8: bool, o_packed: bool,
                o_fp8: bool, w4_max_rows: int, pk_fold: bool, prefill_fold: bool, fuse_combine: bool,
                fuse_add_norm: bool, ar_fuse: bool, tp_overlap: bool, verify_attn: str, spec_max_tokens: int,
-               dec_chunk: int, ar_fusable: bool, capturing: bool) -> StepRoute:
+               dec_chunk: int, ar_fusable: bool, capturing: bool, kv_fp8: bool = False) -> StepRoute:
     """``have_*``: the model holds such copies at all; ``o_packed`` / ``o_fp8``: of ``l0.o``;
     ``ar_fusable``: the comm's one-shot all-reduce can ride in a GEMM producing ``B * S * hidden``
     outputs; ``capturing``: the current stream is capturing a graph.  The rest are the model's
-    dimensions on this rank and its switches under their own names."""
+    dimensions on this rank and its switches under their own names; ``kv_fp8``: the cache is e4m3."""
     T = B * S
     proj = proj_tiers(T, have_packed, have_w4, have_fp8, w4_max_rows)
     # TP = 1: the residual add rides in the o / down epilogues (h = r + a Wo^T, r' = h + g Wd^T), so
@@ -112,9 +112,10 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
     # a verify step (all_rows: every row's candidates) of a few positions per sequence: its attention
     # runs split-KV on the matrix cores with the T positions x G heads of a KV head on one MFMA's lane
     # columns (ops.decode_attention_multi); MLS_VERIFY_ATTN=ctx keeps the chunk kernel (the A/B arm).
-    # Chunked prefill (all_rows False) stays on flash_attention_ctx.
+    # Chunked prefill (all_rows False) stays on flash_attention_ctx.  An e4m3 cache has no verify kernel
+    # of its own: its verify steps take the context kernel too (ops.flash_attention_ctx_fp8, split-KV).
     multi = (has_past and all_rows and verify_attn != "ctx" and S <= spec_max_tokens
-             and S * (hq // max(hkv, 1)) <= 16)
+             and S * (hq // max(hkv, 1)) <= 16 and not kv_fp8)
     # TP prefill: two batch halves interleaved so each o / down all-reduce overlaps the other half's
     # compute (LlamaTP._prefill_overlapped); MLS_TP_OVERLAP=0 runs the plain layer loop
     overlap = not decode and not has_past and tp > 1 and B >= 2 and T >= 64 and tp_overlap and not capturing

@@ -116,6 +116,7 @@ from .transformer import (  # noqa: F401
     embedding,
     flash_attention,
     flash_attention_ctx,
+    flash_attention_ctx_fp8,
     flash_attention_rows,
     flash_ctx_workspace_elems,
     kv_append,

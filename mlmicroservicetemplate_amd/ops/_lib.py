@@ -101,6 +101,9 @@ _SIGS = {
     "mls_flash_attention_rows": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P, I, F, P],
     "mls_flash_attention_ctx": [P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, F, P],
     "mls_flash_attention_ctx_split": [P, P, P, P, P, L, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F, P],
+    "mls_flash_attention_ctx_fp8": [P, P, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, F, P],
+    "mls_flash_attention_ctx_fp8_split": [P, P, P, P, P, P, P, L, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F,
+                                          P],
     "mls_decode_attention_multi": [P, P, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F, P],
     "mls_decode_combine": [P, P, P, I, P, I, I, I, I, P],
     "mls_skinny_gemm": [P, P, P, P, P, P, SZ, I, I, I, I, I, P],

@@ -19,6 +19,7 @@
 //     to.  Each run gets its own buffer descriptor -- a 64-bit base and the run's valid bytes -- so
 //     caches beyond 4 GiB are addressed exactly, rows >= lens[b] (and anything past the slot's rows)
 //     read as zero through the hardware range check, and lane offsets stay 16-bit constants.
+// flash_ctx_fp8_kernel (below the split-KV kernels) is the same launch pair on an e4m3 cache.
 #include "attn_tiles.h"
 
 namespace {
@@ -384,7 +385,254 @@ int ctx_args(CtxArgs& a, const void* qkv, const void* k_cache, const void* v_cac
   return 0;
 }
 
+// ---- e4m3 caches (kv_fp8.hip's layout): the chunk path of kv_prefill="cache" ------------------------
+// uint8 caches [blocks][Hkv][R][128] with one fp32 scale per (row, KV head) in [blocks][Hkv][R].  A
+// 64-key tile of a head is one contiguous 8 KiB run of bytes and one 256-B run of scales; each of the
+// four runs (K, V, their scales) gets its own descriptor, valid up to the rows below lens[b].  One
+// kernel text for the unsplit and the split launch (SPLIT: flash_ctx_split_kernel's tile bounds and
+// partial epilogue, so flash_ctx_combine_kernel merges it); tile body, LDS images, page-table
+// read-ahead, masks and MLS_CHECK codes are the bf16 kernels'.
+//
+// Dequantisation is in the staging step: a 16-B load is 16 dims of one row, converted exactly (e4m3 ->
+// fp32), the fp32 product with the row's scale is rounded to bf16 (RNE) into the same LDS
+// images -- so the MFMAs see bf16(e4m3 * scale), one rounding of relative 2^-9 per element on top of
+// what the cache holds (the reference attends the unrounded fp32 product).  The alternative of
+// decode_attn_fp8_kernel (K scale on the S^T row, V scale folded into P) would need the scales inside
+// Flash2Tile, which the bf16 kernels share: not taken.  A row past lens[b] reads zero bytes and a zero
+// scale: a zero row, as in the bf16 kernel.
+struct CtxFp8Args {
+  CtxSplitArgs s;      // s.c.kc / s.c.vc are unused: the caches are k8 / v8
+  const uint8_t* k8;
+  const uint8_t* v8;
+  const float* ksc;
+  const float* vsc;
+};
+
+MLS_DEV float bload_f32(rsrc_t r, int byte_off) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
+}
+
+// 8 e4m3 bytes of a row times the row's scale -> 8 bf16: e4m3 -> fp32 is exact (what fp8x8_to_bf16 of
+// kv_fp8.hip yields, without its detour through bf16), one fp32 product, one rounding
+MLS_DEV uint4 fp8x8_dequant(uint32_t d0, uint32_t d1, float sc) {
+  const f32x2 s2 = {sc, sc};
+  const f32x2 f0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, false) * s2;
+  const f32x2 f1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, true) * s2;
+  const f32x2 f2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, false) * s2;
+  const f32x2 f3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, true) * s2;
+  bf16x8 r;
+  r[0] = (bf16)f0[0]; r[1] = (bf16)f0[1]; r[2] = (bf16)f1[0]; r[3] = (bf16)f1[1];
+  r[4] = (bf16)f2[0]; r[5] = (bf16)f2[1]; r[6] = (bf16)f3[0]; r[7] = (bf16)f3[1];
+  return __builtin_bit_cast(uint4, r);
+}
+
+// c ? a : b per dword (v_cndmask; a select of the whole vector went through scratch)
+MLS_DEV uint4 sel16(int c, uint4 a, uint4 b) {
+  return make_uint4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w);
+}
+
+template <bool SPLIT>
+__global__ __launch_bounds__(256, 3) void flash_ctx_fp8_kernel(const CtxFp8Args fa) {
+  const CtxSplitArgs& sa = fa.s;
+  const CtxArgs& a = sa.c;
+  constexpr int D = 128, NW = 4;
+  using T = FlashTile<D>;
+  constexpr int NT = 64 * NW;
+  constexpr int BQ = 16 * NW, BKV = T::BKV, CPR = T::CPR;
+  __shared__ __attribute__((aligned(16))) char smem[T::K_BYTES + T::V_BYTES];
+  char* Ks = smem;
+  char* Vs = smem + T::K_BYTES;
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4, fr = lane & 15;
+  const int nsplit = SPLIT ? sa.nsplit : 1;
+  const int b = blockIdx.z / nsplit, sp = blockIdx.z % nsplit, h = blockIdx.y;
+  const int hk = h / (a.Hq / a.Hkv);
+  const int q0 = blockIdx.x * BQ;
+  const int qw = q0 + wid * 16;
+  const bool paged = a.page_table != nullptr;
+
+  const int slot = __builtin_amdgcn_readfirstlane(a.slot_ids ? a.slot_ids[b] : b);
+  const int L0 = __builtin_amdgcn_readfirstlane(a.lens[b]);
+  const int P0 = __builtin_amdgcn_readfirstlane(a.past[b]);
+  const bool slot_ok = slot >= 0 && slot < a.slots;
+  MLS_CHECK(slot_ok, 312);
+  MLS_CHECK(P0 >= 0 && P0 <= L0 && L0 <= a.rows_cap, 311);
+  const int L = slot_ok ? min(L0, a.rows_cap) : 0;
+  const int P = max(0, min(P0, L));
+  const int n = min(L - P, a.S);
+  const long tokq = (long)b * a.S;
+
+  if (q0 >= n) {  // padding rows only: zeros here, or (split) from the combine
+    if (!SPLIT)
+      for (int c = tid; c < BQ * CPR; c += NT) {
+        const int q = q0 + c / CPR;
+        if (q < a.S) st16(a.o + (tokq + q) * a.o_stride + (long)h * D + (c % CPR) * 8, make_uint4(0, 0, 0, 0));
+      }
+    return;
+  }
+
+  const rsrc_t qr = make_rsrc(a.q, a.q_bytes);
+  bf16x8 qf[T::KK];
+  {
+    const int q = qw + fr;
+#pragma unroll
+    for (int kk = 0; kk < T::KK; ++kk) {
+      const int off = q < a.S ? (int)(((tokq + q) * a.q_stride + (long)h * D + 32 * kk + 8 * g) * 2) : OOB;
+      qf[kk] = __builtin_bit_cast(bf16x8, bload16(qr, off));
+    }
+  }
+
+  f32x4 acc_o[T::DT];
+#pragma unroll
+  for (int dt = 0; dt < T::DT; ++dt) acc_o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m_run = -1e30f, l_run = 0.f;
+
+  const int kv_end = min(L, P + q0 + BQ);
+  const int ntiles = (kv_end + BKV - 1) / BKV;
+  MLS_CHECK(!SPLIT || ntiles <= sa.nsplit * sa.tiles_per_split, 314);
+  const int kt0 = SPLIT ? sp * sa.tiles_per_split : 0;  // this block's run of key tiles: [kt0, kt1)
+  const int kt1 = SPLIT ? min(kt0 + sa.tiles_per_split, ntiles) : ntiles;
+  const int pw = P + qw;
+
+  // a tile: 64 rows x 128 B = 512 chunks of 16 B (16 dims of one row), two per thread and cache;
+  // chunk idx = tid + NT i is bytes [16 (idx & 7), +16) of row idx >> 3
+  constexpr int NI = BKV * D / 16 / NT;
+  const int* tab = paged ? a.page_table + (long)slot * a.pages_per_seq : nullptr;
+  auto page_of = [&](int kt) { return paged && kt < kt1 ? __builtin_amdgcn_readfirstlane(tab[kt]) : 0; };
+  uint4 kreg[NI], vreg[NI];
+  float ksr[NI], vsr[NI];
+  auto load_tile = [&](int kt, int pg) {
+    const bool blk_ok = !paged || (pg >= 0 && pg < a.blocks);
+    MLS_CHECK(blk_ok, 313);
+    const long row0 = paged ? ((long)(blk_ok ? pg : 0) * a.Hkv + hk) * BKV
+                            : ((long)slot * a.Hkv + hk) * a.block_rows + (long)kt * BKV;
+    const uint32_t rows = blk_ok ? (uint32_t)min(BKV, L - kt * BKV) : 0u;
+    const rsrc_t kr = make_rsrc(fa.k8 + row0 * D, rows * D);
+    const rsrc_t vr = make_rsrc(fa.v8 + row0 * D, rows * D);
+    const rsrc_t ksd = make_rsrc(fa.ksc + row0, rows * 4);
+    const rsrc_t vsd = make_rsrc(fa.vsc + row0, rows * 4);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const int idx = tid + NT * i;
+      kreg[i] = bload16(kr, idx * 16);
+      vreg[i] = bload16(vr, idx * 16);
+      ksr[i] = bload_f32(ksd, (idx >> 3) * 4);
+      vsr[i] = bload_f32(vsd, (idx >> 3) * 4);
+    }
+  };
+  const float c = a.scale_log2;
+  const int causal = 1;
+  const Flash2Tile<D, true> tile_body{acc_o, m_run, l_run, qf, Ks, Vs, causal, pw, L, c, g, fr};
+  if (kt0 < kt1) {
+    int pg_next = page_of(kt0 + 1);
+    load_tile(kt0, page_of(kt0));
+    for (int kt = kt0; kt < kt1; ++kt) {
+      const int kv0 = kt * BKV;
+#pragma unroll
+      for (int i = 0; i < NI; ++i) {
+        const int idx = tid + NT * i;
+        const int row = idx >> 3, ch = (idx & 7) * 2;  // the load's dims are the row's 16-B chunks ch, ch + 1
+        const uint4 k0 = fp8x8_dequant(kreg[i].x, kreg[i].y, ksr[i]), k1 = fp8x8_dequant(kreg[i].z, kreg[i].w, ksr[i]);
+        const uint4 v0 = fp8x8_dequant(vreg[i].x, vreg[i].y, vsr[i]), v1 = fp8x8_dequant(vreg[i].z, vreg[i].w, vsr[i]);
+        // 16 lanes (two rows, an even and an odd one) per 256-B LDS pass: the K swizzle already puts the
+        // odd row's even chunks on odd 16-B bank groups; in the V image (row stride 256 + 32 B) the odd
+        // row writes its second chunk first for the same effect
+        const int od = row & 1;
+        const int ca = ch + od, cb = ch + 1 - od;
+        *reinterpret_cast<uint4*>(Ks + row * (D * 2) + ((ch ^ (row & (CPR - 1))) * 16)) = k0;
+        *reinterpret_cast<uint4*>(Vs + row * T::VST + ca * 16) = sel16(od, v1, v0);
+        *reinterpret_cast<uint4*>(Ks + row * (D * 2) + (((ch + 1) ^ (row & (CPR - 1))) * 16)) = k1;
+        *reinterpret_cast<uint4*>(Vs + row * T::VST + cb * 16) = sel16(od, v0, v1);
+      }
+      __syncthreads();
+      if (kt + 1 < kt1) {
+        load_tile(kt + 1, pg_next);
+        pg_next = page_of(kt + 2);
+      }
+      tile_body(kv0, kv0 + BKV > L || kv0 + BKV - 1 > pw);
+      __syncthreads();
+    }
+  }
+
+  float l = l_run + xor16_f(l_run);
+  l += xor32_f(l);
+  if (SPLIT) {  // the partial as it stands (flash_ctx_split_kernel's epilogue)
+    const int q = qw + fr;
+    if (q < a.S) {
+      const long row = ((long)sp * a.B * a.S + tokq + q) * a.Hq + h;
+      float* po = sa.ws_o + row * D + 4 * g;
+#pragma unroll
+      for (int dt = 0; dt < T::DT; ++dt)
+        *reinterpret_cast<float4*>(po + 16 * dt) = make_float4(acc_o[dt][0], acc_o[dt][1], acc_o[dt][2], acc_o[dt][3]);
+      if (g == 0) *reinterpret_cast<float2*>(sa.ws_ml + row * 2) = make_float2(m_run, l);
+    }
+    return;
+  }
+  // ---- normalise and store through LDS as 16-B row stores (flash_ctx_kernel's epilogue)
+  const float inv_l = l > 0.f ? 1.f / l : 0.f;
+  constexpr int OST = T::OST;
+  bf16* Os = reinterpret_cast<bf16*>(smem) + wid * 16 * OST;
+#pragma unroll
+  for (int dt = 0; dt < T::DT; ++dt) {
+    bf16x4 o4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o4[j] = (bf16)(acc_o[dt][j] * inv_l);
+    *reinterpret_cast<bf16x4*>(Os + fr * OST + 16 * dt + 4 * g) = o4;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int cc = lane; cc < 16 * CPR; cc += 64) {
+    const int r = cc / CPR, ch = cc % CPR;
+    const int q = qw + r;
+    // rows at or past the batch row's valid length: zeros, as on the split route
+    if (q < a.S)
+      st16(a.o + (tokq + q) * a.o_stride + (long)h * D + ch * 8,
+           q < n ? ld16(Os + r * OST + ch * 8) : make_uint4(0, 0, 0, 0));
+  }
+}
+
 }  // namespace
+
+// both e4m3 launches: nsplit = 0 the unsplit kernel (no workspace), else the split kernel + the combine
+static int ctx_fp8_launch(const void* qkv, const void* k_cache, const void* v_cache, const float* k_scale,
+                          const float* v_scale, void* o, void* workspace, long ws_elems, int q_stride, int o_stride,
+                          const int* past, const int* lens, const int* slot_ids, const int* page_table,
+                          int pages_per_seq, int slots, int B, int S, int Hq, int Hkv, int D, long blocks, int hm_rows,
+                          int max_ctx, int nsplit, float scale, void* stream) {
+  CtxFp8Args fa{};
+  CtxSplitArgs& sa = fa.s;
+  const int rc = ctx_args(sa.c, qkv, k_cache, v_cache, o, q_stride, o_stride, past, lens, slot_ids, page_table,
+                          pages_per_seq, slots, B, S, Hq, Hkv, D, blocks, hm_rows, scale);
+  if (rc) return rc;
+  if (!k_scale || !v_scale) return MLS_BAD_ARG;
+  if ((reinterpret_cast<uintptr_t>(k_scale) | reinterpret_cast<uintptr_t>(v_scale)) & 3) return MLS_BAD_ARG;
+  sa.c.kc = sa.c.vc = nullptr;
+  fa.k8 = (const uint8_t*)k_cache;
+  fa.v8 = (const uint8_t*)v_cache;
+  fa.ksc = k_scale;
+  fa.vsc = v_scale;
+  if (nsplit == 0) {
+    sa.nsplit = 1;
+    dim3 grid((S + 63) / 64, Hq, B);
+    hipLaunchKernelGGL(flash_ctx_fp8_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, fa);
+    return (int)hipGetLastError();
+  }
+  if (nsplit < 1 || nsplit > 64 || max_ctx < 1 || !workspace) return MLS_BAD_ARG;
+  sa.nsplit = nsplit;
+  if (reinterpret_cast<uintptr_t>(workspace) & 15) return MLS_BAD_ARG;
+  const long rows = (long)B * S * Hq;
+  if ((long)B * nsplit > 65535 || rows > 0x7FFFFFFFl / 8) return MLS_BAD_ARG;
+  if (ws_elems < (long)nsplit * rows * (D + 2)) return MLS_BAD_ARG;
+  const int ntiles = ((max_ctx < sa.c.rows_cap ? max_ctx : sa.c.rows_cap) + 63) / 64;
+  sa.tiles_per_split = (ntiles + nsplit - 1) / nsplit;
+  sa.ws_o = (float*)workspace;
+  sa.ws_ml = sa.ws_o + (long)nsplit * rows * D;
+  dim3 grid((S + 63) / 64, Hq, B * nsplit);
+  hipLaunchKernelGGL(flash_ctx_fp8_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, fa);
+  hipLaunchKernelGGL(flash_ctx_combine_kernel, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, (hipStream_t)stream, sa);
+  return (int)hipGetLastError();
+}
 
 extern "C" {
 
@@ -460,6 +708,31 @@ int mls_flash_attention_ctx_split(const void* qkv, const void* k_cache, const vo
   hipLaunchKernelGGL(flash_ctx_split_kernel, grid, dim3(256), 0, (hipStream_t)stream, sa);
   hipLaunchKernelGGL(flash_ctx_combine_kernel, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, (hipStream_t)stream, sa);
   return (int)hipGetLastError();
+}
+
+// mls_flash_attention_ctx / _split on an e4m3 cache (kv_fp8.hip's layout): k_cache / v_cache uint8
+// [blocks][Hkv][hm_rows][128], k_scale / v_scale fp32 [blocks][Hkv][hm_rows]; every other argument as
+// the bf16 entry points take it, the split partials merged by the same combine kernel.
+int mls_flash_attention_ctx_fp8(const void* qkv, const void* k_cache, const void* v_cache, const float* k_scale,
+                                const float* v_scale, void* o, int q_stride, int o_stride, const int* past,
+                                const int* lens, const int* slot_ids, const int* page_table, int pages_per_seq,
+                                int slots, int B, int S, int Hq, int Hkv, int D, long blocks, int hm_rows, float scale,
+                                void* stream) {
+  return ctx_fp8_launch(qkv, k_cache, v_cache, k_scale, v_scale, o, nullptr, 0, q_stride, o_stride, past, lens,
+                        slot_ids, page_table, pages_per_seq, slots, B, S, Hq, Hkv, D, blocks, hm_rows, 0, 0, scale,
+                        stream);
+}
+
+int mls_flash_attention_ctx_fp8_split(const void* qkv, const void* k_cache, const void* v_cache, const float* k_scale,
+                                      const float* v_scale, void* o, void* workspace, long ws_elems, int q_stride,
+                                      int o_stride, const int* past, const int* lens, const int* slot_ids,
+                                      const int* page_table, int pages_per_seq, int slots, int B, int S, int Hq,
+                                      int Hkv, int D, long blocks, int hm_rows, int max_ctx, int nsplit, float scale,
+                                      void* stream) {
+  if (nsplit < 1) return MLS_BAD_ARG;
+  return ctx_fp8_launch(qkv, k_cache, v_cache, k_scale, v_scale, o, workspace, ws_elems, q_stride, o_stride, past,
+                        lens, slot_ids, page_table, pages_per_seq, slots, B, S, Hq, Hkv, D, blocks, hm_rows, max_ctx,
+                        nsplit, scale, stream);
 }
 
 }  // extern "C"

@@ -543,6 +543,86 @@ def rope_kv_fp8_(qkv: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, 
     return qkv
 
 
+def flash_attention_ctx_fp8(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: torch.Tensor,
+                            v_scale: torch.Tensor, past: torch.Tensor, lens: torch.Tensor, batch: int, seq: int,
+                            n_q_heads: int, n_kv_heads: int, head_dim: int, *,
+                            slot_ids: Optional[torch.Tensor] = None, page_table: Optional[torch.Tensor] = None,
+                            scale: Optional[float] = None, out: Optional[torch.Tensor] = None, splits: int = 1,
+                            max_ctx: Optional[int] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`flash_attention_ctx` on an FP8 (e4m3) cache: the contract, arguments and split-KV route
+    (``splits``, ``max_ctx``, ``workspace`` of :func:`flash_ctx_workspace_elems` elements) are that
+    function's; the caches are :func:`rope_kv_fp8_`'s -- head-major uint8 ``[slots, Hkv, max_seq, 128]``
+    or page pools ``[pages, Hkv, 64, 128]`` with fp32 scales of the same shape without the last
+    dimension.  A row is attended as ``bf16(e4m3 * scale)``; padding rows (at or past a row's valid
+    length) are zeros on both routes; the oracle is
+    ``reference.attention_ctx`` on ``reference.kv_dequant_fp8`` of the same bytes."""
+    dev = qkv.device
+    splits = int(splits)
+    if splits < 1 or splits > 64:
+        raise ValueError(f"flash_attention_ctx_fp8: splits must be in [1, 64], got {splits}")
+    if splits > 1 and max_ctx is None:
+        raise ValueError("flash_attention_ctx_fp8: splits > 1 needs max_ctx (a host bound on lens)")
+    _need(qkv, "qkv", torch.bfloat16, dev)
+    _need_kv_fp8(k_cache, v_cache, k_scale, v_scale, n_kv_heads, head_dim, dev)
+    _need(past, "past", torch.int32, dev)
+    _need(lens, "lens", torch.int32, dev)
+    if batch <= 0 or seq <= 0 or n_kv_heads <= 0 or n_q_heads % n_kv_heads:
+        raise ValueError("batch, seq > 0 and Hq a multiple of Hkv")
+    W = (n_q_heads + 2 * n_kv_heads) * head_dim
+    if qkv.dim() != 2 or tuple(qkv.shape) != (batch * seq, W):
+        raise ValueError("qkv shape does not match batch/seq/heads")
+    if past.numel() != batch or lens.numel() != batch:
+        raise ValueError(f"past and lens must have {batch} elements")
+    blocks, rows = k_cache.shape[0], k_cache.shape[2]
+    if slot_ids is not None:
+        _need(slot_ids, "slot_ids", torch.int32, dev)
+        if slot_ids.numel() != batch:
+            raise ValueError(f"slot_ids must have {batch} elements")
+    if page_table is not None:
+        _need(page_table, "page_table", torch.int32, dev)
+        if page_table.dim() != 2:
+            raise ValueError("page_table must be [slots, pages_per_seq]")
+        if rows != 64:
+            raise ValueError(f"paged flash_attention_ctx_fp8: pages of 64 rows (one K/V tile), got {rows}")
+        slots, pps = page_table.shape
+    else:
+        slots, pps = blocks, 0
+    if slot_ids is None and batch > slots:
+        raise ValueError("the cache holds fewer slots than the batch")
+    if out is not None:
+        _need(out, "out", torch.bfloat16, dev)
+        if out.dim() != 2 or out.shape[0] < batch * seq or out.shape[1] != n_q_heads * head_dim:
+            raise ValueError("out must be [B*S, Hq*D]")
+    else:
+        out = torch.empty(batch * seq, n_q_heads * head_dim, device=dev, dtype=torch.bfloat16)
+    scale = head_dim ** -0.5 if scale is None else scale
+    caches = (k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr())
+    tail = (past.data_ptr(), lens.data_ptr(), _ptr(slot_ids), _ptr(page_table), pps, slots, batch, seq, n_q_heads,
+            n_kv_heads, head_dim, blocks, rows)
+    if splits > 1:
+        if int(max_ctx) < 1:
+            raise ValueError(f"flash_attention_ctx_fp8: max_ctx must be positive, got {max_ctx}")
+        need = flash_ctx_workspace_elems(batch, seq, n_q_heads, head_dim, splits)
+        if workspace is None:
+            workspace = torch.empty(need, device=dev, dtype=torch.float32)
+        _need(workspace, "workspace", torch.float32, dev)
+        if workspace.numel() < need or not workspace.is_contiguous():
+            raise ValueError(f"flash_attention_ctx_fp8: the workspace holds {workspace.numel()} fp32 elements, "
+                             f"{splits} splits need {need} (contiguous)")
+        if batch * splits > 65535:
+            raise ValueError(f"flash_attention_ctx_fp8: batch x splits = {batch * splits} exceeds the grid's 65535")
+        rc = lib().mls_flash_attention_ctx_fp8_split(qkv.data_ptr(), *caches, out.data_ptr(), workspace.data_ptr(),
+                                                     workspace.numel(), W, out.stride(0), *tail,
+                                                     min(int(max_ctx), 0x7FFFFFFF), splits, float(scale),
+                                                     stream_ptr(dev))
+        check(rc, "mls_flash_attention_ctx_fp8_split")
+        return out
+    rc = lib().mls_flash_attention_ctx_fp8(qkv.data_ptr(), *caches, out.data_ptr(), W, out.stride(0), *tail,
+                                           float(scale), stream_ptr(dev))
+    check(rc, "mls_flash_attention_ctx_fp8")
+    return out
+
+
 def decode_attention_fp8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: torch.Tensor,
                          v_scale: torch.Tensor, lens: torch.Tensor, n_q_heads: int, n_kv_heads: int, head_dim: int, *,
                          chunk: int = 64, scale: Optional[float] = None, workspace: Optional[torch.Tensor] = None,

@@ -39,6 +39,7 @@ class LlamaPlugin(ModelPlugin):
         self.prefill_chunk = 0
         self.speculate, self.speculate_ngram = 0, 3
         self.prefix_cache = False
+        self.kv_pages = 0
         self._lock = threading.Lock()
 
     def init(self, ctx: PluginContext) -> None:
@@ -68,7 +69,9 @@ class LlamaPlugin(ModelPlugin):
         self.prefill_chunk = int(extra.get("prefill_chunk", 0) or 0)
         if self.prefill_chunk < 0:
             raise ValueError(f"prefill_chunk must be >= 0, got {self.prefill_chunk}")
-        if self.prefill_chunk and kv_dtype == "fp8":  # LlamaTP.check_prefill_chunk's rule
+        # MODEL_CONFIG kv_prefill: rows | cache (fp8 only: prefill attends the e4m3 cache rows, LlamaTP(kv_prefill=))
+        kv_prefill = str(extra.get("kv_prefill", "rows"))
+        if self.prefill_chunk and kv_dtype == "fp8" and kv_prefill != "cache":  # LlamaTP.check_prefill_chunk's rule
             raise ValueError("prefill_chunk is not available with kv_dtype: fp8 (a chunk would attend e4m3 context "
                              "rows where one-shot prefill attends unquantised ones)")
         kv_pages = self._kv_pages(extra.get("kv_pages", 0), cfg, tp, max_batch, max_seq, dev, backend, kv_dtype)
@@ -78,10 +81,10 @@ class LlamaPlugin(ModelPlugin):
             kv_pages = int(-mdist.max_over_ranks(-float(kv_pages)))
         self.model = llama.LlamaTP(params, cfg, tp=tp, rank=ctx.rank, comm=llama.TPComm(None, tp, device=dev), backend=backend,
                                    device=dev, max_batch=max_batch, max_seq=max_seq, kv_pages=kv_pages,
-                                   kv_dtype=kv_dtype, weight_dtype=weight_dtype)
+                                   kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_prefill=kv_prefill)
         if self.speculate:  # refused at start-up on the lockstep path too (the engine below checks for itself)
             self.model.check_speculate(self.speculate)
-        if self.prefix_cache:  # no paged KV, fp8 KV, row-major cache, head_dim != 128: refused, nothing falls back
+        if self.prefix_cache:  # no paged KV, fp8 KV with kv_prefill: rows, row-major cache, head_dim != 128: refused, nothing falls back
             self.model.check_prefix_cache()
             if not bool(getattr(s, "CONTINUOUS_BATCHING", True)):
                 raise ValueError("prefix_cache needs continuous batching (the lockstep generate path has no page sharing)")
@@ -96,10 +99,11 @@ class LlamaPlugin(ModelPlugin):
                                           drafter=self._drafter(), prefix_cache=self.prefix_cache)
             if ctx.rank == 0:
                 self.engine.start()
-        logger.info("llama ready: tp=%d rank=%d backend=%s device=%s kv_dtype=%s kv_bytes_per_token=%d "
+        self.kv_pages = kv_pages
+        logger.info("llama ready: tp=%d rank=%d backend=%s device=%s kv_dtype=%s kv_prefill=%s kv_bytes_per_token=%d "
                     "weight_dtype=%s layer_weight_bytes=%d prefix_cache=%s", tp, ctx.rank, backend, dev, kv_dtype,
-                    self.kv_page_bytes(cfg, tp, backend, kv_dtype) // 64, weight_dtype, self.model.layer_weight_bytes(),
-                    self.prefix_cache)
+                    kv_prefill, self.kv_page_bytes(cfg, tp, backend, kv_dtype) // 64, weight_dtype,
+                    self.model.layer_weight_bytes(), self.prefix_cache)
 
     @staticmethod
     def parse_weight_dtype(extra: dict) -> str:
@@ -399,5 +403,7 @@ class LlamaPlugin(ModelPlugin):
         if self.model is not None:
             d.update({"tp": self.model.tp, "backend": self.model.backend, "max_batch": self.model.max_batch,
                       "max_seq": self.model.max_seq, "speculate": self.speculate,
-                      "speculate_ngram": self.speculate_ngram, "prefix_cache": self.prefix_cache})
+                      "speculate_ngram": self.speculate_ngram, "prefix_cache": self.prefix_cache,
+                      "kv_dtype": self.model.kv_dtype, "kv_prefill": self.model.kv_prefill,
+                      "kv_pages": self.kv_pages, "prefill_chunk": self.prefill_chunk})
         return d

@@ -195,7 +195,8 @@ def bench_llama_prefix(args):
         raise SystemExit("--shared-prefix measures the paged cache: give --kv-pages")
     p = init_llama_shard(LLAMA3_8B, 1, 0, seed=0, device=dev)
     m = LlamaTP(p, LLAMA3_8B, backend="fused", device=dev, max_batch=B, max_seq=args.max_seq, kv_pages=args.kv_pages,
-                kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype)
+                kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype,
+                kv_prefill=args.kv_prefill)
     del p
     shared = np.random.default_rng(1).integers(1000, 100000, N).tolist()
 
@@ -263,13 +264,15 @@ def bench_llama(args):
     p = init_llama_shard(LLAMA3_8B, tp, 0, seed=0, device=dev)
     comm = ShardEmulationComm(tp) if tp > 1 else None
     m = LlamaTP(p, LLAMA3_8B, tp=tp, rank=0, comm=comm, backend="fused", device=dev, max_batch=max(args.batches),
-                max_seq=args.max_seq, kv_pages=args.kv_pages, kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype)
+                max_seq=args.max_seq, kv_pages=args.kv_pages, kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype,
+                kv_prefill=args.kv_prefill)
     if m.pages is not None and args.shuffle_pages:  # pages scattered as in a long-running server
         import random
 
         random.Random(0).shuffle(m.pages._free)
     print(json.dumps({"bench": "llama3-8b", "tp": tp, "collectives": "stubbed" if tp > 1 else "none",
                       "skinny_max_split": args.skinny_max_split, "kv_pages": args.kv_pages, "kv_dtype": args.kv_dtype,
+                      "kv_prefill": args.kv_prefill,
                       "weight_dtype": args.weight_dtype, "layer_weight_bytes": m.layer_weight_bytes(),
                       "init_s": round(time.time() - t0, 1)}), flush=True)
     for B in args.batches:
@@ -301,7 +304,7 @@ def bench_llama(args):
         torch.cuda.synchronize()
         dec = (time.perf_counter() - t2) / n
         print(json.dumps({"bench": "llama3-8b", "tp": tp, "batch": B, "prompt": S, "kv_pages": args.kv_pages,
-                          "kv_dtype": args.kv_dtype, "weight_dtype": args.weight_dtype, "prefill_ms": round(pre * 1e3, 2), "prefill_tok_s": round(B * S / pre, 1),
+                          "kv_dtype": args.kv_dtype, "kv_prefill": args.kv_prefill, "weight_dtype": args.weight_dtype, "prefill_ms": round(pre * 1e3, 2), "prefill_tok_s": round(B * S / pre, 1),
                           "decode_ms_per_step": round(dec * 1e3, 3), "decode_tok_s": round(B / dec, 1)}), flush=True)
         for K in args.speculate:
             _bench_speculate(m, args, K, B, S, ids, lens, tok, cur)
@@ -341,7 +344,7 @@ def _bench_speculate(m, args, K, B, S, ids, lens, tok, cur):
     m.verify_attn = "multi"
     med = {a: float(np.median(v)) for a, v in times.items()}
     print(json.dumps({"bench": "llama3-8b-verify", "batch": B, "prompt": S, "T": T, "kv_pages": args.kv_pages,
-                      "weight_dtype": args.weight_dtype,
+                      "weight_dtype": args.weight_dtype, "kv_dtype": args.kv_dtype, "kv_prefill": args.kv_prefill,
                       **{a + "_ms": round(v, 3) for a, v in med.items()},
                       **{a + "_ms_min": round(min(times[a]), 3) for a in times},
                       # accepted drafts per step above which a verify step yields more tokens per ms than a decode step
@@ -392,7 +395,8 @@ def bench_llama_serve(args):
     B = args.batches[0]
     p = init_llama_shard(LLAMA3_8B, 1, 0, seed=0, device=dev)
     m = LlamaTP(p, LLAMA3_8B, backend="fused", device=dev, max_batch=B, max_seq=args.max_seq, kv_pages=args.kv_pages,
-                kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype)
+                kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype,
+                kv_prefill=args.kv_prefill)
     eng = ContinuousLlama(m).start()
     rng = np.random.default_rng(0)
     warm = [eng.submit(rng.integers(1000, 100000, args.prompt).tolist(), GenParams(4)) for _ in range(B)]
@@ -408,7 +412,7 @@ def bench_llama_serve(args):
     toks = sum(len(f.result()) for f in futs)
     eng.stop()
     print(json.dumps({"bench": "llama3-8b-continuous", "max_batch": B, "kv_pages": args.kv_pages,
-                      "kv_dtype": args.kv_dtype, "weight_dtype": args.weight_dtype, "requests": args.requests,
+                      "kv_dtype": args.kv_dtype, "kv_prefill": args.kv_prefill, "weight_dtype": args.weight_dtype, "requests": args.requests,
                       "prompt": args.prompt, "new_tokens": args.new, "tokens_per_s": round(toks / dt, 1),
                       "requests_per_s": round(args.requests / dt, 2), "p50_latency_s": round(float(np.median(lat)), 3),
                       "iterations": eng.iterations}), flush=True)
@@ -434,6 +438,9 @@ def main():
     ap.add_argument("--kv-pages", type=int, default=0, help="llama: paged KV pool of N 64-row pages (0: per-slot)")
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
                     help="llama: KV cache rows in bf16, or e4m3 with one fp32 scale per (row, KV head)")
+    ap.add_argument("--kv-prefill", choices=["rows", "cache"], default="rows",
+                    help="llama, --kv-dtype fp8: prefill attends its own bf16 rows, or the e4m3 cache rows (which "
+                         "chunked prefill, prefix caching and speculation need)")
     ap.add_argument("--weight-dtype", choices=["bf16", "int4"], default="bf16",
                     help="llama: layer projections in bf16, or W4A16 (4-bit codes, one bf16 scale per row and 128 k)")
     ap.add_argument("--max-seq", type=int, default=2048, help="llama: cache rows per sequence")
