@@ -5,10 +5,11 @@
 //
 // Flash2Tile and DecodeMerge are closures written out -- a struct of references with a call operator,
 // in an unnamed namespace, not force-inlined: what a local lambda of the kernel is to the compiler.
-// That form compiles flash_ctx_kernel and flash_fwd2_kernel to the instruction stream they had with the
+// That form compiles flash_ctx_kernel<FP8, SPLIT> and flash_fwd2_kernel to the instruction stream they had with the
 // tile body as a local lambda; as a force-inlined function of the same text it took 4-8 VGPRs more and
 // measured 0.6-0.8 % slower at long contexts (docs/PERF_NOTES.md).  For the same reason the kernels
-// keep their own staging loop and epilogue: through helpers of either form their instruction stream moved.
+// keep their own staging loop and epilogue: through helpers of either form their instruction stream moved
+// (flash_ctx_kernel's four instantiations share theirs as one text with `if constexpr` in place).
 #pragma once
 #include "common.h"
 
@@ -36,7 +37,7 @@ struct FlashTile {
   static constexpr int ni(int nt) { return BKV * CPR / nt; }  // a tile's 16-B chunks per thread of nt
 };
 
-// The v2 tile body (flash_fwd2_kernel, flash_ctx_kernel): the prefill loop with the O accumulator
+// The v2 tile body (flash_fwd2_kernel, flash_ctx_kernel<FP8, SPLIT>): the prefill loop with the O accumulator
 // transposed and the per-score VALU cut (Llama prefill, D = 128: the v1 loop issued ~450 VALU + ~170
 // SALU per wave per 64-key tile against 32 MFMAs -- 193 TFLOP/s at B = 8 x 512,
 // profiles/r6_flash_llama_probe.txt).  Same tiling and LDS layouts as flash_fwd_kernel; per tile and wave:
@@ -49,7 +50,7 @@ struct FlashTile {
 //   * the key-range / causal mask runs only on the tiles that need it (`EDGE`, a wave-uniform branch),
 //     where 16-key sub-tiles wholly above the diagonal also skip their MFMAs.
 // One tile body with wave-uniform branches, 158 VGPRs in flash_fwd2_kernel<128> (150 in
-// flash_ctx_kernel): 3 waves per SIMD.
+// flash_ctx_kernel on the bf16 cache, 130 on the e4m3 cache): 3 waves per SIMD.
 // (Full and edge tiles as two straight-line copies of the body took 196 VGPRs -- 2 waves per SIMD --
 // and measured 71-73 vs 62 us at B = 8 x 512: profiles/r6_flash_v2_vs_v1.jsonl.)
 //

@@ -231,6 +231,89 @@ def flash_ctx_workspace_elems(batch: int, seq: int, n_q_heads: int, head_dim: in
     return int(splits) * batch * seq * n_q_heads * (head_dim + 2)
 
 
+def _need_kv_hm(k_cache, v_cache, n_kv_heads: int, head_dim: int, dev) -> None:
+    """The bf16 KV cache :func:`flash_attention_ctx` reads: head-major ``[blocks, Hkv, R, 128]``."""
+    _need(k_cache, "k_cache", torch.bfloat16, dev)
+    _need(v_cache, "v_cache", torch.bfloat16, dev)
+    if head_dim != 128:
+        raise ValueError(f"flash_attention_ctx: head_dim must be 128, got {head_dim}")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
+        raise ValueError("k_cache and v_cache must be 4-d and of the same shape")
+    if k_cache.shape[1] != n_kv_heads or k_cache.shape[3] != head_dim:
+        raise ValueError(f"flash_attention_ctx reads head-major caches [blocks, Hkv={n_kv_heads}, rows, {head_dim}] "
+                         f"only (a row-major cache is not supported), got {tuple(k_cache.shape)}")
+
+
+def _flash_attention_ctx(op: str, need_caches, qkv, caches, past, lens, batch: int, seq: int, n_q_heads: int,
+                         n_kv_heads: int, head_dim: int, slot_ids, page_table, scale, out, splits, max_ctx, workspace):
+    """The body of :func:`flash_attention_ctx` and :func:`flash_attention_ctx_fp8`: ``op`` names the
+    caller in the messages and the library's entry points (``mls_<op>`` and ``mls_<op>_split``),
+    ``need_caches(*caches, n_kv_heads, head_dim, dev)`` checks ``caches`` = (k_cache, v_cache[, k_scale,
+    v_scale]), which the entry points take in that order."""
+    dev = qkv.device
+    splits = int(splits)
+    if splits < 1 or splits > 64:
+        raise ValueError(f"{op}: splits must be in [1, 64], got {splits}")
+    if splits > 1 and max_ctx is None:
+        raise ValueError(f"{op}: splits > 1 needs max_ctx (a host bound on lens)")
+    _need(qkv, "qkv", torch.bfloat16, dev)
+    need_caches(*caches, n_kv_heads, head_dim, dev)
+    _need(past, "past", torch.int32, dev)
+    _need(lens, "lens", torch.int32, dev)
+    if batch <= 0 or seq <= 0 or n_kv_heads <= 0 or n_q_heads % n_kv_heads:
+        raise ValueError("batch, seq > 0 and Hq a multiple of Hkv")
+    W = (n_q_heads + 2 * n_kv_heads) * head_dim
+    if qkv.dim() != 2 or tuple(qkv.shape) != (batch * seq, W):
+        raise ValueError("qkv shape does not match batch/seq/heads")
+    if past.numel() != batch or lens.numel() != batch:
+        raise ValueError(f"past and lens must have {batch} elements")
+    blocks, rows = caches[0].shape[0], caches[0].shape[2]
+    if slot_ids is not None:
+        _need(slot_ids, "slot_ids", torch.int32, dev)
+        if slot_ids.numel() != batch:
+            raise ValueError(f"slot_ids must have {batch} elements")
+    if page_table is not None:
+        _need(page_table, "page_table", torch.int32, dev)
+        if page_table.dim() != 2:
+            raise ValueError("page_table must be [slots, pages_per_seq]")
+        if rows != 64:
+            raise ValueError(f"paged {op}: pages of 64 rows (one K/V tile), got {rows}")
+        slots, pps = page_table.shape
+    else:
+        slots, pps = blocks, 0
+    if slot_ids is None and batch > slots:
+        raise ValueError("the cache holds fewer slots than the batch")
+    if out is not None:
+        _need(out, "out", torch.bfloat16, dev)
+        if out.dim() != 2 or out.shape[0] < batch * seq or out.shape[1] != n_q_heads * head_dim:
+            raise ValueError("out must be [B*S, Hq*D]")
+    else:
+        out = torch.empty(batch * seq, n_q_heads * head_dim, device=dev, dtype=torch.bfloat16)
+    scale = head_dim ** -0.5 if scale is None else scale
+    head = (qkv.data_ptr(), *(t.data_ptr() for t in caches), out.data_ptr())
+    tail = (W, out.stride(0), past.data_ptr(), lens.data_ptr(), _ptr(slot_ids), _ptr(page_table), pps, slots, batch,
+            seq, n_q_heads, n_kv_heads, head_dim, blocks, rows)
+    if splits > 1:
+        if int(max_ctx) < 1:
+            raise ValueError(f"{op}: max_ctx must be positive, got {max_ctx}")
+        need = flash_ctx_workspace_elems(batch, seq, n_q_heads, head_dim, splits)
+        if workspace is None:
+            workspace = torch.empty(need, device=dev, dtype=torch.float32)
+        _need(workspace, "workspace", torch.float32, dev)
+        if workspace.numel() < need or not workspace.is_contiguous():
+            raise ValueError(f"{op}: the workspace holds {workspace.numel()} fp32 elements, "
+                             f"{splits} splits need {need} (contiguous)")
+        if batch * splits > 65535:
+            raise ValueError(f"{op}: batch x splits = {batch * splits} exceeds the grid's 65535")
+        rc = getattr(lib(), f"mls_{op}_split")(*head, workspace.data_ptr(), workspace.numel(), *tail,
+                                               min(int(max_ctx), 0x7FFFFFFF), splits, float(scale), stream_ptr(dev))
+        check(rc, f"mls_{op}_split")
+        return out
+    rc = getattr(lib(), f"mls_{op}")(*head, *tail, float(scale), stream_ptr(dev))
+    check(rc, f"mls_{op}")
+    return out
+
+
 def flash_attention_ctx(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, past: torch.Tensor,
                         lens: torch.Tensor, batch: int, seq: int, n_q_heads: int, n_kv_heads: int, head_dim: int, *,
                         slot_ids: Optional[torch.Tensor] = None, page_table: Optional[torch.Tensor] = None,
@@ -244,91 +327,20 @@ def flash_attention_ctx(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
     after this chunk, as :func:`prefill_slots` takes it) / ``slot_ids`` are int32 ``[B]`` on the device;
     nothing is read on the host (capturable).  Head-major bf16 caches only, D = 128:
     ``[slots, Hkv, max_seq, D]``, or page pools ``[pages, Hkv, 64, D]`` through ``page_table
-    [slots, pages_per_seq]``.  Returns ``[B*S, Hq*D]``; rows at or past a row's valid length are
-    unspecified.
+    [slots, pages_per_seq]``.  Returns ``[B*S, Hq*D]``; rows at or past a row's valid length (padding
+    rows) are zeros.
 
     ``splits`` > 1 (at most 64): split-KV -- every (row, query tile)'s key tiles are cut into ``splits``
     runs that separate blocks walk, then merged (few queries against a long context: a prefix-cache
     hit).  It needs ``max_ctx``, a host bound on ``lens`` that fixes where the runs are cut, and an
     fp32 ``workspace`` of :func:`flash_ctx_workspace_elems` elements (allocated when None).  Padding
-    rows are zeros on this route.  ``max_ctx`` is the caller's promise: ``lens`` is device data the host
+    rows are zeros on this route too.  ``max_ctx`` is the caller's promise: ``lens`` is device data the host
     never reads, so a ``lens[b]`` above it is NOT refused -- the key tiles past the last split are
     dropped and that row's result is silently wrong (nothing is read or written out of bounds); only the
     ``MLS_DEBUG`` build reports it (code 314).  A bound that is too large is always safe."""
-    dev = qkv.device
-    splits = int(splits)
-    if splits < 1 or splits > 64:
-        raise ValueError(f"flash_attention_ctx: splits must be in [1, 64], got {splits}")
-    if splits > 1 and max_ctx is None:
-        raise ValueError("flash_attention_ctx: splits > 1 needs max_ctx (a host bound on lens)")
-    _need(qkv, "qkv", torch.bfloat16, dev)
-    _need(k_cache, "k_cache", torch.bfloat16, dev)
-    _need(v_cache, "v_cache", torch.bfloat16, dev)
-    _need(past, "past", torch.int32, dev)
-    _need(lens, "lens", torch.int32, dev)
-    if batch <= 0 or seq <= 0 or n_kv_heads <= 0 or n_q_heads % n_kv_heads:
-        raise ValueError("batch, seq > 0 and Hq a multiple of Hkv")
-    if head_dim != 128:
-        raise ValueError(f"flash_attention_ctx: head_dim must be 128, got {head_dim}")
-    W = (n_q_heads + 2 * n_kv_heads) * head_dim
-    if qkv.dim() != 2 or tuple(qkv.shape) != (batch * seq, W):
-        raise ValueError("qkv shape does not match batch/seq/heads")
-    if past.numel() != batch or lens.numel() != batch:
-        raise ValueError(f"past and lens must have {batch} elements")
-    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
-        raise ValueError("k_cache and v_cache must be 4-d and of the same shape")
-    if k_cache.shape[1] != n_kv_heads or k_cache.shape[3] != head_dim:
-        raise ValueError(f"flash_attention_ctx reads head-major caches [blocks, Hkv={n_kv_heads}, rows, {head_dim}] "
-                         f"only (a row-major cache is not supported), got {tuple(k_cache.shape)}")
-    blocks, rows = k_cache.shape[0], k_cache.shape[2]
-    if slot_ids is not None:
-        _need(slot_ids, "slot_ids", torch.int32, dev)
-        if slot_ids.numel() != batch:
-            raise ValueError(f"slot_ids must have {batch} elements")
-    if page_table is not None:
-        _need(page_table, "page_table", torch.int32, dev)
-        if page_table.dim() != 2:
-            raise ValueError("page_table must be [slots, pages_per_seq]")
-        if rows != 64:
-            raise ValueError(f"paged flash_attention_ctx: pages of 64 rows (one K/V tile), got {rows}")
-        slots, pps = page_table.shape
-    else:
-        slots, pps = blocks, 0
-    if slot_ids is None and batch > slots:
-        raise ValueError("the cache holds fewer slots than the batch")
-    if out is not None:
-        _need(out, "out", torch.bfloat16, dev)
-        if out.dim() != 2 or out.shape[0] < batch * seq or out.shape[1] != n_q_heads * head_dim:
-            raise ValueError("out must be [B*S, Hq*D]")
-    else:
-        out = torch.empty(batch * seq, n_q_heads * head_dim, device=dev, dtype=torch.bfloat16)
-    scale = head_dim ** -0.5 if scale is None else scale
-    if splits > 1:
-        if int(max_ctx) < 1:
-            raise ValueError(f"flash_attention_ctx: max_ctx must be positive, got {max_ctx}")
-        need = flash_ctx_workspace_elems(batch, seq, n_q_heads, head_dim, splits)
-        if workspace is None:
-            workspace = torch.empty(need, device=dev, dtype=torch.float32)
-        _need(workspace, "workspace", torch.float32, dev)
-        if workspace.numel() < need or not workspace.is_contiguous():
-            raise ValueError(f"flash_attention_ctx: the workspace holds {workspace.numel()} fp32 elements, "
-                             f"{splits} splits need {need} (contiguous)")
-        if batch * splits > 65535:
-            raise ValueError(f"flash_attention_ctx: batch x splits = {batch * splits} exceeds the grid's 65535")
-        rc = lib().mls_flash_attention_ctx_split(qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                                 out.data_ptr(), workspace.data_ptr(), workspace.numel(), W,
-                                                 out.stride(0), past.data_ptr(), lens.data_ptr(), _ptr(slot_ids),
-                                                 _ptr(page_table), pps, slots, batch, seq, n_q_heads, n_kv_heads,
-                                                 head_dim, blocks, rows, min(int(max_ctx), 0x7FFFFFFF), splits, float(scale),
-                                                 stream_ptr(dev))
-        check(rc, "mls_flash_attention_ctx_split")
-        return out
-    rc = lib().mls_flash_attention_ctx(qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), W,
-                                       out.stride(0), past.data_ptr(), lens.data_ptr(), _ptr(slot_ids),
-                                       _ptr(page_table), pps, slots, batch, seq, n_q_heads, n_kv_heads, head_dim,
-                                       blocks, rows, float(scale), stream_ptr(dev))
-    check(rc, "mls_flash_attention_ctx")
-    return out
+    return _flash_attention_ctx("flash_attention_ctx", _need_kv_hm, qkv, (k_cache, v_cache), past, lens, batch, seq,
+                                n_q_heads, n_kv_heads, head_dim, slot_ids, page_table, scale, out, splits, max_ctx,
+                                workspace)
 
 
 def decode_attention_multi(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, past: torch.Tensor,
@@ -556,71 +568,9 @@ def flash_attention_ctx_fp8(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: t
     dimension.  A row is attended as ``bf16(e4m3 * scale)``; padding rows (at or past a row's valid
     length) are zeros on both routes; the oracle is
     ``reference.attention_ctx`` on ``reference.kv_dequant_fp8`` of the same bytes."""
-    dev = qkv.device
-    splits = int(splits)
-    if splits < 1 or splits > 64:
-        raise ValueError(f"flash_attention_ctx_fp8: splits must be in [1, 64], got {splits}")
-    if splits > 1 and max_ctx is None:
-        raise ValueError("flash_attention_ctx_fp8: splits > 1 needs max_ctx (a host bound on lens)")
-    _need(qkv, "qkv", torch.bfloat16, dev)
-    _need_kv_fp8(k_cache, v_cache, k_scale, v_scale, n_kv_heads, head_dim, dev)
-    _need(past, "past", torch.int32, dev)
-    _need(lens, "lens", torch.int32, dev)
-    if batch <= 0 or seq <= 0 or n_kv_heads <= 0 or n_q_heads % n_kv_heads:
-        raise ValueError("batch, seq > 0 and Hq a multiple of Hkv")
-    W = (n_q_heads + 2 * n_kv_heads) * head_dim
-    if qkv.dim() != 2 or tuple(qkv.shape) != (batch * seq, W):
-        raise ValueError("qkv shape does not match batch/seq/heads")
-    if past.numel() != batch or lens.numel() != batch:
-        raise ValueError(f"past and lens must have {batch} elements")
-    blocks, rows = k_cache.shape[0], k_cache.shape[2]
-    if slot_ids is not None:
-        _need(slot_ids, "slot_ids", torch.int32, dev)
-        if slot_ids.numel() != batch:
-            raise ValueError(f"slot_ids must have {batch} elements")
-    if page_table is not None:
-        _need(page_table, "page_table", torch.int32, dev)
-        if page_table.dim() != 2:
-            raise ValueError("page_table must be [slots, pages_per_seq]")
-        if rows != 64:
-            raise ValueError(f"paged flash_attention_ctx_fp8: pages of 64 rows (one K/V tile), got {rows}")
-        slots, pps = page_table.shape
-    else:
-        slots, pps = blocks, 0
-    if slot_ids is None and batch > slots:
-        raise ValueError("the cache holds fewer slots than the batch")
-    if out is not None:
-        _need(out, "out", torch.bfloat16, dev)
-        if out.dim() != 2 or out.shape[0] < batch * seq or out.shape[1] != n_q_heads * head_dim:
-            raise ValueError("out must be [B*S, Hq*D]")
-    else:
-        out = torch.empty(batch * seq, n_q_heads * head_dim, device=dev, dtype=torch.bfloat16)
-    scale = head_dim ** -0.5 if scale is None else scale
-    caches = (k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr())
-    tail = (past.data_ptr(), lens.data_ptr(), _ptr(slot_ids), _ptr(page_table), pps, slots, batch, seq, n_q_heads,
-            n_kv_heads, head_dim, blocks, rows)
-    if splits > 1:
-        if int(max_ctx) < 1:
-            raise ValueError(f"flash_attention_ctx_fp8: max_ctx must be positive, got {max_ctx}")
-        need = flash_ctx_workspace_elems(batch, seq, n_q_heads, head_dim, splits)
-        if workspace is None:
-            workspace = torch.empty(need, device=dev, dtype=torch.float32)
-        _need(workspace, "workspace", torch.float32, dev)
-        if workspace.numel() < need or not workspace.is_contiguous():
-            raise ValueError(f"flash_attention_ctx_fp8: the workspace holds {workspace.numel()} fp32 elements, "
-                             f"{splits} splits need {need} (contiguous)")
-        if batch * splits > 65535:
-            raise ValueError(f"flash_attention_ctx_fp8: batch x splits = {batch * splits} exceeds the grid's 65535")
-        rc = lib().mls_flash_attention_ctx_fp8_split(qkv.data_ptr(), *caches, out.data_ptr(), workspace.data_ptr(),
-                                                     workspace.numel(), W, out.stride(0), *tail,
-                                                     min(int(max_ctx), 0x7FFFFFFF), splits, float(scale),
-                                                     stream_ptr(dev))
-        check(rc, "mls_flash_attention_ctx_fp8_split")
-        return out
-    rc = lib().mls_flash_attention_ctx_fp8(qkv.data_ptr(), *caches, out.data_ptr(), W, out.stride(0), *tail,
-                                           float(scale), stream_ptr(dev))
-    check(rc, "mls_flash_attention_ctx_fp8")
-    return out
+    return _flash_attention_ctx("flash_attention_ctx_fp8", _need_kv_fp8, qkv, (k_cache, v_cache, k_scale, v_scale), past,
+                                lens, batch, seq, n_q_heads, n_kv_heads, head_dim, slot_ids, page_table, scale, out,
+                                splits, max_ctx, workspace)
 
 
 def decode_attention_fp8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: torch.Tensor,

@@ -1,4 +1,4 @@
-"""Context attention on the e4m3 KV cache (ops/csrc/flash_ctx.hip ``flash_ctx_fp8_kernel``,
+"""Context attention on the e4m3 KV cache (ops/csrc/flash_ctx.hip ``flash_ctx_kernel<true, SPLIT>``,
 ``ops.flash_attention_ctx_fp8``): the chunk path of ``kv_prefill="cache"``, unsplit and split-KV, per-slot
 and paged.  Cases as ``test_flash_ctx_split_gpu.py::_case`` builds them (ragged ``past``, shuffled slots,
 a shuffled page pool holding the same rows); the cache rows are ``R.kv_quant_fp8`` of random bf16 rows and

@@ -69,9 +69,14 @@ def _case(Hq, Hkv, S, seed=0):
 
 
 def _valid(out, c):
-    """The valid rows of every batch row, concatenated (the others are unspecified)."""
+    """The valid rows of every batch row, concatenated (the others, ``_padding``, are zeros)."""
     o = out.view(c["B"], c["S"], -1)
     return torch.cat([o[b, : int(c["n"][b])] for b in range(c["B"])])
+
+
+def _padding(out, c):
+    o = out.view(c["B"], c["S"], -1)
+    return torch.cat([o[b, int(c["n"][b]):] for b in range(c["B"])])
 
 
 @pytest.mark.parametrize("S", [1, 16, 63, 64, 65, 130])
@@ -83,11 +88,15 @@ def test_kernel_vs_oracle_per_slot_and_paged(ops, Hq, Hkv, S):
     ref_p = R.attention_ctx(c["qkv"], c["kp"], c["vp"], c["past"], c["lens"], c["B"], S, Hq, Hkv, D,
                             slot_ids=c["slot_ids"], page_table=c["table"], head_major=True)
     assert torch.equal(ref, ref_p)  # the two cache images hold the same rows
-    out = ops.flash_attention_ctx(c["qkv"], c["kc"], c["vc"], c["past"], c["lens"], c["B"], S, Hq, Hkv, D,
-                                  slot_ids=c["slot_ids"])
-    out_p = ops.flash_attention_ctx(c["qkv"], c["kp"], c["vp"], c["past"], c["lens"], c["B"], S, Hq, Hkv, D,
-                                    slot_ids=c["slot_ids"], page_table=c["table"])
+    out = torch.full((c["B"] * S, Hq * D), float("nan"), device=DEV, dtype=torch.bfloat16)  # an unwritten row fails
+    out_p = torch.full_like(out, float("nan"))
+    ops.flash_attention_ctx(c["qkv"], c["kc"], c["vc"], c["past"], c["lens"], c["B"], S, Hq, Hkv, D,
+                            slot_ids=c["slot_ids"], out=out)
+    ops.flash_attention_ctx(c["qkv"], c["kp"], c["vp"], c["past"], c["lens"], c["B"], S, Hq, Hkv, D,
+                            slot_ids=c["slot_ids"], page_table=c["table"], out=out_p)
     torch.cuda.synchronize()
+    # rows at or past a batch row's valid length: zeros (finite padding for the GEMMs that follow)
+    assert not _padding(out, c).any() and not _padding(out_p, c).any()
     got, got_p, want = _valid(out, c), _valid(out_p, c), _valid(ref, c)
     assert torch.isfinite(got.float()).all()  # no poisoned row or column was read
     err = rel(got, want)
