@@ -1491,14 +1491,18 @@ class LlamaTP:
 
     @torch.no_grad()
     def generate(self, ids: torch.Tensor, lens: torch.Tensor, gp: GenParams, prefill_chunk: int = 0,
-                 speculate: int = 0, drafter=None) -> torch.Tensor:
+                 speculate: int = 0, drafter=None, spec_device: bool = False, spec_ngram=(3, 1)) -> torch.Tensor:
         """ids int ``[B, S]`` (right-padded), lens ``[B]`` -> generated ``[B, max_new_tokens]``.
         ``prefill_chunk = N > 0``: the prompts are prefilled N positions at a time
         (:meth:`prefill_chunked`) instead of in one forward.
         ``speculate = K > 0``: speculative decoding (models/speculative.py) -- each sequence proposes up to
         K draft tokens (``drafter(tokens, n_draft)``, default prompt lookup), one :meth:`verify_step`
         scores them and the sequence keeps the drafts that equal what it would have sampled anyway; a
-        host loop, ``self.spec_stats`` counts its steps / drafted / accepted tokens."""
+        host loop, ``self.spec_stats`` counts its steps / drafted / accepted tokens.
+        ``spec_device`` (with ``speculate``): the loop's verify step is one graph replay that also drafts
+        (prompt lookup, n-grams ``spec_ngram = (max, min)``) and accepts on device
+        (:meth:`serve_spec_graph`); the host reads one small block per step.  ``ValueError`` where the
+        device loop is unavailable or with a ``drafter`` hook -- nothing falls back to the host loop."""
         B, S = ids.shape
         prefill_chunk = int(prefill_chunk)
         if prefill_chunk < 0:
@@ -1510,6 +1514,8 @@ class LlamaTP:
             raise ValueError(f"speculate must be >= 0, got {speculate}")
         if speculate:
             self.check_speculate(speculate)
+        if spec_device:
+            self.check_spec_device(speculate, drafter, k=max(1, min(gp.top_k, self.top_k_max)), Bv=B)
         if B > self.max_batch or S + gp.max_new_tokens > self.max_seq:
             raise ValueError("batch / sequence exceed the KV cache")
         lens_host = lens.detach().to("cpu")
@@ -1528,6 +1534,9 @@ class LlamaTP:
                     self.pages.assign(b, S + gp.max_new_tokens)
                     assigned = b + 1
             vals, idx = self._prefill(ids, lens, k, prefill_chunk)
+            if spec_device:
+                return self._generate_speculative_device(ids, lens, lens_host, vals, idx, gp, k, speculate,
+                                                         spec_ngram)
             if speculate:
                 return self._generate_speculative(ids, lens_host, vals, idx, gp, k, speculate, drafter)
             out = []
@@ -1585,6 +1594,62 @@ class LlamaTP:
                 st["accepted"] += len(got) - 1
         return torch.tensor(outs, dtype=torch.int32)
 
+    def _generate_speculative_device(self, ids: torch.Tensor, lens: torch.Tensor, lens_host: torch.Tensor, vals, idx,
+                                     gp: GenParams, k: int, K: int, ngram) -> torch.Tensor:
+        """:meth:`_generate_speculative` with the drafter and the acceptance inside the captured verify
+        step (:meth:`serve_spec_graph`): batch row b is serving slot b, the verify batch is the rows that
+        still owe tokens (as the host loop's), and one read-back of the per-slot ``(n, got, tokens)``
+        blocks per step tells the host who is done and feeds ``spec_stats``."""
+        B, S = ids.shape
+        dev = self.device
+        T = K + 1
+        st = self.serve_state(self.max_batch, spec_T=T)
+        sl = slice(0, B)
+        st["prompt"][sl, :S] = ids.to(torch.int32)
+        st["plen"][sl] = lens
+        st["max_new"][sl] = int(gp.max_new_tokens)
+        st["step"][sl] = 0
+        st["topk"][sl] = int(gp.top_k)
+        st["temp"][sl] = float(gp.temperature)
+        st["seed"][sl] = int(gp.seed)
+        st["pos"][sl] = lens - 1  # the pick advances them to (lens, lens + 1): the first decode position
+        st["lens"][sl] = lens
+        cv, ci = self._gather_dev(vals, idx)
+        self.ops.decode_pick(cv, ci, st["tok"], st["pos"], st["lens"], st["step"], topk=st["topk"], temp=st["temp"],
+                             seed=st["seed"], hist=st["hist"], rows=torch.arange(B, dtype=torch.int32, device=dev))
+        stats = self.spec_stats = {"steps": 0, "drafted": 0, "accepted": 0}
+        cur = [int(x) for x in lens_host.tolist()]  # position of each row's last emitted token
+        have = [1] * B
+        try:
+            while True:
+                rows = [b for b in range(B) if have[b] < gp.max_new_tokens]
+                if not rows:
+                    break
+                max_ctx = max(cur[b] + 1 + max(0, min(K, gp.max_new_tokens - have[b] - 1)) for b in rows)
+                g = self.serve_spec_graph(len(rows), T, k, self.ctx_bucket(max_ctx), ngram=ngram, eos=())
+                st["spec_rows"][: len(rows)].copy_(torch.tensor(rows, dtype=torch.int32), non_blocking=True)
+                if self.pages is not None:
+                    self.pages.device_table()  # the graph reads the table buffer in place
+                with tracing.range("llama.verify"):
+                    g.replay()
+                rb = st["spec_rb"].cpu().tolist()
+                stats["steps"] += 1
+                for b in rows:
+                    n, got = rb[b][0], rb[b][1]
+                    if got < 1:
+                        raise RuntimeError(f"speculative step emitted nothing for row {b} (n = {n})")
+                    have[b] += got
+                    cur[b] += got
+                    stats["drafted"] += n - 1
+                    stats["accepted"] += got - 1
+                if self.health_every > 0 and stats["steps"] % self.health_every == 0:
+                    self.check_comm_health()
+            self.check_comm_health()
+            return st["hist"][sl, : gp.max_new_tokens].cpu()
+        finally:  # the slots are idle again for a serving loop on this model
+            st["pos"][sl] = 0
+            st["lens"][sl] = 1
+
     # ---------------------------------------------------------------- device-resident decode loop
     def _gather_pad(self, k: int) -> int:
         return (-2 * k) % 4  # [B, 2k + pad] fp32 rows: a 16-B multiple per row (one-shot all-gather)
@@ -1603,6 +1668,43 @@ class LlamaTP:
         if car is not None:  # + the serving step's control row (serve_graph)
             return (B + 1) * (2 * k + self._gather_pad(k)) * 4 <= car.cap
         return self._rccl_graphs and not getattr(self.comm, "host_staged", False)
+
+    def _spec_device_ok(self, Bv: int, T: int, k: int) -> bool:
+        """May a verify step of ``Bv`` sequences x ``T`` positions draft, gather and accept inside its
+        captured graph?  What :meth:`_device_loop_ok` asks, for the ``Bv * T + 1``-row gather."""
+        if os.environ.get("MLS_DEVICE_PICK", "1") == "0":
+            return False
+        if not (self.backend == "fused" and self.device.type == "cuda" and self.use_graphs
+                and self._graph_ok(Bv * T)):
+            return False
+        if self.tp * k > 512 or k > 64:
+            return False
+        if self.tp == 1 or getattr(self.comm, "graph_safe", False):
+            return True
+        car = getattr(self.comm, "car", None)
+        if car is not None:
+            return (Bv * T + 1) * (2 * k + self._gather_pad(k)) * 4 <= car.cap
+        return self._rccl_graphs and not getattr(self.comm, "host_staged", False)
+
+    def check_spec_device(self, speculate: int, drafter=None, k: Optional[int] = None, Bv: Optional[int] = None) -> None:
+        """``spec_device`` (the verify step drafts and accepts on device): raises ``ValueError`` without
+        ``speculate``, with a host ``drafter`` hook, for what :meth:`check_speculate` refuses and wherever
+        the device loop is unavailable -- nothing falls back to the host loop."""
+        speculate = int(speculate)
+        if speculate < 1:
+            raise ValueError("spec_device needs speculate >= 1")
+        if drafter is not None:
+            raise ValueError("spec_device drafts by prompt lookup inside the captured step: a drafter callable "
+                             "(a host hook) cannot run there")
+        self.check_speculate(speculate)
+        T = speculate + 1
+        Bv = max(1, 16 // T) if Bv is None else int(Bv)
+        k = self.top_k_max if k is None else int(k)
+        if not self._spec_device_ok(Bv, T, k):
+            raise ValueError("spec_device needs the device-resident loop: the fused backend on a GPU with graphs on, "
+                             f"MLS_DEVICE_PICK != 0, tp * k <= 512 and a {Bv * T + 1}-row candidate gather that "
+                             f"fits the one-shot buffer (backend {self.backend}, device {self.device.type}, "
+                             f"graphs {bool(self.use_graphs)}, tp {self.tp}, k {k})")
 
     def _gather_dev(self, vals: torch.Tensor, idx: torch.Tensor, ctl: Optional[torch.Tensor] = None):
         """X4 on device: every rank's [B, k] candidates -> ([tp, B, k] f32, [tp, B, k] i32), one
@@ -1672,7 +1774,7 @@ class LlamaTP:
         return g
 
     # ---------------------------------------------------------------- serving (ContinuousLlama) on device
-    def serve_state(self, B: int) -> Dict[str, torch.Tensor]:
+    def serve_state(self, B: int, spec_T: int = 0) -> Dict[str, torch.Tensor]:
         """Per-slot device state of the continuous-batching decode loop (models/llama_serving.py):
         ``E`` int32 [2, B] is the one per-iteration read-back -- row 0 the prefill picks of the
         iteration's new sequences, row 1 (= ``tok``, the decode graph's input and output token) the
@@ -1680,26 +1782,46 @@ class LlamaTP:
         their own cache row / the scratch page and keep pos 0).  ``E_all`` = ``E`` followed by
         ``ctl_out`` (int32 [CTL_WORDS]): rank 0's ``ctl_in`` as the decode step's gather carried it
         (the next iteration's header at TP > 1), and ``err_out`` (int32 [1]): this rank's one-shot
-        collectives' sticky peer-timeout word after the step -- all read back in the same copy."""
+        collectives' sticky peer-timeout word after the step -- all read back in the same copy.
+        ``spec_T = K + 1`` (speculation on device, :meth:`serve_spec_graph`): the state also holds each slot's
+        tokens for the drafter -- ``prompt`` int32 [B, max_seq] / ``plen``, ``hist`` int32 [B, max_seq] (the
+        emitted tokens, ``step`` of them) and ``max_new`` -- the verify rows' slots ``spec_rows``, and the
+        read-back block ``spec_rb`` int32 [B, spec_T + 2] = (n fed, got, the got tokens) per slot, appended to
+        ``E_all`` behind ``err_out``: still one copy per iteration.  A state built without (or for a smaller
+        ``spec_T``) is rebuilt, with the graphs that baked its addresses; ``spec_T = 0`` returns what exists."""
         st = self._serve.get(B)
+        if st is not None and int(spec_T) > st.get("spec_T", 0):
+            for key in [q for q in self._dev_graphs if isinstance(q[0], str) and q[0].startswith("serve")]:
+                del self._dev_graphs[key]
+            st = None
         if st is None:
             dev = self.device
+            T = int(spec_T)
             z = lambda dt: torch.zeros(B, device=dev, dtype=dt)  # noqa: E731
-            E_all = torch.zeros(2 * B + CTL_WORDS + 1, device=dev, dtype=torch.int32)
+            base = 2 * B + CTL_WORDS + 1
+            E_all = torch.zeros(base + (B * (T + 2) if T else 0), device=dev, dtype=torch.int32)
             E = E_all[: 2 * B].view(2, B)
-            st = {"E": E, "E_all": E_all, "ctl_out": E_all[2 * B: 2 * B + CTL_WORDS], "err_out": E_all[2 * B + CTL_WORDS:],
+            st = {"E": E, "E_all": E_all, "ctl_out": E_all[2 * B: 2 * B + CTL_WORDS],
+                  "err_out": E_all[2 * B + CTL_WORDS: base],
                   "ctl_in": torch.zeros(CTL_WORDS, device=dev, dtype=torch.int32),
                   "tok": E[1], "pos": z(torch.int32), "lens": torch.ones(B, device=dev, dtype=torch.int32),
                   "step": z(torch.int32), "topk": torch.ones(B, device=dev, dtype=torch.int32),
                   "temp": torch.ones(B, device=dev, dtype=torch.float32), "seed": z(torch.int64),
                   "active": z(torch.int32)}
+            if T:
+                st.update(spec_T=T, spec_rb=E_all[base:].view(B, T + 2), plen=z(torch.int32), max_new=z(torch.int32),
+                          prompt=torch.zeros(B, self.max_seq, device=dev, dtype=torch.int32),
+                          hist=torch.zeros(B, self.max_seq, device=dev, dtype=torch.int32),
+                          spec_rows=torch.zeros(max(B, 16), device=dev, dtype=torch.int32))
             self._serve[B] = st
         return st
 
-    def serve_graph(self, B: int, k: int, ctx: int) -> torch.cuda.CUDAGraph:
+    def serve_graph(self, B: int, k: int, ctx: int, hist: bool = False) -> torch.cuda.CUDAGraph:
         """Captured serving decode step over all B slots: forward + X4 gather + the on-device pick
-        of the ACTIVE slots (``ops.decode_pick(active=...)``), advancing their state in place."""
-        key = ("serve", B, k, ctx)
+        of the ACTIVE slots (``ops.decode_pick(active=...)``), advancing their state in place.
+        ``hist`` (speculation on device): the pick also appends each token to the slot's ``hist`` row, so
+        a later verify step drafts from the complete history; captured and keyed separately."""
+        key = ("serve_hist" if hist else "serve", B, k, ctx)
         g = self._dev_graphs.get(key)
         if g is not None:
             return g
@@ -1713,10 +1835,67 @@ class LlamaTP:
             if car is not None:  # did a peer wait of this step (or an earlier one) time out?
                 car.error_peek(st["err_out"])
             self.ops.decode_pick(cv, ci, st["tok"], st["pos"], st["lens"], st["step"], topk=st["topk"],
-                                 temp=st["temp"], seed=st["seed"], active=st["active"])
+                                 temp=st["temp"], seed=st["seed"], active=st["active"],
+                                 hist=st["hist"] if hist else None)
 
         g, _ = self._capture(ctx, self._warm_decode(B, k, ctx), body)
         self._dev_graphs[key] = g
+        return g
+
+    def serve_spec_graph(self, Bv: int, T: int, k: int, ctx: int, ngram=(3, 1), eos=None) -> torch.cuda.CUDAGraph:
+        """Captured speculative step of the ``Bv`` slots listed in ``spec_rows[:Bv]`` of the serving state
+        (:meth:`serve_state` with ``spec_T = T``): ``ops.spec_draft`` writes the verify forward's inputs
+        from each slot's own tokens, the ``all_rows`` forward scores the ``Bv * T`` rows, the X4 gather
+        carries the control row as :meth:`serve_graph`'s does, and ``ops.spec_accept`` picks each fed row,
+        keeps the drafts that equal the picks and advances the slots in place -- one replay, then one
+        ``E_all`` copy.  ``ngram = (max, min)`` of the prompt lookup; ``eos``: ids that end a sequence
+        (default the model's).  Warm-up runs the forward on scratch inputs with ``lens == past`` (every
+        row is padding: no cache row is written, no slot state touched)."""
+        eos = tuple(sorted(self.cfg.eos_ids if eos is None else eos))
+        key = ("serve_spec", Bv, T, k, ctx, self.verify_attn, tuple(ngram), eos)
+        hit = self._dev_graphs.get(key)
+        if hit is not None:
+            return hit[0]
+        B = self.max_batch
+        st = self.serve_state(B, spec_T=T)
+        if st["spec_T"] != T:
+            raise ValueError(f"the serving state was built for {st['spec_T']} verify positions, not {T}")
+        dev = self.device
+        zi = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)  # noqa: E731
+        ids, n, past, lens = zi(Bv, T), zi(Bv), zi(Bv), zi(Bv)
+        rows = st["spec_rows"][:Bv]
+        off = torch.arange(T, dtype=torch.int32, device=dev).unsqueeze(0)
+        eos_t = torch.tensor(eos, dtype=torch.int32, device=dev) if eos else None
+        w_ids, w_zero, w_rows = zi(Bv, T), zi(Bv), torch.arange(Bv, dtype=torch.int32, device=dev) % B
+        if self.pages is not None:
+            self.pages.device_table()
+
+        def warm():
+            v, i = self.step(w_ids, w_zero.unsqueeze(1) + off, w_zero, decode=False, k=k, slot_ids=w_rows, past=w_zero,
+                             all_rows=True)
+            self._gather_dev(v, i)
+
+        def body():
+            self.ops.spec_draft(rows, st["prompt"], st["plen"], st["hist"], st["step"], st["max_new"], st["pos"], ids,
+                                n, past, lens, K=T - 1, max_ngram=int(ngram[0]), min_ngram=int(ngram[1]))
+            v, i = self.step(ids, past.unsqueeze(1) + off, lens, decode=False, k=k, slot_ids=rows, past=past,
+                             all_rows=True)
+            cv, ci, c0 = self._gather_dev(v, i, ctl=st["ctl_in"])
+            st["ctl_out"].copy_(c0)
+            car = getattr(self.comm, "car", None)
+            if car is not None:  # did a peer wait of this step (or an earlier one) time out?
+                car.error_peek(st["err_out"])
+            self.ops.spec_accept(cv, ci, ids, n, rows, st["tok"], st["pos"], st["lens"], st["step"], st["hist"],
+                                 st["spec_rb"], topk=st["topk"], temp=st["temp"], seed=st["seed"], eos=eos_t)
+
+        # this graph's own split-KV workspace: the first warm-up step sizes it, the capture bakes its address
+        self._ver_ws_graph = torch.empty(0, device=dev, dtype=torch.float32)
+        try:
+            g, _ = self._capture(ctx, warm, body)
+        finally:
+            ws, self._ver_ws_graph = self._ver_ws_graph, None
+        # the buffers stay referenced: the captured launches read / write them at every replay
+        self._dev_graphs[key] = (g, ids, n, past, lens, off, eos_t, ws)
         return g
 
     def check_comm_health(self) -> None:

@@ -29,9 +29,19 @@ decoding sequences <= 16 // (K + 1)`` step 2 is one ``LlamaTP.verify_step`` over
 only -- each proposes up to K draft tokens (prompt lookup unless a ``drafter`` is given) and keeps the
 longest prefix that equals what it would have sampled anyway, so a step yields 1 to K + 1 tokens per
 sequence and the tokens are those of ``speculate=0``.  With more sequences in flight it is the normal
-decode step.  The choice is a function of the slots alone.  Iterations run on the host path (the
-device-resident iteration picks one token per slot), and TP > 1 is refused: the carried-header
-protocol is tied to the device iterations (follow-up).
+decode step.  The choice is a function of the slots alone.  By default the iterations run on the host path
+(drafts and acceptance in Python), and TP > 1 is refused: the carried-header protocol is tied to the
+device iterations.
+
+Speculation on device (``ContinuousLlama(speculate=K, spec_device=True)``, opt-in): the device-resident
+iterations are taken, and where they would replay the decode graph they replay ``LlamaTP.serve_spec_graph``
+when the step is a verify step -- the drafter (prompt lookup over the slot's own tokens, ``ops.spec_draft``),
+the verify forward, the X4 gather with the control row, and the acceptance (``ops.spec_accept``) are one
+captured graph, and each slot's ``(n fed, got, tokens)`` block rides the iteration's one read-back.  The
+slots' tokens live on the device (``serve_state`` ``prompt`` / ``hist``): admission writes the prompt, every
+pick -- prefill, plain decode step, verify step -- appends to ``hist``.  Every TP rank runs the same draft and
+accept kernels on identical state, so there is no new message and TP > 1 is served.  A ``drafter`` hook
+cannot run inside the graph and is refused, as is everything for which the device loop is unavailable.
 
 Prefix caching (``ContinuousLlama(prefix_cache=True)``, opt-in, paged KV only, models/prefix_cache.py):
 full pages of a prompt stay indexed once its prefill (or last chunk) has been issued, and step 1 of a
@@ -125,14 +135,17 @@ class ContinuousLlama:
     def __init__(self, model: LlamaTP, max_queue: int = 4096,
                  broadcast: Optional[Callable[[Optional[List[_Seq]]], Optional[List[_Seq]]]] = None,
                  channel=None, prefill_chunk: int = 0, speculate: int = 0, drafter=None,
-                 prefix_cache: bool = False):
+                 prefix_cache: bool = False, spec_device: bool = False, spec_ngram=(3, 1)):
         """``prefill_chunk = N > 0`` (chunked prefill): an admitted prompt advances by at most N
         positions per iteration, batched over all prefilling slots, and the decoding slots get their
         step in the same iteration -- a long prompt no longer holds every decoding sequence for its
         whole prefill.  0: each iteration prefills its admissions in one forward.
         ``prefix_cache`` (paged KV only): full pages of prompt tokens stay indexed after their prefill
         (models/prefix_cache.py); a later prompt that begins with the same tokens adopts those pages
-        and prefills only the rest, ``step(past=hit rows)``."""
+        and prefills only the rest, ``step(past=hit rows)``.
+        ``spec_device`` (with ``speculate``): verify steps draft and accept on device inside the
+        device-resident iterations (module docstring), ``spec_ngram = (max, min)`` the prompt lookup's
+        n-gram range; ``ValueError`` where that is unavailable -- nothing falls back to the host loop."""
         self.prefill_chunk = int(prefill_chunk)
         if self.prefill_chunk < 0:
             raise ValueError(f"prefill_chunk must be >= 0, got {prefill_chunk}")
@@ -141,7 +154,16 @@ class ContinuousLlama:
         self.speculate = int(speculate)
         if self.speculate < 0:
             raise ValueError(f"speculate must be >= 0, got {speculate}")
-        if self.speculate:
+        self.spec_device = bool(spec_device)
+        self.spec_ngram = (int(spec_ngram[0]), int(spec_ngram[1]))
+        if self.spec_device:
+            if os.environ.get("MLS_SERVE_DEVICE_PICK", "1") == "0":
+                raise ValueError("spec_device needs the device-resident iterations (MLS_SERVE_DEVICE_PICK=0 is set)")
+            model.check_spec_device(self.speculate, drafter)  # ValueError: speculate 0, a drafter hook, no device loop
+            if not model._device_loop_ok(model.max_batch, model.top_k_max):
+                raise ValueError("spec_device needs the device-resident iterations, which are unavailable for "
+                                 f"{model.max_batch} slots x top_k {model.top_k_max} on this model")
+        elif self.speculate:
             if model.tp > 1:
                 raise ValueError("speculate is not available with tp > 1 in the continuous engine: its iterations "
                                  "run on the host path, the TP header protocol rides the device iterations")
@@ -444,7 +466,9 @@ class ContinuousLlama:
 
     # ---------------------------------------------------------------- one iteration (all ranks)
     def _dev_ok(self) -> bool:
-        if not self._want_dev or self.speculate:  # a verify step emits a variable number of tokens: host path
+        if not self._want_dev:
+            return False
+        if self.speculate and not self.spec_device:  # drafts and acceptance in Python: host path
             return False
         if any(s is not None for s in self.slots):  # sequences in flight keep their mode
             return self.dev_mode
@@ -455,6 +479,8 @@ class ContinuousLlama:
         """Admit, decode one step, retire.  Returns the retired sequences (slots already freed);
         :meth:`run_iteration` resolves their futures once the comm-health check has passed."""
         self.dev_mode = self._dev_ok()
+        if self.spec_device and not self.dev_mode:  # e.g. the IPC path was dropped: nothing falls back
+            raise RuntimeError("spec_device: the device-resident iterations are no longer available")
         if self.prefill_chunk:
             return self._iteration_dev_chunked(admit) if self.dev_mode else self._iteration_host_chunked(admit)
         if self.dev_mode:
@@ -537,9 +563,10 @@ class ContinuousLlama:
     def _iteration_dev_chunked(self, admit: List[_Seq]) -> List[_Seq]:
         m = self.m
         dev = m.device
-        st = m.serve_state(self.B)
+        st = m.serve_state(self.B, spec_T=self.speculate + 1) if self.spec_device else m.serve_state(self.B)
         ops = m.ops
         self._admit(admit)
+        self._spec_admit(st, admit)
         pre, w = self._chunk_plan()
         fin: List[_Seq] = []
         if pre:
@@ -576,51 +603,19 @@ class ContinuousLlama:
                 fj = torch.tensor(fin_j, dtype=torch.int64).to(dev, non_blocking=True)
                 ops.decode_pick(cv[:, fj].contiguous(), ci[:, fj].contiguous(), st["tok"], st["pos"], st["lens"],
                                 st["step"], topk=st["topk"], temp=st["temp"], seed=st["seed"],
-                                rows=slot_ids[fj].contiguous(), emit=st["E"][0])
+                                rows=slot_ids[fj].contiguous(), emit=st["E"][0],
+                                hist=st["hist"] if self.spec_device else None)
             for s in pre:
                 s.done = min(len(s.ids), s.done + w)
             for s in fin:
                 s.cur = len(s.ids)
         active = [s for s in self.slots if s is not None and s.done >= len(s.ids)]
-        carry = self._carry and m.tp > 1
+        spec = False
         if active:
-            k = max(1, min(max(s.gp.top_k for s in active), m.top_k_max))
             # the bound covers the prefilling slots' dummy rows (lens = rows done + 1) too
             max_ctx = max(s.cur if s.done >= len(s.ids) else s.done for s in self.slots if s is not None) + 1
-            g = m.serve_graph(self.B, k, m.ctx_bucket(max_ctx))
-            if m.pages is not None:
-                m.pages.device_table()  # the graph reads the table buffer in place
-            if carry and self.leader:
-                self._plan_next(st)  # the next iteration's header rides this step's gather
-            g.replay()
-        done: List[_Seq] = []
-        if fin or active:
-            E_all = st["E_all"].cpu()  # the iteration's one device -> host copy
-            self.host_reads += 1
-            E = E_all[: 2 * self.B].view(2, self.B)
-            e0, e1 = E[0].tolist(), E[1].tolist()
-            if active and carry:
-                c = E_all[2 * self.B:].tolist()
-                ok = c[3] == ctl_check(self.iterations, c[0], c[1], c[2]) and c[0] in (OP_STOP, OP_ITER)
-                self._carry_check = (not ok) or c[4] != 0 or c[1] > 0  # as _iteration_dev
-                self._ctl_bad = None if ok else c[:4]
-                self._next_hdr = (c[0], c[1], c[2]) if ok else None
-            new = {id(s) for s in fin}
-            for s in fin:
-                s.out.append(int(e0[s.slot]))
-                self.tokens += 1
-            for s in active:
-                if id(s) in new and (len(s.out) >= s.gp.max_new_tokens or s.out[-1] in self.eos):
-                    continue  # finished on its prefill token: the decode pick is discarded
-                s.out.append(int(e1[s.slot]))
-                s.cur += 1
-                self.tokens += 1
-            done = self._retire()
-            if done:
-                idx_t = torch.tensor([q.slot for q in done], dtype=torch.int64).to(dev, non_blocking=True)
-                st["active"][idx_t] = 0
-                st["pos"][idx_t] = 0
-                st["lens"][idx_t] = 1
+            spec = self._dev_decode(st, active, fin, max_ctx)
+        done = self._dev_finish(st, fin, active, spec) if fin or active else []
         self.iterations += 1
         return done
 
@@ -628,10 +623,11 @@ class ContinuousLlama:
     def _iteration_dev(self, admit: List[_Seq]) -> List[_Seq]:
         m = self.m
         dev = m.device
-        st = m.serve_state(self.B)
+        st = m.serve_state(self.B, spec_T=self.speculate + 1) if self.spec_device else m.serve_state(self.B)
         ops = m.ops
         if admit:
             self._admit(admit)
+            self._spec_admit(st, admit)
             S = max(len(s.ids) - s.hit for s in admit)  # the longest suffix (hit = 0 without prefix caching)
             ids = torch.zeros(len(admit), S, dtype=torch.int32)
             for j, s in enumerate(admit):
@@ -663,54 +659,111 @@ class ContinuousLlama:
             st["temp"][sl] = temps
             st["active"][sl] = 1
             ops.decode_pick(cv, ci, st["tok"], st["pos"], st["lens"], st["step"], topk=st["topk"], temp=st["temp"],
-                            seed=st["seed"], rows=slot_ids, emit=st["E"][0])
+                            seed=st["seed"], rows=slot_ids, emit=st["E"][0],
+                            hist=st["hist"] if self.spec_device else None)
             for s in admit:
                 s.cur = len(s.ids)
         active = [s for s in self.slots if s is not None]
-        carry = self._carry and m.tp > 1
+        spec = False
         if active:
-            k = max(1, min(max(s.gp.top_k for s in active), m.top_k_max))
-            max_ctx = max(s.cur for s in active) + 1
-            g = m.serve_graph(self.B, k, m.ctx_bucket(max_ctx))
-            if m.pages is not None:
-                m.pages.device_table()  # the graph reads the table buffer in place
-            if carry and self.leader:
-                self._plan_next(st)  # the next iteration's header rides this step's gather
-            g.replay()
-        if admit or active:
-            E_all = st["E_all"].cpu()  # the iteration's one device -> host copy
-            self.host_reads += 1
-            E = E_all[: 2 * self.B].view(2, self.B)
-            e0, e1 = E[0].tolist(), E[1].tolist()
-            if active and carry:
-                c = E_all[2 * self.B:].tolist()
-                ok = c[3] == ctl_check(self.iterations, c[0], c[1], c[2]) and c[0] in (OP_STOP, OP_ITER)
-                # a carried header is trusted only with no peer timeout on this rank; any doubt, and
-                # any header that announces admissions (the process group is about to be used), goes
-                # through the comm-health all-reduce first -- a rank in doubt stops taking part in
-                # the one-shot collectives, so its peers time out too and join that all-reduce
-                self._carry_check = (not ok) or c[4] != 0 or c[1] > 0
-                self._ctl_bad = None if ok else c[:4]
-                self._next_hdr = (c[0], c[1], c[2]) if ok else None
-            new = {id(s) for s in admit}
-            for s in admit:
-                s.out.append(int(e0[s.slot]))
-                self.tokens += 1
-            for s in active:
-                if id(s) in new and (len(s.out) >= s.gp.max_new_tokens or s.out[-1] in self.eos):
-                    continue  # finished on its prefill token: the decode pick is discarded
+            spec = self._dev_decode(st, active, admit, max(s.cur for s in active) + 1)
+        done = self._dev_finish(st, admit, active, spec) if admit or active else []
+        self.iterations += 1
+        return done
+
+    def _spec_admit(self, st, admit: List[_Seq]) -> None:
+        """spec_device: what the on-device drafter needs of the admissions -- each prompt into
+        ``prompt[slot]``, its length and the sequence's token budget -- in one H2D."""
+        if not (self.spec_device and admit):
+            return
+        S = max(len(s.ids) for s in admit)
+        buf = torch.zeros(len(admit), 3 + S, dtype=torch.int32)
+        for j, s in enumerate(admit):
+            buf[j, :3] = torch.tensor([s.slot, len(s.ids), s.gp.max_new_tokens], dtype=torch.int32)
+            buf[j, 3: 3 + len(s.ids)] = torch.tensor(s.ids, dtype=torch.int32)
+        d = buf.to(self.m.device, non_blocking=True)
+        sl = d[:, 0].to(torch.int64)
+        st["prompt"][sl, :S] = d[:, 3:]
+        st["plen"][sl] = d[:, 1]
+        st["max_new"][sl] = d[:, 2]
+
+    def _dev_decode(self, st, active: List[_Seq], new: List[_Seq], max_ctx: int) -> bool:
+        """The device iterations' decode step over the decoding sequences ``active`` (``new``: those whose
+        prefill pick this iteration issued, not yet read back): one graph replay -- the verify step with
+        its drafter and acceptance (``serve_spec_graph``) when ``spec_device`` is on and
+        :meth:`_spec_ok` holds, else the decode step of all slots under the bound ``max_ctx``.  At
+        TP > 1 rank 0 first writes the next iteration's header, which rides either graph's gather.
+        Returns whether the step was a verify step."""
+        m = self.m
+        k = max(1, min(max(s.gp.top_k for s in active), m.top_k_max))
+        spec = self.spec_device and self._spec_ok(active)
+        if spec:
+            K = self.speculate
+            fresh = {id(s) for s in new}
+            # the host loop's bound max(past + n): n = 1 + min(K, remaining - 1) is known without the drafts
+            max_ctx = max(s.cur + 1 + max(0, min(K, s.gp.max_new_tokens - len(s.out) - (id(s) in fresh) - 1))
+                          for s in active)
+            g = m.serve_spec_graph(len(active), K + 1, k, m.ctx_bucket(max_ctx), ngram=self.spec_ngram, eos=self.eos)
+            st["spec_rows"][: len(active)].copy_(torch.tensor([s.slot for s in active], dtype=torch.int32),
+                                                 non_blocking=True)  # the decoding slots: one small H2D
+        else:  # spec_device: the pick appends to hist, so a later verify step drafts from the whole history
+            g = (m.serve_graph(self.B, k, m.ctx_bucket(max_ctx), hist=True) if self.spec_device
+                 else m.serve_graph(self.B, k, m.ctx_bucket(max_ctx)))
+        if m.pages is not None:
+            m.pages.device_table()  # the graph reads the table buffer in place
+        if self._carry and m.tp > 1 and self.leader:
+            self._plan_next(st)  # the next iteration's header rides this step's gather
+        g.replay()
+        return spec
+
+    def _dev_finish(self, st, new: List[_Seq], active: List[_Seq], spec: bool) -> List[_Seq]:
+        """The device iterations' one device -> host copy and what follows from it: the carried header,
+        the prefill tokens of ``new``, each decoding sequence's token (or, after a verify step, its
+        ``got`` tokens and the speculation counters), retirement and the retired slots' reset."""
+        m, B = self.m, self.B
+        E_all = st["E_all"].cpu()  # the iteration's one device -> host copy
+        self.host_reads += 1
+        e0, e1 = E_all[:B].tolist(), E_all[B: 2 * B].tolist()
+        if active and self._carry and m.tp > 1:
+            c = E_all[2 * B: 2 * B + CTL_WORDS + 1].tolist()
+            ok = c[3] == ctl_check(self.iterations, c[0], c[1], c[2]) and c[0] in (OP_STOP, OP_ITER)
+            # a carried header is trusted only with no peer timeout on this rank; any doubt, and
+            # any header that announces admissions (the process group is about to be used), goes
+            # through the comm-health all-reduce first -- a rank in doubt stops taking part in
+            # the one-shot collectives, so its peers time out too and join that all-reduce
+            self._carry_check = (not ok) or c[4] != 0 or c[1] > 0
+            self._ctl_bad = None if ok else c[:4]
+            self._next_hdr = (c[0], c[1], c[2]) if ok else None
+        fresh = {id(s) for s in new}
+        for s in new:
+            s.out.append(int(e0[s.slot]))
+            self.tokens += 1
+        rb = E_all[2 * B + CTL_WORDS + 1:].view(B, -1).tolist() if spec else None
+        stepped = False
+        for s in active:
+            if id(s) in fresh and (len(s.out) >= s.gp.max_new_tokens or s.out[-1] in self.eos):
+                continue  # finished on its prefill token: the decode pick / verify output is discarded
+            if rb is None:
                 s.out.append(int(e1[s.slot]))
                 s.cur += 1
                 self.tokens += 1
-            done = self._retire()
-            if done:
-                idx_t = torch.tensor([q.slot for q in done], dtype=torch.int64).to(dev, non_blocking=True)
-                st["active"][idx_t] = 0
-                st["pos"][idx_t] = 0
-                st["lens"][idx_t] = 1
-        else:
-            done = []
-        self.iterations += 1
+                continue
+            n, got = rb[s.slot][0], rb[s.slot][1]
+            if not 1 <= got <= n:
+                raise RuntimeError(f"verify step of slot {s.slot}: fed {n}, emitted {got}")
+            s.out += [int(t) for t in rb[s.slot][2: 2 + got]]
+            s.cur += got
+            self.tokens += got
+            self.spec["spec_drafted"] += n - 1
+            self.spec["spec_accepted"] += got - 1
+            stepped = True
+        self.spec["spec_steps"] += stepped
+        done = self._retire()
+        if done:
+            idx_t = torch.tensor([q.slot for q in done], dtype=torch.int64).to(m.device, non_blocking=True)
+            st["active"][idx_t] = 0
+            st["pos"][idx_t] = 0
+            st["lens"][idx_t] = 1
         return done
 
     @torch.no_grad()

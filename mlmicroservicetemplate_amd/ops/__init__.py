@@ -129,6 +129,8 @@ from .transformer import (  # noqa: F401
     rope_kv_fp8_,
     skinny_packed_combine,
     skinny_packed_combine_ar,
+    spec_accept,
+    spec_draft,
 )
 from .image import (  # noqa: F401
     IMAGE_CONTAINER_BYTES,

@@ -91,6 +91,8 @@ _SIGS = {
     "mls_flash_set_version": [I],
     "mls_image_decode": [P, P, P, L, I, P, P],
     "mls_decode_pick": [P, P, I, I, I, P, P, P, P, P, P, P, I, P, P, P, P, P],
+    "mls_spec_draft": [P, I, I, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P, P],
+    "mls_spec_accept": [P, P, I, I, I, I, P, P, P, I, P, P, P, P, P, P, P, P, I, P, I, P, P],
     "mls_ar_destroy": [P],
     "mls_rope_kv": [P, P, P, P, L, I, I, I, I, P, P, P, P, I, I, L, I, I, P],
     "mls_kv_append": [P, I, I, I, P, P, P, L, I, I, I, P],
@@ -152,7 +154,8 @@ def _bind(lib: ctypes.CDLL) -> None:
 
 
 DEBUG = os.environ.get("MLS_DEBUG", "0") == "1"
-DEBUG_TUS = ("attention", "norm_ops", "stem_pool", "conv3x3_halo", "kv_fp8", "flash_ctx", "decode_verify")  # translation units with MLS_CHECK bounds
+DEBUG_TUS = ("attention", "norm_ops", "stem_pool", "conv3x3_halo", "kv_fp8", "flash_ctx", "decode_verify",
+             "decode_pick", "spec_step")  # translation units with MLS_CHECK bounds
 DEBUG_CODES = {
     101: "rope/KV append: cache slot beyond the cache",
     102: "rope/KV append: position beyond the RoPE table",
@@ -167,6 +170,13 @@ DEBUG_CODES = {
     321: "decode attention (multi): not 0 <= past[b] <= lens[b] <= the rows of a slot / the split grid (max_len)",
     322: "decode attention (multi): slot outside the cache",
     323: "decode attention (multi): page id outside the pool",
+    401: "decode pick: winning candidate index outside [0, tp * k) (a row of NaN candidates)",
+    411: "spec draft: rows[r] is not a serving slot",
+    412: "spec draft / accept: token count or history column outside the prompt / history arrays",
+    413: "spec draft: the fed positions pos[s] .. pos[s] + n leave the slot's rows",
+    414: "spec accept: rows[r] is not a serving slot",
+    415: "spec accept: n[r] outside [0, T]",
+    416: "spec accept: winning candidate index outside [0, tp * k) (a fed row of NaN candidates)",
 }
 
 

@@ -745,3 +745,92 @@ def decode_pick(cand_v: torch.Tensor, cand_i: torch.Tensor, tok: torch.Tensor, p
                                tok.data_ptr(), pos.data_ptr(), lens.data_ptr(), _ptr(hist), cols, step.data_ptr(),
                                _ptr(rows), _ptr(active), _ptr(emit), stream_ptr(dev))
     check(rc, "mls_decode_pick")
+
+
+def _need_rows(t: torch.Tensor, name: str, dt, dev, n: int) -> None:
+    _need(t, name, dt, dev)
+    if t.numel() != n:
+        raise ValueError(f"{name} must have {n} elements")
+
+
+def spec_draft(rows: torch.Tensor, prompt: torch.Tensor, plen: torch.Tensor, hist: torch.Tensor, step: torch.Tensor,
+               max_new: torch.Tensor, pos: torch.Tensor, ids: torch.Tensor, n: torch.Tensor, past: torch.Tensor,
+               lens: torch.Tensor, *, K: int, max_ngram: int = 3, min_ngram: int = 1) -> None:
+    """Speculative decoding's drafter on device (csrc/spec_step.hip): for verify row r of slot ``rows[r]``
+    the feed ``ids[r, :n[r]]`` (the slot's last token and up to K prompt-lookup drafts, zero-padded to
+    ``T = ids.shape[1]``), ``past[r] = pos[slot]`` and ``lens[r] = past[r] + n[r]`` -- the static inputs of
+    the verify forward.  The slot's tokens are ``prompt[slot, :plen]`` then ``hist[slot, :step]``; the rule
+    is ``speculative.spec_feed(tokens, K, max_new - step, prompt_lookup_draft(max_ngram, min_ngram))``, and a
+    slot that may emit nothing more (``max_new - step <= 0``) feeds ``n = 0``.  Capturable."""
+    dev = rows.device
+    _need(rows, "rows", torch.int32, dev)
+    Bv = rows.numel()
+    _need(prompt, "prompt", torch.int32, dev)
+    _need(hist, "hist", torch.int32, dev)
+    if prompt.dim() != 2 or tuple(prompt.shape) != tuple(hist.shape):
+        raise ValueError("prompt and hist must both be [slots, cols]")
+    S, cols = prompt.shape
+    for name, t in (("plen", plen), ("step", step), ("max_new", max_new), ("pos", pos)):
+        _need_rows(t, name, torch.int32, dev, S)
+    _need(ids, "ids", torch.int32, dev)
+    if ids.dim() != 2 or ids.shape[0] != Bv:
+        raise ValueError(f"ids must be [{Bv}, T]")
+    T = ids.shape[1]
+    K = int(K)
+    if K < 0 or T < K + 1 or Bv < 1 or int(max_ngram) < 1:
+        raise ValueError(f"spec_draft: need rows, 0 <= K < T = {T} and max_ngram >= 1 (got K {K}, max_ngram {max_ngram})")
+    for name, t in (("n", n), ("past", past), ("lens", lens)):
+        _need_rows(t, name, torch.int32, dev, Bv)
+    rc = lib().mls_spec_draft(rows.data_ptr(), Bv, S, prompt.data_ptr(), plen.data_ptr(), hist.data_ptr(),
+                              step.data_ptr(), max_new.data_ptr(), pos.data_ptr(), cols, K, T, int(max_ngram),
+                              int(min_ngram), ids.data_ptr(), n.data_ptr(), past.data_ptr(), lens.data_ptr(),
+                              stream_ptr(dev))
+    check(rc, "mls_spec_draft")
+
+
+def spec_accept(cand_v: torch.Tensor, cand_i: torch.Tensor, ids: torch.Tensor, n: torch.Tensor, rows: torch.Tensor,
+                tok: torch.Tensor, pos: torch.Tensor, lens: torch.Tensor, step: torch.Tensor, hist: torch.Tensor,
+                readback: torch.Tensor, *, topk: Optional[torch.Tensor] = None, temp: Optional[torch.Tensor] = None,
+                seed: Optional[torch.Tensor] = None, eos: Optional[torch.Tensor] = None) -> None:
+    """Speculative decoding's acceptance on device (csrc/spec_step.hip): ``cand_v`` / ``cand_i`` are the
+    all-gathered ``[tp, Bv * T, k]`` candidates of a verify step whose row r (slot ``rows[r]``) fed
+    ``ids[r, :n[r]]``.  Row r emits ``y[0]``, then ``y[t]`` while ``ids[r, t] == y[t - 1]`` and ``t < n[r]``,
+    stopping after the first token in ``eos`` (``speculative.accept``), with ``y[t]`` the pick of candidate
+    row ``r * T + t`` at generated-token index ``step[slot] + t`` by :func:`decode_pick`'s rule.  The ``got``
+    tokens go to ``hist[slot, step : step + got]``; ``step`` / ``pos`` advance by ``got``, ``tok`` is the last
+    one, ``lens = pos + 1``; ``readback[slot] = (n fed, got, the got tokens)`` (int32 ``[slots, T + 2]``).
+    Slots not in ``rows`` are untouched; rows ``t >= n[r]`` are never read.  Capturable."""
+    dev = cand_v.device
+    _need(cand_v, "cand_v", torch.float32, dev)
+    _need(cand_i, "cand_i", torch.int32, dev)
+    _need(ids, "ids", torch.int32, dev)
+    _need(rows, "rows", torch.int32, dev)
+    Bv = rows.numel()
+    if ids.dim() != 2 or ids.shape[0] != Bv or Bv < 1:
+        raise ValueError(f"ids must be [{Bv}, T]")
+    T = ids.shape[1]
+    if cand_v.dim() != 3 or cand_v.shape[1] != Bv * T or tuple(cand_i.shape) != tuple(cand_v.shape):
+        raise ValueError(f"cand_v / cand_i must be [tp, {Bv * T}, k]")
+    tp, _, k = cand_v.shape
+    if tp * k > 512:
+        raise ValueError("spec_accept: tp * k must be <= 512")
+    _need_rows(n, "n", torch.int32, dev, Bv)
+    S = tok.numel()
+    for name, t in (("tok", tok), ("pos", pos), ("lens", lens), ("step", step)):
+        _need_rows(t, name, torch.int32, dev, S)
+    for name, t, dt in (("topk", topk, torch.int32), ("temp", temp, torch.float32), ("seed", seed, torch.int64)):
+        if t is not None:
+            _need_rows(t, name, dt, dev, S)
+    _need(hist, "hist", torch.int32, dev)
+    if hist.dim() != 2 or hist.shape[0] != S:
+        raise ValueError("hist must be [state rows, cols]")
+    _need_rows(readback, "readback", torch.int32, dev, S * (T + 2))
+    n_eos = 0
+    if eos is not None and eos.numel():
+        _need(eos, "eos", torch.int32, dev)
+        n_eos = eos.numel()
+    rc = lib().mls_spec_accept(cand_v.data_ptr(), cand_i.data_ptr(), tp, Bv, T, k, ids.data_ptr(), n.data_ptr(),
+                               rows.data_ptr(), S, _ptr(topk), _ptr(temp), _ptr(seed), tok.data_ptr(), pos.data_ptr(),
+                               lens.data_ptr(), step.data_ptr(), hist.data_ptr(), hist.shape[1],
+                               _ptr(eos) if n_eos else None, n_eos, readback.data_ptr(), stream_ptr(dev))
+    check(rc, "mls_spec_accept")

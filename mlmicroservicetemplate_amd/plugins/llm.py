@@ -38,6 +38,7 @@ class LlamaPlugin(ModelPlugin):
         self.comm_dev = None
         self.prefill_chunk = 0
         self.speculate, self.speculate_ngram = 0, 3
+        self.speculate_device = False
         self.prefix_cache = False
         self.kv_pages = 0
         self._lock = threading.Lock()
@@ -50,6 +51,7 @@ class LlamaPlugin(ModelPlugin):
         extra = s.model_yaml() if hasattr(s, "model_yaml") else {}
         weight_dtype = self.parse_weight_dtype(extra)  # before any weight is read or allocated
         self.speculate, self.speculate_ngram = self.parse_speculate(extra)
+        self.speculate_device = self.parse_speculate_device(extra, self.speculate)
         self.prefix_cache = self.parse_prefix_cache(extra)
         size = extra.get("config", "8b")
         cfg = llama.LLAMA3_8B if size == "8b" else llama.tiny_config(**extra.get("overrides", {}))
@@ -84,6 +86,8 @@ class LlamaPlugin(ModelPlugin):
                                    kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_prefill=kv_prefill)
         if self.speculate:  # refused at start-up on the lockstep path too (the engine below checks for itself)
             self.model.check_speculate(self.speculate)
+        if self.speculate_device:  # no device loop (reference backend, CPU, graphs off ...): refused, nothing falls back
+            self.model.check_spec_device(self.speculate)
         if self.prefix_cache:  # no paged KV, fp8 KV with kv_prefill: rows, row-major cache, head_dim != 128: refused, nothing falls back
             self.model.check_prefix_cache()
             if not bool(getattr(s, "CONTINUOUS_BATCHING", True)):
@@ -96,7 +100,8 @@ class LlamaPlugin(ModelPlugin):
 
             self.engine = ContinuousLlama(self.model, max_queue=int(s.MAX_QUEUE), channel=self if tp > 1 else None,
                                           prefill_chunk=self.prefill_chunk, speculate=self.speculate,
-                                          drafter=self._drafter(), prefix_cache=self.prefix_cache)
+                                          drafter=self._drafter(), prefix_cache=self.prefix_cache,
+                                          **self._spec_device_kw())
             if ctx.rank == 0:
                 self.engine.start()
         self.kv_pages = kv_pages
@@ -135,8 +140,24 @@ class LlamaPlugin(ModelPlugin):
             out.append(v)
         return tuple(out)
 
+    @staticmethod
+    def parse_speculate_device(extra: dict, speculate: int) -> bool:
+        """MODEL_CONFIG ``speculate_device``: ``true`` | ``false`` (default): with ``speculate``, verify
+        steps draft (prompt lookup, ``speculate_ngram``) and accept on device inside the captured step
+        (models/llama_serving.py); needs ``speculate >= 1``."""
+        v = extra.get("speculate_device", False)
+        if not isinstance(v, bool):
+            raise ValueError(f"speculate_device must be true or false, got {v!r}")
+        if v and not speculate:
+            raise ValueError("speculate_device needs speculate >= 1")
+        return v
+
+    def _spec_device_kw(self) -> dict:
+        """``spec_device`` / ``spec_ngram`` of the engine and of ``generate`` (nothing when off)."""
+        return dict(spec_device=True, spec_ngram=(self.speculate_ngram, 1)) if self.speculate_device else {}
+
     def _drafter(self):
-        if not self.speculate:
+        if not self.speculate or self.speculate_device:  # on device the drafter is the kernel's prompt lookup
             return None
         from ..models.speculative import make_prompt_lookup
 
@@ -269,7 +290,7 @@ class LlamaPlugin(ModelPlugin):
         with self._lock:
             self._broadcast_cmd(OP_GENERATE, ids, lens, gp)
             out = self.model.generate(ids, lens, gp, prefill_chunk=self.prefill_chunk, speculate=self.speculate,
-                                      drafter=self._drafter())
+                                      drafter=self._drafter(), **self._spec_device_kw())
         return out.cpu().tolist()
 
     # ---- the continuous engine's TP control channel (models/llama_serving.py ContinuousLlama):
@@ -385,7 +406,8 @@ class LlamaPlugin(ModelPlugin):
             dist.broadcast(ids, src=0)
             dist.broadcast(lens, src=0)
             self.model.generate(ids, lens, GenParams(mnt, topk, temp / 1000.0, seed),
-                                prefill_chunk=self.prefill_chunk, speculate=self.speculate, drafter=self._drafter())
+                                prefill_chunk=self.prefill_chunk, speculate=self.speculate, drafter=self._drafter(),
+                                **self._spec_device_kw())
 
     def close(self) -> None:
         if self.engine is not None and self.ctx.rank == 0:
@@ -403,7 +425,8 @@ class LlamaPlugin(ModelPlugin):
         if self.model is not None:
             d.update({"tp": self.model.tp, "backend": self.model.backend, "max_batch": self.model.max_batch,
                       "max_seq": self.model.max_seq, "speculate": self.speculate,
-                      "speculate_ngram": self.speculate_ngram, "prefix_cache": self.prefix_cache,
+                      "speculate_ngram": self.speculate_ngram, "speculate_device": self.speculate_device,
+                      "prefix_cache": self.prefix_cache,
                       "kv_dtype": self.model.kv_dtype, "kv_prefill": self.model.kv_prefill,
                       "kv_pages": self.kv_pages, "prefill_chunk": self.prefill_chunk})
         return d
