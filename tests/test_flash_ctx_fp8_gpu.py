@@ -16,6 +16,7 @@ import sys
 import pytest
 import torch
 
+import attn_cases as A
 from mlmicroservicetemplate_amd.ops import reference as R
 
 pytestmark = pytest.mark.gpu
@@ -81,8 +82,11 @@ def _case(Hq, Hkv, S, seed=0, pasts=PASTS, max_seq=MAX_SEQ, slot_ids=(7, 2, 8, 0
     ref = R.attention_ctx(qkv, R.kv_dequant_fp8(kc, ks), R.kv_dequant_fp8(vc, vs), past, lens, B, S, Hq, Hkv, D,
                           slot_ids=slot_ids, head_major=True)
     assert torch.isfinite(ref).all()
-    return dict(B=B, S=S, Hq=Hq, Hkv=Hkv, past=past, n=n, lens=lens, qkv=qkv, slot_ids=slot_ids, kc=kc, vc=vc, ks=ks,
-                vs=vs, table=table, kp=kp, vp=vp, ksp=ksp, vsp=vsp, ref=ref, max_ctx=int(lens.max()))
+    # per (row, head) bound: 4 x the rounding model on the dequantised rows (tests/attn_cases.py)
+    tol = A.tolerance(A.rows_ctx(qkv, R.kv_dequant_fp8(kc, ks), R.kv_dequant_fp8(vc, vs), past, lens, B, S, Hq, Hkv, D,
+                                 slot_ids), D)
+    return dict(tol=tol, B=B, S=S, Hq=Hq, Hkv=Hkv, past=past, n=n, lens=lens, qkv=qkv, slot_ids=slot_ids, kc=kc, vc=vc,
+                ks=ks, vs=vs, table=table, kp=kp, vp=vp, ksp=ksp, vsp=vsp, ref=ref, max_ctx=int(lens.max()))
 
 
 _CASES = {}
@@ -134,6 +138,7 @@ def test_fp8_ctx_vs_oracle(ops, Hq, Hkv, S):
             err = rel(_valid(out, c), want)
             print(f"Hq={Hq} Hkv={Hkv} S={S} splits={splits} paged={paged}: rel vs oracle {err:.5f}")
             assert err < BOUND
+            assert A.head_err(_valid(out, c), want, D).max() < c["tol"]
             assert not _padding(out, c).any()  # rows q >= n are zeros
 
 
@@ -168,9 +173,12 @@ def test_graph_replay_follows_past_and_lens(ops):
                               B, S, Hq, c["Hkv"], D, slot_ids=c["slot_ids"], head_major=True)
         assert torch.equal(outs[0], eager)
         cur = dict(c, n=ln - pa)
+        tol = A.tolerance(A.rows_ctx(c["qkv"], R.kv_dequant_fp8(c["kc"], c["ks"]), R.kv_dequant_fp8(c["vc"], c["vs"]),
+                                     pa, ln, B, S, Hq, c["Hkv"], D, c["slot_ids"]), D)
         for o in outs:
             assert torch.isfinite(o.float()).all()
             assert rel(_valid(o, cur), _valid(ref, cur)) < BOUND
+            assert A.head_err(_valid(o, cur), _valid(ref, cur), D).max() < tol
             assert not _padding(o, cur).any()
 
 

@@ -4,6 +4,7 @@ dequantised cache, and the fused Llama with ``kv_dtype="fp8"`` against its refer
 import pytest
 import torch
 
+import attn_cases as A
 from mlmicroservicetemplate_amd.ops import reference as R
 from test_kv_fp8_cpu import CFG128, D_REF, decode_top5_deviation, roundtrip_bound
 
@@ -134,10 +135,12 @@ def test_decode_plain(ops, Hq, Hkv, chunk):
     lens = torch.tensor([1, 64, 65, 300, 512], device=DEV, dtype=torch.int32)
     cnt = torch.zeros(B * Hkv, device=DEV, dtype=torch.int32)
     ref = R.decode_attention(q, kd, vd, lens, Hq, Hkv, D)
+    tol = A.tolerance(A.rows_decode(q, kd, vd, lens, Hq, Hkv, D), D)  # per (row, head): tests/attn_cases.py
     for _ in range(3):
         out = ops.decode_attention_fp8(q, k8, v8, ks, vs, lens, Hq, Hkv, D, chunk=chunk, counters=cnt)
         print("plain rel", rel(out, ref))
         assert rel(out, ref) < 2e-2
+        assert A.head_err(out, ref, D).max() < tol
     assert not cnt.any()
     # combine=False + the o-projection's fused combine == combine=True + the plain packed GEMM
     # (tests/test_skinny_packed_gpu.py test_packed_combine_matches_attention_then_gemm, M <= 4 rows)
@@ -168,6 +171,7 @@ def test_decode_plain_many_splits(ops, L, max_len):
     out = ops.decode_attention_fp8(q, k8, v8, ks, vs, lens, Hq, Hkv, D, chunk=chunk)
     print("many splits rel", rel(out, ref))
     assert rel(out, ref) < 2e-2
+    assert A.head_err(out, ref, D).max() < A.tolerance(A.rows_decode(q, kd, vd, lens, Hq, Hkv, D), D)
 
 
 # ------------------------------------------------------------------------------- 3. rope + append
@@ -192,6 +196,8 @@ def test_decode_rope_append(ops, Hq, Hkv, chunk):
     ref = R.decode_attention(qkv2, _deq_rows(k8, ks), _deq_rows(v8, vs), lens, Hq, Hkv, D)
     print("rope rel", rel(out, ref))
     assert rel(out, ref) < 1e-2
+    rows = A.rows_decode(qkv2, _deq_rows(k8, ks), _deq_rows(v8, vs), lens, Hq, Hkv, D)
+    assert A.head_err(out, ref, D).max() < A.tolerance(rows, D)
 
 
 # ------------------------------------------------------------------------------- 4. paged == contiguous
