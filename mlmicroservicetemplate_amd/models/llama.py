@@ -480,11 +480,26 @@ class LlamaTP:
         keeps the packed codes (``self.w4``) and streams them in decode steps of up to
         ``w4_max_rows`` rows (``ops.skinny_w4``), larger steps run the bf16 rounding of the same
         weights.  Every quantised matrix needs K % 128 == 0 on this rank (row-parallel shards
-        then cut K at group boundaries, so every TP degree sees the same groups).  Changes numerics."""
+        then cut K at group boundaries, so every TP degree sees the same groups).  Changes numerics.
+        ``weight_dtype="w8a8"``: FP8 (e4m3) layer projections with e4m3 activations -- one fp32 scale per
+        output channel (``ops.reference.w8_quant``, on the weights as held: gains folded, gate / up
+        interleaved on the fused backend) and one dynamic scale per activation row
+        (``ops.reference.a8_quant`` of the bf16-valued row that enters the projection; the two normalised
+        projections quantise the un-normalised residual row and multiply its scale by its ``rstd``).
+        ``lm_head`` and the embedding stay bf16.  One rule at every row count, so a row's result depends on
+        that row alone and chunked prefill, prefix caching and speculation compose with it.  Reference
+        backend: ``self.p`` holds the dequantised weights, ``self.w8`` the codes every projection multiplies
+        (``ops.reference.w8a8_linear``).  Fused backend: ``self.w8`` holds ``ops.pack_w8``'s codes + scales
+        and nothing else of a quantised matrix (no bf16, granule-packed or ``MLS_DECODE_FP8`` copy); every
+        layer projection is ``ops.quant_rows_fp8`` + ``ops.gemm_w8a8`` (the block-scaled MFMA), the TP
+        all-reduce and the split-KV combine run as their own launches.  Every layer matrix needs
+        K % 128 == 0 and N % 16 == 0 on this rank (``ValueError`` otherwise: nothing falls back).  Changes
+        numerics (e4m3 keeps 3 mantissa bits of weights AND activations); at TP > 1 a row-parallel projection
+        quantises each rank's K slice with its own row scale, so logits differ slightly from TP = 1."""
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
-        if weight_dtype not in ("bf16", "int4"):
-            raise ValueError(f"weight_dtype must be 'bf16' or 'int4', got {weight_dtype!r}")
+        if weight_dtype not in ("bf16", "int4", "w8a8"):
+            raise ValueError(f"weight_dtype must be 'bf16', 'int4' or 'w8a8', got {weight_dtype!r}")
         if kv_prefill not in ("rows", "cache"):
             raise ValueError(f"kv_prefill must be 'rows' or 'cache', got {kv_prefill!r}")
         if kv_prefill == "cache" and kv_dtype != "fp8":
@@ -512,6 +527,12 @@ class LlamaTP:
             self._check_int4_shapes()
             if backend != "fused":
                 self._quantise_reference()
+        # w8a8: name -> (e4m3 codes, fp32 scales per output row, N); reference: codes [N, K], fused: ops.pack_w8's
+        self.w8: Dict[str, Tuple[torch.Tensor, torch.Tensor, int]] = {}
+        if weight_dtype == "w8a8":
+            self._check_w8a8_shapes()
+            if backend != "fused":
+                self._quantise_reference_w8()
         # the fused forward's switches and copies of the weights (name -> tensors), set on both backends
         # so that whatever reads them needs no default; models/llama_route.py holds the rules they feed
         self.packed: Dict[str, torch.Tensor] = {}  # granule-packed bf16 copies (_pack_decode_copies)
@@ -592,6 +613,29 @@ class LlamaTP:
             for gain in ("attn_norm", "mlp_norm"):
                 self.p[f"l{i}.{gain}"] = torch.ones_like(self.p[f"l{i}.{gain}"])
 
+    def _check_w8a8_shapes(self) -> None:
+        for i in range(self.cfg.layers):
+            for n in ("qkv", "o", "gate", "up", "down"):
+                N_, K_ = self.p[f"l{i}.{n}"].shape
+                if K_ % 128 or N_ % 16:
+                    raise ValueError(f"weight_dtype='w8a8': l{i}.{n} is [{N_}, {K_}] on this rank (tp {self.tp}); "
+                                     f"needs K % 128 == 0 and N % 16 == 0")
+
+    def _quantise_reference_w8(self) -> None:
+        """``weight_dtype="w8a8"`` on the reference backend, the CPU oracle: gains folded as ops.fold_norm,
+        then ``R.w8_quant``: ``self.w8`` keeps the codes + scales the projections multiply, ``self.p`` the
+        exact dequantised product under the unchanged keys; the folded norms become ones."""
+        for i in range(self.cfg.layers):
+            for n, gain in (("qkv", "attn_norm"), ("gate", "mlp_norm"), ("up", "mlp_norm"), ("o", None), ("down", None)):
+                w = self.p[f"l{i}.{n}"]
+                if gain is not None:
+                    w = (w.float() * self.p[f"l{i}.{gain}"].float().view(1, -1)).to(w.dtype)
+                q, sc = R.w8_quant(w)
+                self.w8[f"l{i}.{n}"] = (q, sc, w.shape[0])
+                self.p[f"l{i}.{n}"] = R.w8_dequant(q, sc)
+            for gain in ("attn_norm", "mlp_norm"):
+                self.p[f"l{i}.{gain}"] = torch.ones_like(self.p[f"l{i}.{gain}"])
+
     def _alloc_kv_cache(self, kv_pages: int) -> None:
         """The per-layer K / V caches (paged pools with ``kv_pages > 0``), their layout flags and, for an
         e4m3 cache on the fused backend, the scale tensors."""
@@ -643,6 +687,13 @@ class LlamaTP:
             self.p[f"l{i}.gate_up"] = ops.fold_norm(gu, mlp_g)
             self.p[f"l{i}.qkv"] = ops.fold_norm(self.p[f"l{i}.qkv"], self.p.pop(f"l{i}.attn_norm"))
         self.p["lm_head"] = ops.fold_norm(self.p["lm_head"], self.p.pop("final_norm"))
+        if weight_dtype == "w8a8":
+            # quantised as held here; the codes + scales are ALL the model keeps of a layer matrix
+            for i in range(cfg.layers):
+                for n in ("qkv", "o", "gate_up", "down"):
+                    w = self.p.pop(f"l{i}.{n}")
+                    self.w8[f"l{i}.{n}"] = (*ops.pack_w8(w), w.shape[0])
+                    del w
         if weight_dtype != "int4":
             return
         # quantised as held here (gain folded, gate / up interleaved: a row permutation).  p
@@ -667,6 +718,7 @@ class LlamaTP:
         if self.device.type != "cuda":
             return
         names = [f"l{i}.{n}" for i in range(cfg.layers) for n in ("qkv", "o", "gate_up", "down")] + ["lm_head"]
+        names = [n for n in names if n in self.p]  # w8a8: the layer matrices live in self.w8 alone
         # Decode (<= 24 tokens per step) streams a second, granule-packed copy of every projection
         # (ops.pack_skinny: each wave reads contiguous 1 KiB granules, non-temporal): 3.4-4.5 ->
         # 4.6-6.2 TB/s on the Llama-3-8B shapes (profiles/r2_decode_packed_weight_probe.jsonl).
@@ -700,8 +752,11 @@ class LlamaTP:
 
     def layer_weight_bytes(self) -> int:
         """Bytes of the layer projections a decode step streams on this rank: the int4 codes + scales
-        where the model holds them (fused ``weight_dtype="int4"``), else the matrices as held."""
+        where the model holds them (fused ``weight_dtype="int4"``), the e4m3 codes + scales of fused
+        ``weight_dtype="w8a8"``, else the matrices as held."""
         total = 0
+        if self.backend == "fused":
+            total += sum(t.numel() * t.element_size() for wq, ws, _ in self.w8.values() for t in (wq, ws))
         for name, w in self.p.items():
             if name.rsplit(".", 1)[-1] in ("qkv", "o", "gate", "up", "gate_up", "down"):
                 held = self.w4.get(name, (w,))
@@ -743,8 +798,12 @@ class LlamaTP:
                    slots_b: torch.Tensor, decode: bool, past: Optional[torch.Tensor] = None) -> torch.Tensor:
         cfg, sd, p = self.cfg, self.sd, self.p
         D = cfg.head_dim
-        xn = R.layernorm(x, p[f"l{i}.attn_norm"], None, eps=cfg.eps, rms=True)[0]
-        qkv = xn @ p[f"l{i}.qkv"].float().T
+        w8 = self.weight_dtype == "w8a8"
+        if w8:
+            qkv = self._ref_w8(f"l{i}.qkv", x, norm=True)
+        else:
+            xn = R.layernorm(x, p[f"l{i}.attn_norm"], None, eps=cfg.eps, rms=True)[0]
+            qkv = xn @ p[f"l{i}.qkv"].float().T
         T = qkv.shape[0]
         # chunked prefill: a padding row's position may lie past the RoPE table (it is never stored)
         rpos = positions if past is None else positions.clamp(max=self.max_seq - 1)
@@ -786,12 +845,24 @@ class LlamaTP:
                                     slot_ids=slots_b, page_table=table)
             else:
                 a = R.attention(qkv_r, B, S, sd.hq, sd.hkv, D, kv_lens=lens, causal=True)
+        if w8:
+            x = x + self.comm.all_reduce_(self._ref_w8(f"l{i}.o", a))
+            h = F.silu(self._ref_w8(f"l{i}.gate", x, norm=True)) * self._ref_w8(f"l{i}.up", x, norm=True)
+            return x + self.comm.all_reduce_(self._ref_w8(f"l{i}.down", h))
         o = self.comm.all_reduce_(a @ p[f"l{i}.o"].float().T)
         x = x + o
         xn = R.layernorm(x, p[f"l{i}.mlp_norm"], None, eps=cfg.eps, rms=True)[0]
         h = F.silu(xn @ p[f"l{i}.gate"].float().T) * (xn @ p[f"l{i}.up"].float().T)
         d = self.comm.all_reduce_(h @ p[f"l{i}.down"].float().T)
         return x + d
+
+    def _ref_w8(self, name: str, x: torch.Tensor, norm: bool = False) -> torch.Tensor:
+        """The W8A8 projection of the rows ``x`` (rounded to bf16) by W_name; ``norm``: of RMSNorm(x), its gain
+        folded into W -- the un-normalised row is quantised and rstd multiplies its scale."""
+        h = x.to(torch.bfloat16)
+        rstd = torch.rsqrt(h.float().pow(2).mean(-1) + self.cfg.eps) if norm else None
+        wq, ws, _ = self.w8[name]
+        return R.w8a8_linear(h, wq, ws, rstd)
 
     def _ref_forward(self, ids: torch.Tensor, positions: torch.Tensor, lens: torch.Tensor, B: int, S: int,
                      decode: bool, k: int, slot_ids: Optional[torch.Tensor] = None,
@@ -816,6 +887,7 @@ class LlamaTP:
         return step_route(
             B=B, S=S, decode=decode, has_past=has_past, all_rows=all_rows, tp=self.tp, hq=sd.hq, hkv=sd.hkv,
             head_dim=cfg.head_dim, hidden=cfg.hidden, have_packed=bool(self.packed), have_w4=bool(self.w4),
+            have_w8=bool(self.w8),
             have_fp8=bool(self.fp8), o_packed="l0.o" in self.packed, o_fp8="l0.o" in self.fp8, kv_fp8=self.kv_fp8,
             w4_max_rows=self.w4_max_rows, pk_fold=self.pk_fold, prefill_fold=self.prefill_fold,
             fuse_combine=self.fuse_combine, fuse_add_norm=self.fuse_add_norm, ar_fuse=self.ar_fuse,
@@ -827,8 +899,14 @@ class LlamaTP:
     def _skinny(self, tr: ProjTiers, name: str, K: int):
         """The decode kernel over the copy of W_name that ``tr``'s row count streams -- int4 codes, e4m3,
         granule-packed bf16, in that order -- as ``f(x, **kw)``; None: the model holds no such copy (or
-        the rows are too many), the caller runs the row-major matrix."""
-        ops, N = self.ops, self.p[name].shape[0]
+        the rows are too many), the caller runs the row-major matrix.  A w8a8 matrix has one route at every
+        row count: quantise the rows, then the block-scaled MFMA GEMM."""
+        ops = self.ops
+        if name in self.w8:
+            if not tr.w8:
+                raise RuntimeError(f"{name} is held as w8a8 codes only, and the route has no w8a8 tier")
+            return self._w8_proj(name)
+        N = self.p[name].shape[0]
         if tr.w4 and name in self.w4:
             return lambda x, **kw: ops.skinny_w4(x, *self.w4[name], N, variant=self.w4_variant, **kw)
         if tr.fp8_for(K) and name in self.fp8:
@@ -836,6 +914,15 @@ class LlamaTP:
         if tr.packed and name in self.packed:
             return lambda x, **kw: ops.skinny_packed(x, self.packed[name], N, variant=self.pk_variant, **kw)
         return None
+
+    def _w8_proj(self, name: str):
+        ops, (wq, ws, N) = self.ops, self.w8[name]
+
+        def run(x, delta=None, resid_out=None, norm=False, act=ops.ACT_NONE, eps=1e-5, residual=None):
+            xq, xs = ops.quant_rows_fp8(x, delta, resid_out, norm=norm, eps=eps)
+            return ops.gemm_w8a8(xq, xs, wq, ws, N, act=act, residual=residual, workspace=self.workspace)
+
+        return run
 
     def _proj(self, tr: ProjTiers, x: torch.Tensor, name: str, residual: Optional[torch.Tensor] = None):
         """``x @ W_name^T (+ residual)``."""
@@ -852,7 +939,7 @@ class LlamaTP:
         written nowhere.  ``xn``: RMSNorm(x) as a preceding :meth:`_proj_add_norm` staged it (``d`` is
         None then); ``impl``: ``ops.linear``'s, above 16 rows."""
         ops, eps, ws = self.ops, self.cfg.eps, self.workspace
-        w = self.p[name]
+        w = self.p.get(name)  # None: held as w8a8 codes, which _skinny routes below
         act = ops.ACT_NONE if act is None else act
         if xn is not None:
             return ops.linear(xn, w, act=act, workspace=ws), x

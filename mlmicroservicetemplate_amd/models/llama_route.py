@@ -10,13 +10,16 @@ from dataclasses import dataclass
 class ProjTiers:
     """The weight copies a projection of ``rows`` activation rows may stream, best first: int4 codes,
     e4m3, granule-packed bf16, then the row-major matrix (fused-norm skinny GEMM while ``fuse``,
-    RMSNorm + ``ops.linear`` above).  A copy is taken only if the model holds one of that matrix."""
+    RMSNorm + ``ops.linear`` above).  A copy is taken only if the model holds one of that matrix.  ``w8``
+    stands apart: a ``weight_dtype="w8a8"`` model holds its layer matrices as e4m3 codes only, so that tier
+    serves them at every row count (the lm_head, never quantised, walks the ladder without it)."""
 
     rows: int
     w4: bool
     fp8: bool
     packed: bool
     fuse: bool
+    w8: bool = False  # weight_dtype="w8a8": the only copy of a layer matrix, at every row count
 
     def fp8_for(self, K: int) -> bool:
         """The e4m3 tier for a projection of inner size K: ops.skinny_fp8 takes rows * K bf16 activations
@@ -24,8 +27,14 @@ class ProjTiers:
         return self.fp8 and self.rows * K * 2 <= 65536
 
 
-def proj_tiers(rows: int, have_packed: bool, have_w4: bool, have_fp8: bool, w4_max_rows: int) -> ProjTiers:
+def proj_tiers(rows: int, have_packed: bool, have_w4: bool, have_fp8: bool, w4_max_rows: int,
+               have_w8: bool = False) -> ProjTiers:
     return ProjTiers(
+        # weight_dtype="w8a8": every layer projection, at every row count, is ops.quant_rows_fp8 +
+        # ops.gemm_w8a8 on the e4m3 codes (the model holds nothing else of those matrices); the all-reduce
+        # and the split-KV combine run as their own launches, as with int4.  Steps of <= 4 rows stay on it
+        # too: ops.skinny_fp8 would need a second packed copy and was not measured ahead
+        w8=have_w8,
         rows=rows,
         # weight_dtype="int4": the layer projections stream their 4-bit codes (ops.skinny_w4) instead;
         # no all-reduce tail / combine prologue there, so those run as separate launches.  Up to
@@ -80,19 +89,20 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
                head_dim: int, hidden: int, have_packed: bool, have_w4: bool, have_fp8: bool, o_packed: bool,
                o_fp8: bool, w4_max_rows: int, pk_fold: bool, prefill_fold: bool, fuse_combine: bool,
                fuse_add_norm: bool, ar_fuse: bool, tp_overlap: bool, verify_attn: str, spec_max_tokens: int,
-               dec_chunk: int, ar_fusable: bool, capturing: bool, kv_fp8: bool = False) -> StepRoute:
+               dec_chunk: int, ar_fusable: bool, capturing: bool, kv_fp8: bool = False,
+               have_w8: bool = False) -> StepRoute:
     """``have_*``: the model holds such copies at all; ``o_packed`` / ``o_fp8``: of ``l0.o``;
     ``ar_fusable``: the comm's one-shot all-reduce can ride in a GEMM producing ``B * S * hidden``
     outputs; ``capturing``: the current stream is capturing a graph.  The rest are the model's
     dimensions on this rank and its switches under their own names; ``kv_fp8``: the cache is e4m3."""
     T = B * S
-    proj = proj_tiers(T, have_packed, have_w4, have_fp8, w4_max_rows)
+    proj = proj_tiers(T, have_packed, have_w4, have_fp8, w4_max_rows, have_w8)
     # TP = 1: the residual add rides in the o / down epilogues (h = r + a Wo^T, r' = h + g Wd^T), so
     # the next pre-norm GEMM reads one activation stream instead of two (r + delta) and writes no
     # residual copy.  With TP > 1 the add has to wait for the all-reduce.  prefill_fold: prefill at
     # TP = 1 with the residual add in the o / down GEMM epilogues too (the following RMSNorm then reads
     # one stream and writes one: 64 instead of 128 B per element)
-    fold = tp == 1 and (((proj.packed or proj.w4) and pk_fold) or (not decode and prefill_fold))
+    fold = tp == 1 and (((proj.packed or proj.w4 or proj.w8) and pk_fold) or (not decode and prefill_fold))
     # decode: the o-projection merges the split-KV partials in its prologue (one launch instead of
     # two) while every block's share of partials is small -- B x local q heads <= 32: one emulated
     # TP = 8 rank 1.166 -> 1.125 ms/token at batch 1, 1.294 -> 1.254 at 4; TP = 1 batch 1 level,
@@ -108,7 +118,7 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
     # slabs to one kernel that adds them to the residual stream and normalises it for the next
     # projection (ops.linear_add_rmsnorm) -- one launch instead of reduce + RMSNorm, bit-identical.
     # A projection it cannot take (no split on that shape) runs the plain pair.
-    fuse_rn = tp == 1 and not proj.packed and not proj.fuse and not fold and fuse_add_norm
+    fuse_rn = tp == 1 and not proj.packed and not proj.fuse and not fold and fuse_add_norm and not proj.w8
     # a verify step (all_rows: every row's candidates) of a few positions per sequence: its attention
     # runs split-KV on the matrix cores with the T positions x G heads of a KV head on one MFMA's lane
     # columns (ops.decode_attention_multi); MLS_VERIFY_ATTN=ctx keeps the chunk kernel (the A/B arm).

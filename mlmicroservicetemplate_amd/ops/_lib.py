@@ -121,6 +121,9 @@ _SIGS = {
     "mls_skinny_fp8": [P, P, P, P, P, P, P, P, I, I, I, I, I, F, I, P],
     "mls_skinny_w4": [P, P, P, P, P, P, P, P, I, I, I, I, I, F, I, P],
     "mls_skinny_w4_num_variants": [],
+    "mls_gemm_w8a8": [P, P, P, P, P, P, P, I, I, I, I, I, I, P, _c.c_longlong, P, I, P],
+    "mls_gemm_w8a8_num_variants": [],
+    "mls_quant_rows_fp8": [P, P, P, P, P, I, I, I, F, P],
     "mls_stream_create_cumask": [P, I, _c.POINTER(P)],
     "mls_stream_get_cumask": [P, P, I],
     "mls_stream_destroy": [P],

@@ -7,7 +7,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from ._lib import check, lib, stream_ptr
-from ._core import ACT_GELU, ACT_NONE, ACT_SILU_MUL, _act, _need, _ptr, _workspace_args
+from ._core import ACT_GELU, ACT_NONE, ACT_SILU_MUL, StreamWorkspace, _act, _need, _ptr, _workspace_args
 
 
 def gemm(
@@ -533,6 +533,134 @@ def skinny_w4(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, N: int, *
                              _ptr(bias), _ptr(residual), out.data_ptr(), M, N, K, code, int(norm), float(eps),
                              int(variant), stream_ptr(dev))
     check(rc, "mls_skinny_w4")
+    return out
+
+
+W8A8_CFGS = {1: (256, 256), 2: (256, 128), 3: (128, 128), 4: (64, 128), 5: (32, 128)}  # variant -> (BM, BN)
+W8A8_VARIANTS = 6  # launch shapes of csrc/gemm_w8a8.hip (0: the launcher's pick; 4 / 5: decode-shaped, split-K)
+_W8_WORKSPACE: Dict[int, StreamWorkspace] = {}
+
+
+def _w8_bytes(t: torch.Tensor, name: str, dev: torch.device, numel: int) -> None:
+    if t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{name}: contiguous uint8 of {numel} e4m3 codes on {dev}")
+
+
+def _w8_f32(t: torch.Tensor, name: str, dev: torch.device, numel: int) -> None:
+    if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{name}: contiguous fp32 of {numel} elements on {dev}")
+
+
+def _w8_bf16(t: torch.Tensor, name: str, dev: torch.device, shape) -> None:
+    if t.dtype != torch.bfloat16 or t.device != dev or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: contiguous bf16 {list(shape)} on {dev}")
+
+
+def quant_rows_fp8(x: torch.Tensor, delta: Optional[torch.Tensor] = None, resid_out: Optional[torch.Tensor] = None,
+                   norm: bool = False, eps: float = 1e-5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Activation rows -> ``(e4m3 codes uint8 [M, K], fp32 scale [M])`` by ``reference.a8_quant``'s rule, one
+    pass per row (csrc/gemm_w8a8.hip): ``h = bf16(x + delta)`` (written to ``resid_out`` when given), codes of
+    ``h``, and ``scale = hs``, or ``hs * rsqrt(mean(h^2) + eps)`` with ``norm`` (the RMSNorm of a projection
+    whose gain is folded into its weights).  Codes and the ``norm=False`` scales match the rule bit for bit."""
+    dev = x.device
+    if x.dim() != 2:
+        raise ValueError("quant_rows_fp8: x [M, K]")
+    M, K = x.shape
+    _w8_bf16(x, "x", dev, (M, K))
+    if M < 1 or K % 8 or K > 65536:
+        raise ValueError("quant_rows_fp8: M >= 1, K % 8 == 0, K <= 65536")
+    if resid_out is not None and delta is None:
+        raise ValueError("resid_out needs delta")
+    for name, t in (("delta", delta), ("resid_out", resid_out)):
+        if t is not None:
+            _w8_bf16(t, name, dev, (M, K))
+    xq = torch.empty(M, K, device=dev, dtype=torch.uint8)
+    xs = torch.empty(M, device=dev, dtype=torch.float32)
+    rc = lib().mls_quant_rows_fp8(x.data_ptr(), _ptr(delta), _ptr(resid_out), xq.data_ptr(), xs.data_ptr(), M, K,
+                                  int(bool(norm)), float(eps), stream_ptr(dev))
+    check(rc, "mls_quant_rows_fp8")
+    return xq, xs
+
+
+def pack_w8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``w [N, K]`` (N % 16 == 0, K % 128 == 0) -> ``(e4m3 codes, flat uint8 [N * K]; fp32 scales [N])`` by
+    ``reference.w8_quant``, in the layout :func:`gemm_w8a8`'s LDS-DMA reads: row-major ``[N][K]`` -- the
+    kernel applies its LDS bank swizzle on the source address, so the weights need no shuffled copy."""
+    from .reference import w8_quant
+
+    if w.dim() != 2 or w.shape[0] % 16 or w.shape[1] % 128:
+        raise ValueError("pack_w8: w [N, K], N % 16 == 0 and K % 128 == 0")
+    q, s = w8_quant(w)
+    return q.contiguous().reshape(-1), s.contiguous()
+
+
+def unpack_w8_reference(wq: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """Inverse of :func:`pack_w8`'s layout: the row-major codes ``uint8 [N, K]``."""
+    if wq.numel() != N * K:
+        raise ValueError("unpack_w8_reference: wq of N * K codes")
+    return wq.reshape(N, K)
+
+
+def w8a8_reference(xq: torch.Tensor, xs: torch.Tensor, wq_rowmajor: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+    """fp32 product of the same codes :func:`gemm_w8a8` multiplies: ``(xq . wq^T) * xs[m] * ws[n]``."""
+    from .reference import w8a8_product
+
+    return w8a8_product(xq, xs, wq_rowmajor, ws)
+
+
+def gemm_w8a8(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, N: int, *, act=ACT_NONE,
+              bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None, variant: int = 0, splitk: int = 0,
+              workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """FP8 W8A8 projection on the block-scaled MFMA (csrc/gemm_w8a8.hip): ``act((xq . wq^T) * xs[m] * ws[n] +
+    bias) (+ residual)`` as bf16 ``[M, N]``; ``act="silu_mul"``: gate / up rows interleaved in groups of 8
+    (:func:`interleave_gate_up`), output ``[M, N / 2]``.  ``(xq, xs)`` from :func:`quant_rows_fp8`, ``(wq, ws)``
+    from :func:`pack_w8``; any M >= 1, N % 16 == 0, K % 128 == 0.  ``variant``: the tile (:data:`W8A8_CFGS`, 0:
+    by shape); ``splitk``: K splits combined inside the launch, deterministically (0: the launcher's pick),
+    through fp32 slabs in ``workspace`` (default: a per-stream buffer of this module)."""
+    dev = xq.device
+    if xq.dim() != 2 or xq.dtype != torch.uint8 or not xq.is_contiguous():
+        raise ValueError("gemm_w8a8: xq contiguous uint8 [M, K]")
+    M, K = xq.shape
+    N = int(N)
+    if M < 1 or N < 1 or K % 128 or N % 16:
+        raise ValueError(f"gemm_w8a8: M >= 1, N ({N}) % 16 == 0, K ({K}) % 128 == 0")
+    if not 0 <= int(variant) < W8A8_VARIANTS:
+        raise ValueError(f"gemm_w8a8: variant in 0..{W8A8_VARIANTS - 1}")
+    _w8_f32(xs, "xs", dev, M)
+    _w8_bytes(wq, "wq", dev, N * K)
+    _w8_f32(ws, "ws", dev, N)
+    code = _act(act)
+    if code not in (ACT_NONE, ACT_SILU_MUL):
+        raise ValueError("gemm_w8a8: act none or silu_mul")
+    if bias is not None:
+        _w8_f32(bias, "bias", dev, N)
+    if residual is not None:
+        if code == ACT_SILU_MUL:
+            raise ValueError("silu_mul takes no residual")
+        _w8_bf16(residual, "residual", dev, (M, N))
+    n_out = N // 2 if code == ACT_SILU_MUL else N
+    if out is None:
+        out = torch.empty(M, n_out, device=dev, dtype=torch.bfloat16)
+    else:
+        _w8_bf16(out, "out", dev, (M, n_out))
+    if workspace is None:
+        pool = _W8_WORKSPACE.get(dev.index or 0)
+        if pool is None:
+            # one resident wave of split units x the largest splitting tile (128 x 128): 256 x 16k fp32
+            pool = _W8_WORKSPACE[dev.index or 0] = StreamWorkspace(4 << 20, dev)
+        workspace = pool.get()
+    elif workspace.dtype != torch.float32 or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("workspace: contiguous fp32 on the operands' device")
+    if int(splitk) > 1:
+        bm, bn = W8A8_CFGS[int(variant)] if int(variant) else (0, 0)
+        if not bm or (K // 128) % int(splitk) or -(-M // bm) * -(-N // bn) * int(splitk) * bm * bn > workspace.numel():
+            raise ValueError("gemm_w8a8: splitk needs a variant, (K / 128) % splitk == 0 and slabs that fit the workspace")
+    rc = lib().mls_gemm_w8a8(xq.data_ptr(), xs.data_ptr(), wq.data_ptr(), ws.data_ptr(), _ptr(bias), _ptr(residual),
+                             out.data_ptr(), M, N, K, code, int(variant), int(splitk), workspace.data_ptr(),
+                             workspace.numel(), split_counters(workspace).data_ptr(), SPLIT_COUNTER_ELEMS,
+                             stream_ptr(dev))
+    check(rc, "mls_gemm_w8a8")
     return out
 
 

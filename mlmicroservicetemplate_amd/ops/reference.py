@@ -168,5 +168,46 @@ def w4_dequant(q: torch.Tensor, scale: torch.Tensor, group: int = W4_GROUP) -> t
     return (q.float().reshape(N, K // group, group) * scale.float().unsqueeze(-1)).reshape(N, K)
 
 
+def w8_quant(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The W8A8 weight rule for ``w [N, K]``: :func:`kv_quant_fp8`'s rule with one scale per output row
+    (``scale = max(max|row|, 2^-40) / 448`` in fp32, ``q = e4m3fn_rne(row * (1 / scale))``), applied to the
+    weights as the backend holds them (RMSNorm gain folded in, gate / up interleaved on the fused backend).
+    Returns ``(uint8 [N, K], fp32 [N])``."""
+    if w.dim() != 2:
+        raise ValueError("w8_quant: w [N, K]")
+    return kv_quant_fp8(w)
+
+
+def a8_quant(h: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The W8A8 activation rule for ``h [M, K]``, the bf16-valued rows that enter a projection: the same
+    rule, one dynamic scale per row.  Returns ``(uint8 [M, K], fp32 [M])``."""
+    if h.dim() != 2:
+        raise ValueError("a8_quant: h [M, K]")
+    return kv_quant_fp8(h)
+
+
+def w8_dequant(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """fp32 ``float(q) * scale[n]`` of :func:`w8_quant`'s output: exact (4-bit times 24-bit significands)."""
+    return kv_dequant_fp8(q, scale)
+
+
+def w8a8_product(hq: torch.Tensor, hs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+    """``(sum_k float(hq) * float(wq)) * (hs[m] * ws[n])`` with fp32 accumulation: every e4m3 x e4m3 product is
+    exact in fp32, so two implementations differ in summation order only."""
+    acc = hq.view(torch.float8_e4m3fn).float() @ wq.view(torch.float8_e4m3fn).float().T
+    return acc * (hs.float().view(-1, 1) * ws.float().view(1, -1))
+
+
+def w8a8_linear(h: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, rstd: Optional[torch.Tensor] = None):
+    """The W8A8 projection of the rows ``h [M, K]`` (rounded to bf16 first: what enters a projection)
+    against :func:`w8_quant`'s ``(wq, ws)``: ``(sum_k float(hq) * float(wq)) * (hs * rstd)[m] * ws[n]``.
+    ``rstd [M]``: the normalised projections quantise the un-normalised residual row and multiply its scale
+    by ``rstd(h)`` -- a per-row dynamic scale absorbs a per-row scalar."""
+    hq, hs = a8_quant(h.to(torch.bfloat16))
+    if rstd is not None:
+        hs = hs * rstd.float().view(-1)
+    return w8a8_product(hq, hs, wq, ws)
+
+
 def gelu(x):
     return F.gelu(x)

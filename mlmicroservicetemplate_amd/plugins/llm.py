@@ -112,11 +112,12 @@ class LlamaPlugin(ModelPlugin):
 
     @staticmethod
     def parse_weight_dtype(extra: dict) -> str:
-        """MODEL_CONFIG ``weight_dtype``: ``bf16`` (default) | ``int4`` (W4A16 layer projections,
+        """MODEL_CONFIG ``weight_dtype``: ``bf16`` (default) | ``int4`` (W4A16 layer projections) | ``w8a8``
+        (e4m3 weights and activations on the block-scaled MFMA, at every batch size;
         :class:`~..models.llama.LlamaTP`)."""
         wd = str(extra.get("weight_dtype", "bf16"))
-        if wd not in ("bf16", "int4"):
-            raise ValueError(f"weight_dtype must be 'bf16' or 'int4', got {wd!r}")
+        if wd not in ("bf16", "int4", "w8a8"):
+            raise ValueError(f"weight_dtype must be 'bf16', 'int4' or 'w8a8', got {wd!r}")
         return wd
 
     @staticmethod

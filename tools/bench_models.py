@@ -478,8 +478,9 @@ def main():
     ap.add_argument("--kv-prefill", choices=["rows", "cache"], default="rows",
                     help="llama, --kv-dtype fp8: prefill attends its own bf16 rows, or the e4m3 cache rows (which "
                          "chunked prefill, prefix caching and speculation need)")
-    ap.add_argument("--weight-dtype", choices=["bf16", "int4"], default="bf16",
-                    help="llama: layer projections in bf16, or W4A16 (4-bit codes, one bf16 scale per row and 128 k)")
+    ap.add_argument("--weight-dtype", choices=["bf16", "int4", "w8a8"], default="bf16",
+                    help="llama: layer projections in bf16, W4A16 (4-bit codes, one bf16 scale per row and 128 k), or "
+                         "W8A8 (e4m3 weights per channel, e4m3 activations per row, block-scaled MFMA)")
     ap.add_argument("--max-seq", type=int, default=2048, help="llama: cache rows per sequence")
     ap.add_argument("--speculate", type=int, nargs="*", default=[],
                     help="llama: also time the verify step of K + 1 positions per sequence (speculative decoding)")
