@@ -10,10 +10,10 @@
 // forms run at the bf16 rate.  Every e4m3 x e4m3 product is exact in fp32, xs[m] * ws[n] multiplies the
 // fp32 accumulator in the epilogue.
 //
-// Structure: gemm_tile.hip's, one byte per element instead of two --
-//  * a k-step is 128 k = one 128-B LDS row per tile row, so the LDS image, the LDS-DMA (16 B per lane,
-//    swizzle chunk ^ ((row >> 1) & 7) applied on the SOURCE address) and the ds_read_b128 lane pattern are
-//    exactly the bf16 kernel's BK = 64 ones (conflict-free for the same reason);
+// Structure: gemm_ring.h's persistent LDS-DMA ring, split-K combine and tile epilogue (its SCALED form), one
+// byte per element instead of two --
+//  * a k-step is 128 k = one 128-B LDS row per tile row, so the LDS image, the LDS-DMA and the ds_read_b128
+//    lane pattern are exactly the bf16 kernel's BK = 64 ones (conflict-free for the same reason);
 //  * a lane's 32-byte operand (fr = lane & 15 the tile row, fq = lane >> 4 the k group) is two 16-B reads:
 //    k = 16 fq .. + 16 and k = 64 + 16 fq .. + 16 of the step.  The instruction pairs byte b of k group fq
 //    of its A operand with byte b of k group fq of its B operand, and both operands are read the same way,
@@ -21,20 +21,13 @@
 //    (tests/test_w8a8_gpu.py checks the map with exact one-hot rows);
 //  * at twice the MFMA rate and half the operand bytes per k the LDS read rate per clock equals the bf16
 //    kernel's at the same register tiling (32 B per lane per 16x16x128 step against 16 B per 16x16x32);
-//  * STAGES-deep ring, counted s_waitcnt vmcnt(N) and a raw s_barrier per k-step; swapped product (D = W_tile .
-//    A_tile^T: a lane owns consecutive output columns); XCD-aware persistent tile order; rows past M and
-//    columns past N read as zero through the buffer range check and are never stored;
-//  * in-launch split-K with fp32 slabs and per-tile arrival counters, summed in split order by the last
-//    arriver (deterministic): the short-M configurations split K so the weights stream once over the chip.
-// No data-dependent addressing: every offset is a function of the launch shape.
-#include "common.h"
+//  * the short-M configurations split K so the weights stream once over the chip.
+#include "gemm_ring.h"
 
 namespace {
 
-#define W8LDS3 __attribute__((address_space(3)))
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef unsigned w8u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr float W8_FP8_MAX = 448.f;
 constexpr float W8_AMAX_FLOOR = 9.094947017729282e-13f;  // 2^-40
@@ -55,185 +48,18 @@ struct W8Args {
   int splitk;  // K splits per output tile (>= 1)
   float* ws;   // [tiles][splitk][BM * BN] fp32 partial tiles (fragment-linear)
   int* cnt;    // [tiles] arrival counters: zero before the launch, reset by each tile's reducer
+  static constexpr bool SCALED = true;  // ring_epilogue_t: fma(acc, xs[m] * wsc[n], bias)
+  static constexpr int flags = 0;       // no ablation builds: the epilogue's flag tests fold away
+  MLS_DEV int res_pitch() const { return N; }
 };
 
-MLS_DEV void w8_glds16(rsrc_t r, char* lds, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (W8LDS3 void*)lds, 16, voff, soff, 0, 0);
-}
-
-template <int N>
-MLS_DEV void w8_wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt field");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-MLS_DEV void w8_barrier() {
-  // LDS-only wait + raw barrier: __syncthreads() would also wait vmcnt(0) and drain the ring
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-}
-
-MLS_DEV int w8_swz(int row) { return (row >> 1) & 7; }
-
-// tile order of gemm_tile.hip: GROUP_M-row bands walked column by column
-constexpr int W8_GROUP_M = 4;
-MLS_DEV void w8_tile(int t, int tiles_m, int tiles_n, int& tm, int& tn) {
-  const int per_band = W8_GROUP_M * tiles_n;
-  const int band = t / per_band, first = band * W8_GROUP_M;
-  const int gm = tiles_m - first < W8_GROUP_M ? tiles_m - first : W8_GROUP_M;
-  const int r = t - band * per_band;
-  tn = r / gm;
-  tm = first + (r - tn * gm);
-}
-
-// wait until at most LOADS * min(S - 2, left) of this wave's DMA groups are outstanding
-template <int STAGES, int LOADS>
-MLS_DEV void w8_wait_ring(int left) {
-  if constexpr (STAGES == 2) {
-    w8_wait_vmcnt<0>();
-  } else if constexpr (STAGES == 3) {
-    if (left >= 1) w8_wait_vmcnt<LOADS>();
-    else w8_wait_vmcnt<0>();
-  } else {
-    static_assert(STAGES == 4, "ring depth");
-    if (left >= 2) w8_wait_vmcnt<2 * LOADS>();
-    else if (left == 1) w8_wait_vmcnt<LOADS>();
-    else w8_wait_vmcnt<0>();
-  }
-}
-
-// Tile epilogue: lane (fr, fq) holds D[n = 4 fq + e][m = fr] of each 16 x 16 tile; v_permlane16_swap over
-// the column tiles (2p, 2p + 1) gives each lane 8 consecutive columns of its row (fq 0: tile 2p cols 0-7,
-// fq 1: tile 2p+1 cols 0-7, fq 2: tile 2p cols 8-15, fq 3: tile 2p+1 cols 8-15) -> 16-B range-checked
-// loads of the column scales / bias / residual and 16-B stores.  No memory op sits behind a per-element
-// branch.  EPI: 0 plain (+ bias), 1 + residual, 2 SiLU-mul (gate / up interleaved in groups of 8 columns:
-// gate on lanes fq 0 / 1, its up columns on fq 2 / 3 = lane ^ 32).
-template <int MT, int NTL, int EPI>
-MLS_DEV void w8_epilogue_t(f32x4 (&acc)[MT][NTL], const W8Args& g, int m0, int n0, int wrow, int wcol) {
-  static_assert(NTL % 2 == 0, "column tiles pair up");
-  const int lane = threadIdx.x & 63, fr = lane & 15, fq = lane >> 4;
-  const int ldo2 = g.ldo * 2, ldr2 = g.N * 2;
-  const int rows = g.M - m0 < 256 ? g.M - m0 : 256;  // valid rows of this tile (tiles are <= 256 tall)
-  const rsrc_t ro = make_rsrc(g.out + (size_t)m0 * g.ldo, (uint32_t)(rows * ldo2));
-  const rsrc_t rr = make_rsrc(EPI == 1 ? g.res + (size_t)m0 * g.N : g.out, EPI == 1 ? (uint32_t)(rows * ldr2) : 0u);
-  const rsrc_t rb = make_rsrc(g.bias ? (const void*)g.bias : (const void*)g.out, g.bias ? (uint32_t)g.N * 4u : 0u);
-  const rsrc_t rw = make_rsrc(g.wsc, (uint32_t)g.N * 4u);
-  const rsrc_t rx = make_rsrc(g.xs + m0, (uint32_t)rows * 4u);
-  const int sub = (fq & 1) * 16 + (fq >> 1) * 8;  // this lane's 8 columns within the 32-column pair
-  float xs[MT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-    xs[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, (wrow + i * 16 + fr) * 4, 0, 0));
-#pragma unroll
-  for (int p = 0; p < NTL / 2; ++p) {
-    const int c0 = n0 + wcol + p * 32, c = c0 + sub;
-    const bool col_ok = c < g.N;  // N % 16 == 0: an 8-column run is wholly in or out
-    const f32x4 b_lo = __builtin_bit_cast(f32x4, bload16(rb, col_ok ? c * 4 : OOB));
-    const f32x4 b_hi = __builtin_bit_cast(f32x4, bload16(rb, col_ok ? c * 4 + 16 : OOB));
-    const f32x4 s_lo = __builtin_bit_cast(f32x4, bload16(rw, col_ok ? c * 4 : OOB));
-    const f32x4 s_hi = __builtin_bit_cast(f32x4, bload16(rw, col_ok ? c * 4 + 16 : OOB));
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      const int r = wrow + i * 16 + fr;  // row within the tile
-      uint4 rcur = {0, 0, 0, 0};
-      if constexpr (EPI == 1) rcur = bload16(rr, col_ok ? r * ldr2 + c * 2 : OOB);
-      float v[8];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        // __float_as_uint, not __builtin_bit_cast (gemm_tile.hip: hipcc folds the latter to element 0)
-        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[i][2 * p][e]),
-                                                         __float_as_uint(acc[i][2 * p + 1][e]), false, false);
-        v[e] = fmaf(__uint_as_float(sw[0]), xs[i] * s_lo[e], b_lo[e]);
-        v[4 + e] = fmaf(__uint_as_float(sw[1]), xs[i] * s_hi[e], b_hi[e]);
-      }
-      bf16x8 o;
-      int off;
-      if constexpr (EPI == 2) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (bf16)(silu_fast(v[e]) * xor32_f(v[e]));
-        off = fq < 2 && col_ok ? r * ldo2 + ((c0 >> 1) + fq * 8) * 2 : OOB;
-      } else {
-        if constexpr (EPI == 1) {
-          const bf16x8 rb8 = __builtin_bit_cast(bf16x8, rcur);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += (float)rb8[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (bf16)v[e];
-        off = col_ok ? r * ldo2 + c * 2 : OOB;
-      }
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(w8u32x4, o), ro, off, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);  // keep each row block's live range to itself
-    }
-  }
-}
-
+// EPI of ring_epilogue_t: 0 plain (+ bias), 1 + residual, 2 SiLU-mul
 template <int MT, int NTL>
 MLS_DEV void w8_epilogue(f32x4 (&acc)[MT][NTL], const W8Args& g, int m0, int n0, int wrow, int wcol) {
-  if (g.act == ACT_SILU_MUL) w8_epilogue_t<MT, NTL, 2>(acc, g, m0, n0, wrow, wcol);
-  else if (g.res) w8_epilogue_t<MT, NTL, 1>(acc, g, m0, n0, wrow, wcol);
-  else w8_epilogue_t<MT, NTL, 0>(acc, g, m0, n0, wrow, wcol);
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int jn = 0; jn < NTL; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // retire the epilogue's VMEM ops with the builtin wait, which hipcc's waitcnt pass sees: otherwise it
-  // carries them as pending around the k-loop back edge and drains the DMA ring at every k-step
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) expcnt(7) lgkmcnt(15)
-}
-
-// In-launch split-K combine (gemm_tile.hip gt_splitk_arrive): every split writes its fp32 partial tile as
-// a fragment-linear slab, one lane releases at agent scope and draws a ticket from the tile's counter;
-// the split that draws S - 1 acquires, sums ALL S slabs in split order (so the result does not depend on
-// which split arrived last: launches are bit-identical), resets the counter and runs the epilogue.
-template <int TILE_ELEMS, int MT, int NTL>
-MLS_DEV bool w8_splitk_arrive(f32x4 (&acc)[MT][NTL], const W8Args& g, int tile, int split, int* flag) {
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, S = g.splitk;
-  f32x4* const tile_ws = reinterpret_cast<f32x4*>(g.ws + (size_t)tile * S * TILE_ELEMS);
-  const int frag0 = wid * MT * NTL * 64 + lane;  // this lane's first f32x4 in a slab
-  f32x4* mine = tile_ws + (size_t)split * (TILE_ELEMS / 4) + frag0;
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int jn = 0; jn < NTL; ++jn) mine[(i * NTL + jn) * 64] = acc[i][jn];
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // every wave: its slab stores (and the ring's DMAs) retired
-  w8_barrier();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    const int old = __hip_atomic_fetch_add(g.cnt + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = old == S - 1;
-    if (last) {
-      __hip_atomic_store(g.cnt + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      __builtin_amdgcn_s_waitcnt(0x0F70);
-    }
-    *flag = last;
-  }
-  w8_barrier();
-  const bool last = __builtin_amdgcn_readfirstlane(*flag) != 0;
-  w8_barrier();  // flag read by every wave before this block's next unit can rewrite it
-  if (!last) {
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int jn = 0; jn < NTL; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
-    return false;
-  }
-  for (int s2 = 0; s2 < S; ++s2) {
-    const f32x4* slab = tile_ws + (size_t)s2 * (TILE_ELEMS / 4) + frag0;
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      f32x4 t[NTL];
-#pragma unroll
-      for (int jn = 0; jn < NTL; ++jn) t[jn] = slab[(i * NTL + jn) * 64];
-#pragma unroll
-      for (int jn = 0; jn < NTL; ++jn) acc[i][jn] = s2 == 0 ? t[jn] : acc[i][jn] + t[jn];
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  return true;
+  if (g.act == ACT_SILU_MUL) ring_epilogue_t<MT, NTL, 2, ACT_NONE>(acc, g, m0, n0, wrow, wcol);
+  else if (g.res) ring_epilogue_t<MT, NTL, 1, ACT_NONE>(acc, g, m0, n0, wrow, wcol);
+  else ring_epilogue_t<MT, NTL, 0, ACT_NONE>(acc, g, m0, n0, wrow, wcol);
+  ring_epilogue_done(acc);
 }
 
 MLS_DEV i32x8 w8_frag(const char* p0, const char* p1) {
@@ -271,19 +97,19 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_w8a8_kernel(const W8Args g)
 #pragma unroll
   for (int i = 0; i < A_LD; ++i) {
     a_row[i] = (i * NT + tid) / CPR;
-    a_col[i] = ((tid % CPR) ^ w8_swz(a_row[i])) * 16;
+    a_col[i] = ((tid % CPR) ^ ring_swz<ROWB>(a_row[i])) * 16;
   }
 #pragma unroll
   for (int i = 0; i < B_LD; ++i) {
     w_row[i] = (i * NT + tid) / CPR;
-    w_col[i] = ((tid % CPR) ^ w8_swz(w_row[i])) * 16;
+    w_col[i] = ((tid % CPR) ^ ring_swz<ROWB>(w_row[i])) * 16;
   }
   const int K1 = g.K;  // bytes per source row
 
   auto tile_mn = [&](int ti, int& m0, int& n0, int& k0) {
     const int u = bq + ti * G, t = S == 1 ? u : u / S;
     int tm, tn;
-    w8_tile(t, tiles_m, g.tiles_n, tm, tn);
+    ring_tile(t, tiles_m, g.tiles_n, tm, tn);
     m0 = tm * BM;
     n0 = tn * BN;
     k0 = (u - t * S) * nk;
@@ -301,10 +127,10 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_w8a8_kernel(const W8Args g)
     const int sa = m0 * K1 + kt * ROWB, sb = n0 * K1 + kt * ROWB;
 #pragma unroll
     for (int i = 0; i < A_LD; ++i)
-      w8_glds16(ra, base + i * NT * 16, m0 + a_row[i] < g.M ? a_row[i] * K1 + a_col[i] : OOB, sa);
+      ring_glds16(ra, base + i * NT * 16, m0 + a_row[i] < g.M ? a_row[i] * K1 + a_col[i] : OOB, sa);
 #pragma unroll
     for (int i = 0; i < B_LD; ++i)
-      w8_glds16(rw, base + A_BYTES + i * NT * 16, n0 + w_row[i] < g.N ? w_row[i] * K1 + w_col[i] : OOB, sb);
+      ring_glds16(rw, base + A_BYTES + i * NT * 16, n0 + w_row[i] < g.N ? w_row[i] * K1 + w_col[i] : OOB, sb);
   };
 
   f32x4 acc[MT][NTL];
@@ -315,7 +141,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_w8a8_kernel(const W8Args g)
 
   // fragment reads inside a stage image (row r, 16-B chunk c -> r*128 + (c ^ swz(r))*16)
   const int fr = lane & 15, fq = lane >> 4;
-  const int sw = w8_swz(fr);  // tile rows are 16-aligned: swz(r) depends on r & 15 only
+  const int sw = ring_swz<ROWB>(fr);  // tile rows are 16-aligned: swz(r) depends on r & 15 only
   const int a_rd = (wm * WTM + fr) * ROWB, w_rd = A_BYTES + (wn * WTN + fr) * ROWB;
   const int coff0 = (fq ^ sw) << 4, coff1 = ((4 + fq) ^ sw) << 4;
 
@@ -325,8 +151,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_w8a8_kernel(const W8Args g)
 
   int c_kt = 0, c_ti = 0, c_slot = 0;  // compute cursor
   for (int j = 0; j < nsteps; ++j) {
-    w8_wait_ring<STAGES, LOADS>(nsteps - 1 - j);  // step j landed; later ones may still fly
-    w8_barrier();  // step j visible to every wave; step j - 1 fully read by every wave
+    ring_wait<STAGES, LOADS>(nsteps - 1 - j);  // step j landed; later ones may still fly
+    ring_barrier();  // step j visible to every wave; step j - 1 fully read by every wave
     if (j + STAGES - 1 < nsteps) stage();
     const char* base = smem + c_slot * STAGE_BYTES;
     c_slot = c_slot + 1 == STAGES ? 0 : c_slot + 1;
@@ -351,7 +177,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_w8a8_kernel(const W8Args g)
     int m0, n0, k0;
     const int cu = bq + c_ti * G;
     tile_mn(c_ti++, m0, n0, k0);
-    const bool reducer = S == 1 || w8_splitk_arrive<BM * BN, MT, NTL>(acc, g, cu / S, cu - (cu / S) * S,
+    const bool reducer = S == 1 || ring_splitk_arrive<BM * BN, MT, NTL>(acc, g.ws, g.cnt, S, cu / S, cu - (cu / S) * S,
                                                                         (int*)(smem + STAGES * STAGE_BYTES));
     if (reducer) w8_epilogue<MT, NTL>(acc, g, m0, n0, wm * WTM, wn * WTN);
   }
@@ -508,13 +334,11 @@ int mls_gemm_w8a8(const void* Aq, const void* xs, const void* Wq, const void* ws
     g.splitk = have_ws && v >= 3 ? w8_split(tiles, nk, tile_elems, ws_elems, cnt_elems) : 1;
   } else {
     g.splitk = splitk;
-    if (splitk > 1 && (!have_ws || nk % splitk || tiles > cnt_elems || tiles * splitk * tile_elems > ws_elems))
-      return MLS_BAD_ARG;
+    if (splitk > 1 && !ring_splitk_ok(splitk, nk, tiles, tile_elems, ws, ws_elems, cnt, cnt_elems)) return MLS_BAD_ARG;
   }
   g.ws = (float*)ws;
   g.cnt = (int*)cnt;
-  const int units = tiles * g.splitk, cap = mls_num_cus();
-  const dim3 grid(units < cap ? units : cap), block(c.threads);
+  const dim3 grid = ring_grid(tiles * g.splitk, mls_num_cus()), block(c.threads);
   hipStream_t st = (hipStream_t)stream;
   switch (v) {
     case 1: hipLaunchKernelGGL((gemm_w8a8_kernel<256, 256, 2, 4, 2>), grid, block, 0, st, g); break;

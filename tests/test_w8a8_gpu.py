@@ -141,18 +141,45 @@ def test_split_k_is_deterministic(variant, splitk):
     wq, ws = ops.pack_w8(_rand(N, K, scale=K**-0.5))
     xq, xs = ops.quant_rows_fp8(_rand(M, K))
     ref = ops.w8a8_reference(xq, xs, ops.unpack_w8_reference(wq, N, K), ws)
-    first = ops.gemm_w8a8(xq, xs, wq, ws, N, variant=variant, splitk=splitk)
+    work = torch.zeros(4 << 20, device=DEV, dtype=torch.float32)  # its own workspace, so its own counters
+    first = ops.gemm_w8a8(xq, xs, wq, ws, N, variant=variant, splitk=splitk, workspace=work)
     assert rel_err(first, ref) < 1e-2
     for _ in range(3):
-        assert torch.equal(ops.gemm_w8a8(xq, xs, wq, ws, N, variant=variant, splitk=splitk), first)
+        assert torch.equal(ops.gemm_w8a8(xq, xs, wq, ws, N, variant=variant, splitk=splitk, workspace=work), first)
+    torch.cuda.synchronize()
+    assert int(ops.split_counters(work).abs().sum().item()) == 0  # every tile's reducer reset its counter
+
+
+@pytest.mark.parametrize("variant,K,splitk", [(5, 256, 1), (4, 512, 2)])
+def test_blocks_walk_more_than_one_unit(variant, K, splitk):
+    """270 tiles of 32 x 128 / 150 tiles of 64 x 128 in 2 K splits (300 units of 2 k-steps) on a persistent grid
+    of one block per CU: blocks walk two units, so the ring runs across a unit boundary and a unit's epilogue (or
+    its split-K arrive) overlaps the next unit's DMA.  M = 257 leaves a one-row last tile."""
+    from mlmicroservicetemplate_amd import ops
+
+    M, N = 257, 3840
+    bm, bn = ops.W8A8_CFGS[variant]
+    units = -(-M // bm) * -(-N // bn) * splitk
+    cus = torch.cuda.get_device_properties(DEV).multi_processor_count
+    if units <= cus:
+        pytest.skip(f"{units} units on {cus} CUs: no block walks two units")
+    torch.manual_seed(variant)
+    wq, ws = ops.pack_w8(_rand(N, K, scale=K**-0.5))
+    xq, xs = ops.quant_rows_fp8(_rand(M, K))
+    ref = ops.w8a8_reference(xq, xs, ops.unpack_w8_reference(wq, N, K), ws)
+    first = ops.gemm_w8a8(xq, xs, wq, ws, N, variant=variant, splitk=splitk)
+    assert first.shape == (M, N) and rel_err(first, ref) < 1e-2
+    assert torch.equal(ops.gemm_w8a8(xq, xs, wq, ws, N, variant=variant, splitk=splitk), first)
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
-@pytest.mark.parametrize("M", [4, 40])
+@pytest.mark.parametrize("M", [4, 40, 257])
 def test_epilogues(variant, M):
+    """M = 257 (with K = 256): all eight 16-row blocks of the 256-row tiles hold valid rows under every epilogue,
+    and a second, one-row tile follows."""
     from mlmicroservicetemplate_amd import ops
 
-    K, N = 512, 272
+    K, N = (256 if M == 257 else 512), 272
     torch.manual_seed(10 * variant + M)
     wq, ws = ops.pack_w8(_rand(N, K, scale=K**-0.5))
     codes = ops.unpack_w8_reference(wq, N, K)
