@@ -27,7 +27,7 @@ import os
 import re
 import zlib
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.distributed as dist
@@ -168,6 +168,62 @@ class CheckpointSource:
         return self.ck.get_region(key, rows, cols).to(device=self.device, dtype=torch.float32)
 
 
+def qkv_row_slices(cfg: LlamaConfig, tp: int, rank: int) -> Tuple[slice, slice]:
+    """Rows of the full q and of the full k / v matrices that ``rank`` holds (a KV head is replicated over
+    tp / kv_heads ranks when there are more ranks than KV heads)."""
+    sd, D = shard_dims(cfg, tp, rank), cfg.head_dim
+    kvh = (rank * cfg.kv_heads) // tp if cfg.kv_heads < tp else rank * sd.hkv
+    return slice(rank * sd.hq * D, (rank + 1) * sd.hq * D), slice(kvh * D, (kvh + sd.hkv) * D)
+
+
+LORA_TARGETS = {"q_proj": "q", "k_proj": "k", "v_proj": "v"}
+
+
+def parse_lora_config(config: dict) -> Tuple[Tuple[str, ...], int, float, bool]:
+    """``(modules, r, alpha, use_rslora)`` of a PEFT ``adapter_config.json`` dict (or the native form of
+    the same keys); ``ValueError`` for everything the q/k/v LoRA path does not serve -- nothing is dropped."""
+    targets = config.get("target_modules")
+    if isinstance(targets, str) or not targets:
+        raise ValueError(f"LoRA config: target_modules must be a list of module names, got {targets!r}")
+    mods = []
+    for t in targets:
+        name = str(t).rsplit(".", 1)[-1]
+        if name not in LORA_TARGETS and name not in LORA_TARGETS.values():
+            raise ValueError(f"LoRA target module {t!r} is not served: only q_proj, k_proj and v_proj are")
+        mods.append(LORA_TARGETS.get(name, name))
+    if config.get("modules_to_save"):
+        raise ValueError(f"LoRA config: modules_to_save {config['modules_to_save']!r} is not served")
+    if config.get("bias", "none") not in ("none", None):
+        raise ValueError(f"LoRA config: bias={config['bias']!r} is not served (bias terms)")
+    if config.get("use_dora"):
+        raise ValueError("LoRA config: DoRA (use_dora) is not served")
+    for key in ("rank_pattern", "alpha_pattern"):
+        if config.get(key):
+            raise ValueError(f"LoRA config: {key} (per-layer ranks / alphas) is not served")
+    if config.get("peft_type", "LORA") not in ("LORA", None):
+        raise ValueError(f"LoRA config: peft_type {config['peft_type']!r} is not LoRA")
+    r = config.get("r")
+    if not isinstance(r, int) or not 1 <= r <= R.LORA_MAX_RANK:
+        raise ValueError(f"LoRA config: rank r={r!r} outside 1..{R.LORA_MAX_RANK}")
+    alpha = float(config.get("lora_alpha", r))
+    return tuple(p for p in R.LORA_MODULES if p in mods), r, alpha, bool(config.get("use_rslora", False))
+
+
+def random_lora_adapter(cfg: LlamaConfig, rank: int, seed: int = 0, modules=("q", "k", "v"), alpha: float = 32.0,
+                        b_std: float = 0.02, device="cpu") -> Tuple[Dict[str, torch.Tensor], dict]:
+    """A random adapter for tests and benchmarks, ``(tensors, config)`` for :meth:`LlamaTP.load_adapter`:
+    drawn from :class:`RandomSource` under ``l{i}.{q,k,v}.lora_A/B``.  B is normal, not training's zero
+    init: a zero delta would make every test of it vacuous."""
+    src = RandomSource(seed, device)
+    out = {"q": cfg.heads * cfg.head_dim, "k": cfg.kv_heads * cfg.head_dim, "v": cfg.kv_heads * cfg.head_dim}
+    t: Dict[str, torch.Tensor] = {}
+    for i in range(cfg.layers):
+        for p in modules:
+            t[f"l{i}.{p}.lora_A"] = src.region(f"l{i}.{p}.lora_A", (rank, cfg.hidden)) * (50.0 / cfg.hidden ** 0.5)
+            t[f"l{i}.{p}.lora_B"] = src.region(f"l{i}.{p}.lora_B", (out[p], rank)) * (b_std / 0.02)
+    return t, {"r": rank, "lora_alpha": alpha, "target_modules": [f"{p}_proj" for p in modules]}
+
+
 def init_llama_shard(cfg: LlamaConfig, tp: int = 1, rank: int = 0, seed: int = 0, device="cpu",
                      dtype=torch.bfloat16, source=None) -> Dict[str, torch.Tensor]:
     """This rank's shard of a Llama: from ``source`` (:class:`CheckpointSource`) or a
@@ -175,7 +231,6 @@ def init_llama_shard(cfg: LlamaConfig, tp: int = 1, rank: int = 0, seed: int = 0
     src = source if source is not None else RandomSource(seed, device)
     sd = shard_dims(cfg, tp, rank)
     H, D = cfg.hidden, cfg.head_dim
-    kv_rep = cfg.kv_heads < tp  # more ranks than KV heads: replicate a head over tp/kv_heads ranks
     p: Dict[str, torch.Tensor] = {}
 
     def vocab_rows(name):
@@ -188,9 +243,7 @@ def init_llama_shard(cfg: LlamaConfig, tp: int = 1, rank: int = 0, seed: int = 0
     p["embed"] = vocab_rows("embed")
     p["lm_head"] = vocab_rows("lm_head")
     p["final_norm"] = src.region("final_norm", (H,), "norm").to(device=device, dtype=dtype)
-    qs = slice(rank * sd.hq * D, (rank + 1) * sd.hq * D)
-    kvh = (rank * cfg.kv_heads) // tp if kv_rep else rank * sd.hkv
-    ks = slice(kvh * D, (kvh + sd.hkv) * D)
+    qs, ks = qkv_row_slices(cfg, tp, rank)
     sl = slice(rank * sd.inter, (rank + 1) * sd.inter)
     for i in range(cfg.layers):
         q = src.region(f"l{i}.q", (cfg.heads * D, H), rows=qs)
@@ -395,6 +448,8 @@ class GenParams:
     top_k: int = 1  # 1 = greedy
     temperature: float = 1.0
     seed: int = 0
+    # LoRA adapter of the generation (LlamaTP.load_adapter's index; -1: the base model), or one per batch row
+    adapter: Union[int, Sequence[int]] = -1
 
 
 _M64 = (1 << 64) - 1
@@ -443,6 +498,7 @@ class _Forward:
     # refactor"; profiles/llama_route_keepalive_ab.jsonl)
     o: Optional[torch.Tensor] = None
     gu: Optional[torch.Tensor] = None
+    lora_sid: Optional[torch.Tensor] = None  # cache slot of each sequence for the LoRA hook (None: the batch row)
 
     def take_xn(self) -> Optional[torch.Tensor]:
         xn, self.xn = self.xn, None
@@ -456,8 +512,11 @@ class LlamaTP:
     def __init__(self, params: Dict[str, torch.Tensor], cfg: LlamaConfig, tp: int = 1, rank: int = 0,
                  comm: Optional[TPComm] = None, backend: str = "reference", device="cpu", max_batch: int = 8,
                  max_seq: int = 1024, top_k_max: int = 50, kv_pages: int = 0, kv_dtype: str = "bf16",
-                 weight_dtype: str = "bf16", kv_prefill: str = "rows"):
-        """``kv_pages > 0``: paged KV cache -- per layer a pool of ``kv_pages`` pages of 64 rows
+                 weight_dtype: str = "bf16", kv_prefill: str = "rows", lora: Optional[dict] = None):
+        """``lora={"max_adapters": n, "max_rank": r}``: room for n LoRA adapters of rank <= r on the q / k / v
+        projections, chosen per cache slot (:meth:`load_adapter`, :meth:`set_slot_adapter`,
+        ``GenParams.adapter``); until one is loaded neither backend computes anything new.
+        ``kv_pages > 0``: paged KV cache -- per layer a pool of ``kv_pages`` pages of 64 rows
         shared by all sequences (:class:`~.kv_pages.PageTable`), instead of ``max_batch x max_seq``.
         ``kv_dtype="fp8"``: e4m3 KV rows with one fp32 scale per (row, KV head)
         (``ops.reference.kv_quant_fp8``) -- 132 instead of 256 bytes per head row.  Fused backend: uint8
@@ -520,6 +579,20 @@ class LlamaTP:
         self.top_k_max = top_k_max
         D = cfg.head_dim
         self.p = {k: v.to(self.device) for k, v in params.items()}
+        # LoRA: adapter of every cache slot (-1: base), read in place by the captured steps
+        self.lora_slot = torch.full((max_batch,), -1, dtype=torch.int32, device=self.device)
+        self.lora_cfg = None if lora is None else {"max_adapters": int(lora.get("max_adapters", 8)),
+                                                   "max_rank": int(lora.get("max_rank", 16))}
+        self.lora_loaded: set = set()  # adapter indices in use
+        self.lora_pack = None  # fused: ops.LoraPack
+        self._lora_ref: List[Dict[int, dict]] = [dict() for _ in range(cfg.layers)]  # reference: layer -> index -> modules
+        self._attn_gain: List[torch.Tensor] = []
+        if self.lora_cfg is not None:
+            if not 1 <= self.lora_cfg["max_rank"] <= R.LORA_MAX_RANK or self.lora_cfg["max_adapters"] < 1:
+                raise ValueError(f"lora: max_rank must be in 1..{R.LORA_MAX_RANK} and max_adapters positive, "
+                                 f"got {self.lora_cfg}")
+            # the gains as given: both backends fold or overwrite them below
+            self._attn_gain = [self.p[f"l{i}.attn_norm"].float().clone() for i in range(cfg.layers)]
         # int4: name -> (packed codes, scales) of the layer projections (fused backend only)
         self.w4: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
         self.w4_max_rows = self.w4_variant = 0
@@ -558,6 +631,13 @@ class LlamaTP:
             self.dec_ws = torch.empty(max_batch * self.sd.hq * (-(-max_seq // 64)) * (D + 2) + 16,
                                       device=self.device, dtype=torch.float32)
             self.dec_cnt = torch.zeros(max_batch * self.sd.hkv, device=self.device, dtype=torch.int32)
+            if self.lora_cfg is not None:
+                self.lora_pack = ops.pack_lora(cfg.layers, cfg.hidden, tuple(h * D for h in (self.sd.hq, self.sd.hkv,
+                                                                                             self.sd.hkv)),
+                                               self.lora_cfg["max_adapters"], self.lora_cfg["max_rank"], self.device)
+                # split-K slabs of every step up to 4096 rows (more rows run one split from a buffer of their own)
+                self.lora_ws = torch.empty(self.lora_pack.workspace_elems(4096, 1), device=self.device,
+                                           dtype=torch.float32)
             self.ver_ws: Optional[torch.Tensor] = None  # split-KV partials of the uncaptured verify steps
             self._ver_ws_graph: Optional[torch.Tensor] = None  # ... of the verify graph being warmed up / captured
         self._alloc_kv_cache(kv_pages)
@@ -804,6 +884,9 @@ class LlamaTP:
         else:
             xn = R.layernorm(x, p[f"l{i}.attn_norm"], None, eps=cfg.eps, rms=True)[0]
             qkv = xn @ p[f"l{i}.qkv"].float().T
+        if self.lora_loaded:
+            qkv = R.lora_qkv(qkv, x, self._attn_gain[i], self._lora_ref[i], self.lora_slot, B, S,
+                             (sd.hq * D, sd.hkv * D, sd.hkv * D), slot_ids=slots_b, eps=cfg.eps)
         T = qkv.shape[0]
         # chunked prefill: a padding row's position may lie past the RoPE table (it is never stored)
         rpos = positions if past is None else positions.clamp(max=self.max_seq - 1)
@@ -891,7 +974,8 @@ class LlamaTP:
             have_fp8=bool(self.fp8), o_packed="l0.o" in self.packed, o_fp8="l0.o" in self.fp8, kv_fp8=self.kv_fp8,
             w4_max_rows=self.w4_max_rows, pk_fold=self.pk_fold, prefill_fold=self.prefill_fold,
             fuse_combine=self.fuse_combine, fuse_add_norm=self.fuse_add_norm, ar_fuse=self.ar_fuse,
-            tp_overlap=self.tp_overlap, verify_attn=self.verify_attn, spec_max_tokens=self.spec_max_tokens,
+            tp_overlap=self.tp_overlap and not self.lora_loaded, verify_attn=self.verify_attn,
+            spec_max_tokens=self.spec_max_tokens,
             dec_chunk=self.dec_chunk, ar_fusable=car is not None and car.fusable(B * S * cfg.hidden),
             capturing=self.tp > 1 and self.device.type == "cuda" and torch.cuda.is_current_stream_capturing())
 
@@ -1162,12 +1246,16 @@ class LlamaTP:
         if past is not None:  # a padding row's position may lie past the RoPE table (its slot is -1 already)
             pos = pos.clamp(max=self.max_seq - 1)
         st = _Forward(rt, B, S, decode, pos, lens, past, slots, r=self._embed(ids.reshape(-1)))
+        if self.lora_loaded and slot_ids is not None and not decode:
+            st.lora_sid = slot_ids.to(torch.int32)
         if rt.overlap:
             st.r, st.delta = self._prefill_overlapped(rt, st.r, pos, lens, B, S, slots)
         else:
             st.attn_kw = self._attention_kw(rt, B, S, decode, pos, sid, past, all_rows, max_ctx)
             for i in range(cfg.layers):
                 qkv, st.r = self._norm_proj(rt.proj, st.r, f"l{i}.qkv", st.delta, xn=st.take_xn())
+                if self.lora_loaded:
+                    self._lora_fused(i, qkv, st)
                 a, parts = self._fused_attention(i, qkv, st)
                 self._layer_tail(i, st, a, parts)
         r, delta = st.r, st.delta
@@ -1235,6 +1323,89 @@ class LlamaTP:
         if any(x.data_ptr() != y.data_ptr() for x, y in zip(res, (r[:half * S], r[half * S:]))):
             r = torch.cat(res)  # _norm_proj handed back new residual tensors instead of the views
         return r, torch.cat(dlt)
+
+    # ---------------------------------------------------------------- LoRA adapters (q / k / v)
+    def _lora_fused(self, i: int, qkv: torch.Tensor, st: "_Forward") -> None:
+        """``qkv += s B (A . RMSNorm(st.r))`` in place for the rows whose slot names an adapter
+        (``ops.lora_qkv_``: two launches, device arrays only)."""
+        ops, pack, rows = self.ops, self.lora_pack, st.B * st.S
+        nsplit = ops.lora_split(st.B, st.S, self.cfg.hidden, pack.rcap)
+        ws = self.lora_ws
+        if pack.workspace_elems(rows, nsplit) > ws.numel():
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"LoRA: a captured step of {rows} rows exceeds the model's split-K workspace")
+            ws = torch.empty(pack.workspace_elems(rows, nsplit), device=self.device, dtype=torch.float32)
+        ops.lora_qkv_(qkv, st.r, pack, i, self.lora_slot, st.B, st.S, st.lora_sid, eps=self.cfg.eps, workspace=ws,
+                      nsplit=nsplit)
+
+    def load_adapter(self, index: int, tensors: Dict[str, torch.Tensor], config: dict) -> None:
+        """Load LoRA adapter ``index`` in place (fixed addresses: steps captured with an adapter loaded stay
+        valid; the first load drops the steps captured before it, which hold no LoRA launches).  ``tensors``:
+        the unsharded ``l{i}.{q,k,v}.lora_A [r, hidden]`` / ``.lora_B [out, r]`` of every layer; ``config``:
+        PEFT's keys (``r``, ``lora_alpha``, ``use_rslora``, ``target_modules``).  Each rank keeps A whole and
+        the rows of B that it holds of the base matrices.  ``ValueError`` for whatever is not served
+        (:func:`parse_lora_config`), a bad index, shapes that disagree with the config."""
+        if self.lora_cfg is None:
+            raise ValueError("this model was built without lora=...: no room for adapters")
+        if not isinstance(index, int) or not 0 <= index < self.lora_cfg["max_adapters"]:
+            raise ValueError(f"adapter index {index!r} outside [0, {self.lora_cfg['max_adapters']}): more adapters "
+                             f"than max_adapters")
+        mods, r, alpha, rslora = parse_lora_config(config)
+        if r > self.lora_cfg["max_rank"]:
+            raise ValueError(f"adapter rank {r} exceeds the model's lora max_rank {self.lora_cfg['max_rank']}")
+        cfg, D = self.cfg, self.cfg.head_dim
+        qs, ks = qkv_row_slices(cfg, self.tp, self.rank)
+        full = {"q": cfg.heads * D, "k": cfg.kv_heads * D, "v": cfg.kv_heads * D}
+        local: Dict[str, torch.Tensor] = {}
+        for i in range(cfg.layers):
+            for p in mods:
+                try:
+                    A, Bm = tensors[f"l{i}.{p}.lora_A"], tensors[f"l{i}.{p}.lora_B"]
+                except KeyError as e:
+                    raise ValueError(f"adapter has no tensor {e.args[0]!r} (target module {p}_proj)") from None
+                if tuple(A.shape) != (r, cfg.hidden) or tuple(Bm.shape) != (full[p], r):
+                    raise ValueError(f"l{i}.{p}: lora_A {tuple(A.shape)} / lora_B {tuple(Bm.shape)} do not match the "
+                                     f"config: expected ({r}, {cfg.hidden}) / ({full[p]}, {r})")
+                local[f"l{i}.{p}.lora_A"] = A
+                local[f"l{i}.{p}.lora_B"] = Bm[qs if p == "q" else ks]
+        extra = [k for k in tensors if k not in local]
+        if extra:
+            raise ValueError(f"adapter tensors outside the config's target modules: {sorted(extra)[:4]}")
+        scales = {p: R.lora_scale(alpha, r, rslora) for p in mods}
+        if self.backend == "fused":
+            self.lora_pack.load(index, local, scales, gains=self._attn_gain)
+        else:
+            for i in range(cfg.layers):
+                self._lora_ref[i][index] = {p: (local[f"l{i}.{p}.lora_A"].to(self.device, torch.float32),
+                                                local[f"l{i}.{p}.lora_B"].to(self.device, torch.float32), scales[p])
+                                            for p in mods}
+        if not self.lora_loaded:
+            # steps captured so far hold no LoRA launches (nothing new runs while no adapter is loaded): drop
+            # them, the next step captures again with the hook in.  Later loads rewrite fixed addresses only.
+            self._graphs.clear()
+            self._ver_graphs.clear()
+            self._dev_graphs.clear()
+        self.lora_loaded.add(index)
+
+    def set_slot_adapter(self, slot: int, index: int) -> None:
+        """Cache slot ``slot`` serves adapter ``index`` (-1: the base model) from the next step on."""
+        if not isinstance(slot, int) or not 0 <= slot < self.max_batch:
+            raise ValueError(f"slot {slot!r} outside [0, {self.max_batch})")
+        if not isinstance(index, int) or (index != -1 and index not in self.lora_loaded):
+            raise ValueError(f"adapter {index!r} is not loaded (loaded: {sorted(self.lora_loaded)}; -1 = base)")
+        self.lora_slot[slot] = index
+
+    def set_batch_adapters(self, B: int, adapter: Union[int, Sequence[int]]) -> None:
+        """Slots 0 .. B - 1 (the rows of a ``generate`` batch) take ``adapter``: one index, or one per row."""
+        idx = [int(adapter)] * B if isinstance(adapter, int) else [int(a) for a in adapter]
+        if len(idx) != B:
+            raise ValueError(f"{len(idx)} adapter indices for a batch of {B}")
+        if B > self.max_batch:
+            raise ValueError("batch exceeds the KV cache")
+        for a in idx:
+            if a != -1 and a not in self.lora_loaded:
+                raise ValueError(f"adapter {a!r} is not loaded (loaded: {sorted(self.lora_loaded)}; -1 = base)")
+        self.lora_slot[:B] = torch.tensor(idx, dtype=torch.int32).to(self.device)
 
     # ---------------------------------------------------------------- public
     def check_prefill_chunk(self) -> None:
@@ -1605,6 +1776,8 @@ class LlamaTP:
             self.check_spec_device(speculate, drafter, k=max(1, min(gp.top_k, self.top_k_max)), Bv=B)
         if B > self.max_batch or S + gp.max_new_tokens > self.max_seq:
             raise ValueError("batch / sequence exceed the KV cache")
+        if self.lora_loaded or gp.adapter != -1:
+            self.set_batch_adapters(B, gp.adapter)
         lens_host = lens.detach().to("cpu")
         if lens_host.numel() != B or int(lens_host.min()) < 1 or int(lens_host.max()) > S:
             raise ValueError(f"lens must be in [1, {S}] for each of the {B} sequences")

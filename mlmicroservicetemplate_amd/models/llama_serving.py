@@ -173,12 +173,16 @@ class ContinuousLlama:
             from .prefix_cache import PrefixCache
 
             model.check_prefix_cache()  # ValueError: no paged KV, fp8 KV cache, row-major cache, head_dim != 128
+            if getattr(model, "lora_cfg", None) is not None:
+                raise ValueError("prefix_cache is not available with LoRA adapters: cached pages hold adapter-specific "
+                                 "K / V, and the prefix index is not keyed by adapter")
             self.prefix = PrefixCache(model.pages)
             model.ctx_split = True  # a suffix against a long cached prefix may run split-KV (LlamaTP.ctx_splits)
         self.pstats = {"prefix_queries": 0, "prefix_hits": 0, "prefix_hit_tokens": 0}
         self.drafter = drafter
         self.spec = {"spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0}
         self.m = model
+        self._lora = getattr(model, "lora_loaded", frozenset())  # LlamaTP's set of loaded adapter indices (live)
         self.B = model.max_batch
         self.max_queue = max_queue
         self.broadcast = broadcast  # TP (legacy hook): rank 0 publishes each iteration's admissions
@@ -236,7 +240,10 @@ class ContinuousLlama:
             raise ValueError("prompt + max_new_tokens exceeds the whole KV page pool")
         # the temperature every rank samples with: the followers receive it in 1/1000 units
         # (plugins/llm.py _broadcast_iter), so rank 0 uses the same quantised value
-        gp = GenParams(gp.max_new_tokens, gp.top_k, round(float(gp.temperature) * 1000) / 1000.0, gp.seed)
+        adapter = gp.adapter
+        if not isinstance(adapter, int) or (adapter != -1 and adapter not in self._lora):
+            raise ValueError(f"adapter {adapter!r} is not loaded (-1 = the base model)")
+        gp = GenParams(gp.max_new_tokens, gp.top_k, round(float(gp.temperature) * 1000) / 1000.0, gp.seed, adapter)
         fut: cf.Future = cf.Future()
         with self._wake:
             if self._stop:
@@ -454,6 +461,11 @@ class ContinuousLlama:
                     if s.future is not None and not s.future.done():
                         s.future.set_exception(e)
                     self.slots[i] = None
+                    if self._lora and s.gp.adapter != -1:  # as _retire does: an idle slot streams no adapter
+                        try:
+                            self.m.set_slot_adapter(i, -1)
+                        except Exception:  # the device itself failed: _admit sets the slot before its next use
+                            logger.exception("could not reset the adapter of slot %d", i)
                     if self.m.pages is not None:
                         self.m.pages.release(i)
             if self.prefix is not None:  # rows a failed step may have left half-written are never served
@@ -828,6 +840,8 @@ class ContinuousLlama:
         for seq in admit:
             self.slots[seq.slot] = seq
             seq.done = seq.hit = 0
+            if self._lora:  # the slot's rows take the request's adapter from this iteration's forwards on
+                self.m.set_slot_adapter(seq.slot, int(seq.gp.adapter))
             if self.prefix is not None:
                 hit = self.prefix.match(seq.ids, stamp=self.iterations)
                 pages.adopt(seq.slot, hit)
@@ -904,6 +918,8 @@ class ContinuousLlama:
             if len(s.out) >= s.gp.max_new_tokens or (s.out and s.out[-1] in self.eos):
                 self.slots[i] = None
                 done.append(s)
+                if self._lora and s.gp.adapter != -1:
+                    self.m.set_slot_adapter(i, -1)
                 if self.m.pages is not None:
                     self.m.pages.release(i)
         return done

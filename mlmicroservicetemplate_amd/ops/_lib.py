@@ -124,6 +124,9 @@ _SIGS = {
     "mls_gemm_w8a8": [P, P, P, P, P, P, P, I, I, I, I, I, I, P, _c.c_longlong, P, I, P],
     "mls_gemm_w8a8_num_variants": [],
     "mls_quant_rows_fp8": [P, P, P, P, P, I, I, I, F, P],
+    "mls_lora_split": [I, I, I, I],
+    "mls_lora_shrink": [P, I, P, P, P, P, P, SZ, I, I, I, I, I, I, I, P],
+    "mls_lora_expand": [P, I, P, P, P, P, P, P, SZ, I, I, I, F, I, I, I, I, I, I, I, I, P],
     "mls_stream_create_cumask": [P, I, _c.POINTER(P)],
     "mls_stream_get_cumask": [P, P, I],
     "mls_stream_destroy": [P],
@@ -158,7 +161,7 @@ def _bind(lib: ctypes.CDLL) -> None:
 
 DEBUG = os.environ.get("MLS_DEBUG", "0") == "1"
 DEBUG_TUS = ("attention", "norm_ops", "stem_pool", "conv3x3_halo", "kv_fp8", "flash_ctx", "decode_verify",
-             "decode_pick", "spec_step")  # translation units with MLS_CHECK bounds
+             "decode_pick", "spec_step", "lora")  # translation units with MLS_CHECK bounds
 DEBUG_CODES = {
     101: "rope/KV append: cache slot beyond the cache",
     102: "rope/KV append: position beyond the RoPE table",
@@ -180,6 +183,9 @@ DEBUG_CODES = {
     414: "spec accept: rows[r] is not a serving slot",
     415: "spec accept: n[r] outside [0, T]",
     416: "spec accept: winning candidate index outside [0, tp * k) (a fed row of NaN candidates)",
+    501: "lora: a sequence's cache slot lies outside lora_slot",
+    502: "lora: lora_slot names an adapter outside [-1, max_adapters)",
+    503: "lora: an adapter's rank table does not fit the pack (not written by LoraPack.load)",
 }
 
 

@@ -211,3 +211,37 @@ def w8a8_linear(h: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, rstd: Optio
 
 def gelu(x):
     return F.gelu(x)
+
+
+# ------------------------------------------------------------------ LoRA on the q/k/v projection
+LORA_MODULES = ("q", "k", "v")
+LORA_MAX_RANK = 64
+
+
+def lora_scale(alpha: float, rank: int, use_rslora: bool = False) -> float:
+    """``alpha / r``, or ``alpha / sqrt(r)`` with rank-stabilised LoRA."""
+    return float(alpha) / (float(rank) ** 0.5 if use_rslora else float(rank))
+
+
+def lora_qkv(qkv: torch.Tensor, x: torch.Tensor, gain: torch.Tensor, adapters, lora_slot, B: int, S: int, widths,
+             slot_ids=None, eps: float = 1e-5) -> torch.Tensor:
+    """The per-request LoRA rule on the fused projection, in fp32.  Row m of sequence b (``qkv``, ``x``
+    ``[B*S, .]``) lives in cache slot ``slot_ids[b]`` (default b) and takes adapter ``a = lora_slot[slot]``:
+    ``a = -1`` leaves the row as it is, ``a >= 0`` adds ``s_p * B_p (A_p . xn[m])`` to segment p of ``widths
+    = (Nq, Nk, Nv)`` for every module the adapter has, ``xn = RMSNorm(x[m]) * gain``.  ``adapters[a]``:
+    ``{p: (A_p [r, hidden], B_p [N_p, r], s_p)}`` for a subset of ``"q", "k", "v"``.  Returns a new tensor."""
+    out = qkv.float().clone()
+    xf = x.float()
+    xn = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * gain.float().view(1, -1)
+    starts = (0, widths[0], widths[0] + widths[1])
+    for b in range(B):
+        slot = b if slot_ids is None else int(slot_ids[b])
+        a = int(lora_slot[slot])
+        if a < 0:
+            continue
+        rows = slice(b * S, (b + 1) * S)
+        for p, (A, Bm, s) in adapters[a].items():
+            j = LORA_MODULES.index(p)
+            t = xn[rows] @ A.float().T
+            out[rows, starts[j]: starts[j] + widths[j]] += float(s) * (t @ Bm.float().T)
+    return out

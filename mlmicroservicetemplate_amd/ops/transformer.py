@@ -834,3 +834,177 @@ def spec_accept(cand_v: torch.Tensor, cand_i: torch.Tensor, ids: torch.Tensor, n
                                lens.data_ptr(), step.data_ptr(), hist.data_ptr(), hist.shape[1],
                                _ptr(eos) if n_eos else None, n_eos, readback.data_ptr(), stream_ptr(dev))
     check(rc, "mls_spec_accept")
+
+
+# ------------------------------------------------------------------ LoRA on the q/k/v projection
+LORA_GRAN = 16      # ranks are padded to this many rows of A' (one MFMA column tile of t)
+LORA_MAX_RANK = 64
+LORA_K_GRAN = 128   # hidden must be a multiple (4 waves x one k-step of 32 per split)
+_LORA_MODULES = ("q", "k", "v")
+
+
+class LoraPack:
+    """The adapters of one model as the LoRA kernels read them: fixed-address device arrays sized for
+    ``max_adapters x max_rank`` at construction, so a captured graph stays valid across :meth:`load`.
+
+    ``A [layers][max_adapters][rcap][hidden]`` bf16: ``A' = bf16(A diag(gain))``, the q, k, v ranks padded
+    to ``LORA_GRAN`` with zero rows and laid end to end (``rcap = 3 * padded max_rank``);
+    ``B [layers][max_adapters][Nq + Nk + Nv][rb]`` bf16, each row's rank zero-padded to ``rb`` (32 or 64);
+    ``seg [max_adapters][4]`` int32 the padded ranks (0: module absent, all 0: slot empty) and
+    ``scale [max_adapters][4]`` fp32 the ``s_p``, shared by every layer."""
+
+    def __init__(self, layers: int, hidden: int, widths, max_adapters: int, max_rank: int, device):
+        widths = tuple(int(w) for w in widths)
+        if not 1 <= int(max_rank) <= LORA_MAX_RANK:
+            raise ValueError(f"max_rank must be in 1..{LORA_MAX_RANK}, got {max_rank}")
+        if int(max_adapters) < 1:
+            raise ValueError(f"max_adapters must be positive, got {max_adapters}")
+        if hidden % LORA_K_GRAN:
+            raise ValueError(f"hidden {hidden} is not a multiple of the LoRA kernels' K granule {LORA_K_GRAN}")
+        if len(widths) != 3 or any(w < 0 or w % 16 for w in widths) or sum(widths) == 0:
+            raise ValueError(f"segment widths (Nq, Nk, Nv) must be multiples of 16, got {widths}")
+        self.layers, self.hidden, self.widths = int(layers), int(hidden), widths
+        self.max_adapters, self.max_rank = int(max_adapters), int(max_rank)
+        rpad = -(-self.max_rank // LORA_GRAN) * LORA_GRAN
+        self.rcap, self.rb = 3 * rpad, 32 if rpad <= 32 else 64
+        self.device = torch.device(device)
+        dev, n = self.device, self.max_adapters
+        self.A = torch.zeros(self.layers, n, self.rcap, self.hidden, device=dev, dtype=torch.bfloat16)
+        self.B = torch.zeros(self.layers, n, sum(widths), self.rb, device=dev, dtype=torch.bfloat16)
+        self.seg = torch.zeros(n, 4, device=dev, dtype=torch.int32)
+        self.scale = torch.zeros(n, 4, device=dev, dtype=torch.float32)
+        self.loaded = [False] * n
+
+    def workspace_elems(self, rows: int, nsplit: int) -> int:
+        return int(nsplit) * int(rows) * (self.rcap + 1)
+
+    def load(self, index: int, tensors, scales, gains=None) -> None:
+        """Write adapter ``index`` in place.  ``tensors``: ``l{i}.{q,k,v}.lora_A`` ``[r, hidden]`` and
+        ``.lora_B`` ``[N_p, r]`` (this rank's rows) for every layer and every module of ``scales = {p: s_p}``;
+        ``gains``: per layer the RMSNorm gain ``[hidden]`` folded into A (None: ones)."""
+        if not 0 <= int(index) < self.max_adapters:
+            raise ValueError(f"adapter index {index} outside [0, {self.max_adapters})")
+        mods = [p for p in _LORA_MODULES if p in scales]
+        if not mods or len(mods) != len(scales):
+            raise ValueError(f"LoRA modules must be a non-empty subset of {_LORA_MODULES}, got {sorted(scales)}")
+        ranks = {}
+        for p in mods:
+            j = _LORA_MODULES.index(p)
+            for i in range(self.layers):
+                A, Bm = tensors[f"l{i}.{p}.lora_A"], tensors[f"l{i}.{p}.lora_B"]
+                r = A.shape[0]
+                if not 1 <= r <= self.max_rank:
+                    raise ValueError(f"l{i}.{p}: rank {r} outside 1..{self.max_rank} (the pack's max_rank)")
+                if ranks.setdefault(p, r) != r:
+                    raise ValueError(f"l{i}.{p}: rank {r} differs from layer 0's {ranks[p]} (per-layer ranks)")
+                if tuple(A.shape) != (r, self.hidden) or tuple(Bm.shape) != (self.widths[j], r):
+                    raise ValueError(f"l{i}.{p}: lora_A {tuple(A.shape)} / lora_B {tuple(Bm.shape)}; expected "
+                                     f"({r}, {self.hidden}) / ({self.widths[j]}, {r})")
+        pad = {p: -(-ranks[p] // LORA_GRAN) * LORA_GRAN for p in mods}
+        self.seg[index].zero_()  # the slot serves as base while its rows change
+        self.A[:, index].zero_()
+        self.B[:, index].zero_()
+        off, col = 0, 0
+        for j, p in enumerate(_LORA_MODULES):
+            if p in pad:
+                for i in range(self.layers):
+                    A = tensors[f"l{i}.{p}.lora_A"].to(self.device, torch.float32)
+                    if gains is not None:
+                        A = A * gains[i].to(self.device, torch.float32).view(1, -1)
+                    self.A[i, index, off: off + ranks[p]] = A.to(torch.bfloat16)
+                    self.B[i, index, col: col + self.widths[j], : ranks[p]] = tensors[f"l{i}.{p}.lora_B"].to(
+                        self.device, torch.bfloat16)
+                off += pad[p]
+            col += self.widths[j]
+        self.scale[index] = torch.tensor([float(scales.get(p, 0.0)) for p in _LORA_MODULES] + [0.0],
+                                         dtype=torch.float32)
+        self.seg[index] = torch.tensor([pad.get(p, 0) for p in _LORA_MODULES] + [0], dtype=torch.int32)
+        self.loaded[index] = True
+
+
+def pack_lora(layers: int, hidden: int, widths, max_adapters: int, max_rank: int, device) -> LoraPack:
+    """An empty :class:`LoraPack`; adapters go in with :meth:`LoraPack.load`."""
+    return LoraPack(layers, hidden, widths, max_adapters, max_rank, device)
+
+
+def lora_split(B: int, S: int, K: int, rcap: int) -> int:
+    """The K slices ``lora_qkv_`` runs the shrink with (host values only: safe under graph capture)."""
+    return int(lib().mls_lora_split(int(B), int(S), int(K), int(rcap)))
+
+
+def _lora_args(pack: LoraPack, layer: int, lora_slot: torch.Tensor, B: int, S: int, slot_ids, workspace, nsplit: int,
+               dev) -> int:
+    """The checks the two launches share; returns the split count."""
+    _need(lora_slot, "lora_slot", torch.int32, dev)
+    if slot_ids is not None:
+        _need(slot_ids, "slot_ids", torch.int32, dev)
+        if slot_ids.numel() != B:
+            raise ValueError(f"slot_ids has {slot_ids.numel()} entries for {B} sequences")
+    elif B > lora_slot.numel():
+        raise ValueError(f"{B} sequences but lora_slot has {lora_slot.numel()} slots")
+    if pack.A.device != dev:  # the arrays' device: "cuda" given at construction is cuda:0 here
+        raise ValueError(f"pack lives on {pack.A.device}, the rows on {dev}")
+    if not 0 <= int(layer) < pack.layers:
+        raise ValueError(f"layer {layer} outside the pack's {pack.layers}")
+    nsplit = int(nsplit) or lora_split(B, S, pack.hidden, pack.rcap)
+    if nsplit < 1 or nsplit > 64 or pack.hidden % (nsplit * LORA_K_GRAN):
+        raise ValueError(f"nsplit {nsplit}: hidden {pack.hidden} must be a multiple of nsplit * {LORA_K_GRAN}")
+    _need(workspace, "workspace", torch.float32, dev)
+    if workspace.numel() < pack.workspace_elems(B * S, nsplit):
+        raise ValueError(f"workspace holds {workspace.numel()} floats, {nsplit} splits of {B * S} rows need "
+                         f"{pack.workspace_elems(B * S, nsplit)}")
+    return nsplit
+
+
+def lora_shrink(resid: torch.Tensor, pack: LoraPack, layer: int, lora_slot: torch.Tensor, B: int, S: int,
+                slot_ids: Optional[torch.Tensor] = None, *, workspace: torch.Tensor, nsplit: int = 0) -> int:
+    """``mls_lora_shrink``: the split-K partials of ``t = resid . A'[a]^T`` and of each row's square sum into
+    ``workspace`` (fp32 slabs ``[nsplit][B * S][pack.rcap + 1]``) for the rows whose sequence names an adapter.
+    Returns the split count used (``nsplit = 0``: :func:`lora_split`)."""
+    dev = resid.device
+    _need(resid, "resid", torch.bfloat16, dev)
+    if resid.dim() != 2 or tuple(resid.shape) != (B * S, pack.hidden):
+        raise ValueError(f"resid is {tuple(resid.shape)}, expected ({B * S}, {pack.hidden})")
+    nsplit = _lora_args(pack, layer, lora_slot, B, S, slot_ids, workspace, nsplit, dev)
+    rc = lib().mls_lora_shrink(resid.data_ptr(), pack.hidden, pack.A[layer].data_ptr(), pack.seg.data_ptr(),
+                               lora_slot.data_ptr(), _ptr(slot_ids), workspace.data_ptr(), workspace.numel() * 4, B, S,
+                               pack.hidden, pack.rcap, pack.max_adapters, lora_slot.numel(), nsplit, stream_ptr(dev))
+    check(rc, "mls_lora_shrink")
+    return nsplit
+
+
+def lora_expand_(qkv: torch.Tensor, pack: LoraPack, layer: int, lora_slot: torch.Tensor, B: int, S: int,
+                 slot_ids: Optional[torch.Tensor] = None, *, eps: float = 1e-5, workspace: torch.Tensor,
+                 nsplit: int = 0) -> torch.Tensor:
+    """``mls_lora_expand``: ``qkv[m, seg_p] += s_p * rstd[m] * (t[m] . B_p[a]^T)`` in place from the slabs
+    :func:`lora_shrink` wrote with the same arguments."""
+    dev = qkv.device
+    _need(qkv, "qkv", torch.bfloat16, dev)
+    N = sum(pack.widths)
+    if qkv.dim() != 2 or tuple(qkv.shape) != (B * S, N):
+        raise ValueError(f"qkv is {tuple(qkv.shape)}; the pack's segment widths {pack.widths} need ({B * S}, {N})")
+    nsplit = _lora_args(pack, layer, lora_slot, B, S, slot_ids, workspace, nsplit, dev)
+    rc = lib().mls_lora_expand(qkv.data_ptr(), N, pack.B[layer].data_ptr(), pack.seg.data_ptr(),
+                               pack.scale.data_ptr(), lora_slot.data_ptr(), _ptr(slot_ids), workspace.data_ptr(),
+                               workspace.numel() * 4, B, S, pack.hidden, float(eps), *pack.widths, pack.rcap, pack.rb,
+                               pack.max_adapters, lora_slot.numel(), nsplit, stream_ptr(dev))
+    check(rc, "mls_lora_expand")
+    return qkv
+
+
+def lora_qkv_(qkv: torch.Tensor, resid: torch.Tensor, pack: LoraPack, layer: int, lora_slot: torch.Tensor, B: int,
+              S: int, slot_ids: Optional[torch.Tensor] = None, *, eps: float = 1e-5,
+              workspace: Optional[torch.Tensor] = None, nsplit: int = 0) -> torch.Tensor:
+    """``qkv[m, seg_p] += s_p * B_p (A_p . RMSNorm(resid[m]) * gain)`` in place for the adapter of row m's
+    sequence (``lora_slot[slot_ids[b] or b]``, -1: the row is left alone), layer ``layer`` of ``pack``:
+    :func:`lora_shrink` then :func:`lora_expand_`, two launches.  ``workspace``: fp32,
+    ``pack.workspace_elems(B * S, nsplit)`` elements (None: allocated here); ``nsplit = 0``: :func:`lora_split`."""
+    N = sum(pack.widths)
+    if qkv.dim() != 2 or tuple(qkv.shape) != (B * S, N):  # before anything is launched
+        raise ValueError(f"qkv is {tuple(qkv.shape)}; the pack's segment widths {pack.widths} need ({B * S}, {N})")
+    _need(qkv, "qkv", torch.bfloat16, qkv.device)
+    if workspace is None:
+        ns = int(nsplit) or lora_split(B, S, pack.hidden, pack.rcap)
+        workspace = torch.empty(pack.workspace_elems(B * S, max(ns, 1)), device=qkv.device, dtype=torch.float32)
+    nsplit = lora_shrink(resid, pack, layer, lora_slot, B, S, slot_ids, workspace=workspace, nsplit=nsplit)
+    return lora_expand_(qkv, pack, layer, lora_slot, B, S, slot_ids, eps=eps, workspace=workspace, nsplit=nsplit)

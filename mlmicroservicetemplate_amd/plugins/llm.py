@@ -40,6 +40,7 @@ class LlamaPlugin(ModelPlugin):
         self.speculate, self.speculate_ngram = 0, 3
         self.speculate_device = False
         self.prefix_cache = False
+        self.adapters: Dict[str, int] = {}  # MODEL_CONFIG lora: adapter name -> index
         self.kv_pages = 0
         self._lock = threading.Lock()
 
@@ -53,6 +54,7 @@ class LlamaPlugin(ModelPlugin):
         self.speculate, self.speculate_ngram = self.parse_speculate(extra)
         self.speculate_device = self.parse_speculate_device(extra, self.speculate)
         self.prefix_cache = self.parse_prefix_cache(extra)
+        lora_paths, lora_kw = self.parse_lora(extra, self.prefix_cache)
         size = extra.get("config", "8b")
         cfg = llama.LLAMA3_8B if size == "8b" else llama.tiny_config(**extra.get("overrides", {}))
         tp = ctx.world_size if int(s.TP) > 1 else 1
@@ -83,7 +85,13 @@ class LlamaPlugin(ModelPlugin):
             kv_pages = int(-mdist.max_over_ranks(-float(kv_pages)))
         self.model = llama.LlamaTP(params, cfg, tp=tp, rank=ctx.rank, comm=llama.TPComm(None, tp, device=dev), backend=backend,
                                    device=dev, max_batch=max_batch, max_seq=max_seq, kv_pages=kv_pages,
-                                   kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_prefill=kv_prefill)
+                                   kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_prefill=kv_prefill, lora=lora_kw)
+        for index, (name, path) in enumerate(lora_paths.items()):  # every rank reads the adapter and keeps its B rows
+            from ..utils.checkpoint import load_lora_adapter
+
+            tensors, acfg = load_lora_adapter(path, cfg.layers)
+            self.model.load_adapter(index, tensors, acfg)
+            self.adapters[name] = index
         if self.speculate:  # refused at start-up on the lockstep path too (the engine below checks for itself)
             self.model.check_speculate(self.speculate)
         if self.speculate_device:  # no device loop (reference backend, CPU, graphs off ...): refused, nothing falls back
@@ -119,6 +127,21 @@ class LlamaPlugin(ModelPlugin):
         if wd not in ("bf16", "int4", "w8a8"):
             raise ValueError(f"weight_dtype must be 'bf16', 'int4' or 'w8a8', got {wd!r}")
         return wd
+
+    @staticmethod
+    def parse_lora(extra: dict, prefix_cache: bool = False):
+        """MODEL_CONFIG ``lora: {name: PEFT directory, ...}`` (+ optional ``lora_max_rank``, default 64):
+        ``(paths, LlamaTP's lora=...)``, ``({}, None)`` without adapters.  Refused together with
+        ``prefix_cache: true`` (cached pages hold adapter-specific K / V)."""
+        paths = extra.get("lora") or {}
+        if not isinstance(paths, dict) or not all(isinstance(k, str) and isinstance(v, str) for k, v in paths.items()):
+            raise ValueError(f"lora must map adapter names to directories, got {paths!r}")
+        if not paths:
+            return {}, None
+        if prefix_cache:
+            raise ValueError("prefix_cache: true is not available together with lora adapters (cached pages hold "
+                             "adapter-specific K / V; the prefix index is not keyed by adapter)")
+        return dict(paths), {"max_adapters": len(paths), "max_rank": int(extra.get("lora_max_rank", 64))}
 
     @staticmethod
     def parse_prefix_cache(extra: dict) -> bool:
@@ -213,12 +236,21 @@ class LlamaPlugin(ModelPlugin):
             ids = self.tok.encode(str(req["prompt"]))
         gp = GenParams(max_new_tokens=int(req.get("max_new_tokens", self.ctx.settings.MAX_NEW_TOKENS)),
                        top_k=int(req.get("top_k", 1)), temperature=float(req.get("temperature", 1.0)),
-                       seed=int(req.get("seed", 0)))
+                       seed=int(req.get("seed", 0)), adapter=self.adapter_index(req.get("adapter")))
         if not ids:
             raise ValueError("empty prompt")
         if gp.max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         return ids, gp
+
+    def adapter_index(self, name) -> int:
+        """``"adapter"`` of a request -> the model's adapter index (absent: -1, the base model); an unknown
+        name is a ``ValueError``, as an empty prompt is."""
+        if name is None:
+            return -1
+        if not isinstance(name, str) or name not in self.adapters:
+            raise ValueError(f"unknown adapter {name!r} (configured: {sorted(self.adapters)})")
+        return self.adapters[name]
 
     def submit_generate(self, sample):
         """Continuous batching: enqueue into the scheduler; a concurrent.futures.Future of the
@@ -251,14 +283,17 @@ class LlamaPlugin(ModelPlugin):
         def run_batch(samples):
             groups: Dict[tuple, List[int]] = {}
             for i, (_ids, gp) in enumerate(samples):
-                groups.setdefault((gp.top_k, gp.temperature, gp.seed), []).append(i)
+                if not isinstance(gp.adapter, int):
+                    raise ValueError(f"a request names one adapter index, got {gp.adapter!r}")
+                groups.setdefault((gp.top_k, gp.temperature, gp.seed, gp.adapter), []).append(i)
             results: List[Any] = [None] * len(samples)
             for _key, members in groups.items():
                 ids_l = [samples[i][0] for i in members]
                 gp = samples[members[0]][1]
                 from ..models.llama import GenParams
 
-                gpg = GenParams(max(samples[i][1].max_new_tokens for i in members), gp.top_k, gp.temperature, gp.seed)
+                gpg = GenParams(max(samples[i][1].max_new_tokens for i in members), gp.top_k, gp.temperature, gp.seed,
+                                gp.adapter)
                 toks = self._generate_batch(ids_l, gpg)
                 for j, i in enumerate(members):
                     results[i] = (len(ids_l[j]), toks[j][: samples[i][1].max_new_tokens])
@@ -272,10 +307,12 @@ class LlamaPlugin(ModelPlugin):
 
         if self.model.tp == 1:
             return
-        hdr = torch.zeros(7, dtype=torch.int64, device=self.comm_dev)
+        hdr = torch.zeros(8, dtype=torch.int64, device=self.comm_dev)
         if op == OP_GENERATE:
+            if not isinstance(gp.adapter, int):  # one adapter per lockstep batch (run_batch groups by it)
+                raise ValueError(f"the lockstep header carries one adapter index, got {gp.adapter!r}")
             hdr[:] = torch.tensor([op, ids.shape[0], ids.shape[1], gp.max_new_tokens, gp.top_k,
-                                   int(gp.temperature * 1000), gp.seed])
+                                   int(gp.temperature * 1000), gp.seed, int(gp.adapter)])
         dist.broadcast(hdr, src=0)
         if op == OP_GENERATE:
             dist.broadcast(ids.to(self.comm_dev), src=0)
@@ -300,7 +337,7 @@ class LlamaPlugin(ModelPlugin):
         """Rank 0: one iteration's header (None = stop), then its admissions when it has any."""
         import torch.distributed as dist
 
-        hdr = torch.zeros(7, dtype=torch.int64, device=self.comm_dev)
+        hdr = torch.zeros(8, dtype=torch.int64, device=self.comm_dev)
         if admit is None:
             dist.broadcast(hdr, src=0)  # OP_STOP
             return
@@ -318,7 +355,7 @@ class LlamaPlugin(ModelPlugin):
         n = len(admit)
         S = max(len(a.ids) for a in admit)
         meta = torch.tensor([[a.slot, len(a.ids), a.gp.max_new_tokens, a.gp.top_k, round(a.gp.temperature * 1000),
-                              a.gp.seed] for a in admit], dtype=torch.int64, device=self.comm_dev)
+                              a.gp.seed, int(a.gp.adapter)] for a in admit], dtype=torch.int64, device=self.comm_dev)
         ids = torch.zeros(n, S, dtype=torch.int64, device=self.comm_dev)
         for j, a in enumerate(admit):
             ids[j, : len(a.ids)] = torch.tensor(a.ids, dtype=torch.int64)
@@ -329,7 +366,7 @@ class LlamaPlugin(ModelPlugin):
         """Followers: (op, admissions, longest prompt) of rank 0's explicit header."""
         import torch.distributed as dist
 
-        hdr = torch.zeros(7, dtype=torch.int64, device=self.comm_dev)
+        hdr = torch.zeros(8, dtype=torch.int64, device=self.comm_dev)
         dist.broadcast(hdr, src=0)
         op, n, S = hdr[:3].tolist()
         return op, n, S
@@ -341,14 +378,14 @@ class LlamaPlugin(ModelPlugin):
         from ..models.llama import GenParams
         from ..models.llama_serving import _Seq
 
-        meta = torch.zeros(n, 6, dtype=torch.int64, device=self.comm_dev)
+        meta = torch.zeros(n, 7, dtype=torch.int64, device=self.comm_dev)
         ids = torch.zeros(n, S, dtype=torch.int64, device=self.comm_dev)
         dist.broadcast(meta, src=0)
         dist.broadcast(ids, src=0)
         admit = []
         ids_l = ids.tolist()
-        for j, (slot, ln, mnt_j, topk_j, temp_j, seed_j) in enumerate(meta.tolist()):
-            seq = _Seq(ids_l[j][:ln], GenParams(mnt_j, topk_j, temp_j / 1000.0, seed_j), None)
+        for j, (slot, ln, mnt_j, topk_j, temp_j, seed_j, ad_j) in enumerate(meta.tolist()):
+            seq = _Seq(ids_l[j][:ln], GenParams(mnt_j, topk_j, temp_j / 1000.0, seed_j, ad_j), None)
             seq.slot = slot
             admit.append(seq)
         return admit
@@ -375,9 +412,9 @@ class LlamaPlugin(ModelPlugin):
         st = self.follower_stats = {"iters": 0, "hdr_s": 0.0, "hdr_max_s": 0.0, "iter_s": 0.0}
         while True:
             t0 = time.perf_counter()
-            hdr = torch.zeros(7, dtype=torch.int64, device=self.comm_dev)
+            hdr = torch.zeros(8, dtype=torch.int64, device=self.comm_dev)
             dist.broadcast(hdr, src=0)
-            op, B, S, mnt, topk, temp, seed = hdr.tolist()
+            op, B, S, mnt, topk, temp, seed, adapter = hdr.tolist()
             dt = time.perf_counter() - t0
             st["hdr_s"] += dt
             st["hdr_max_s"] = max(st["hdr_max_s"], dt)
@@ -389,12 +426,12 @@ class LlamaPlugin(ModelPlugin):
 
                 admit = []
                 if B:
-                    meta = torch.zeros(B, 6, dtype=torch.int64, device=self.comm_dev)
+                    meta = torch.zeros(B, 7, dtype=torch.int64, device=self.comm_dev)
                     ids = torch.zeros(B, S, dtype=torch.int64, device=self.comm_dev)
                     dist.broadcast(meta, src=0)
                     dist.broadcast(ids, src=0)
-                    for j, (slot, n, mnt_j, topk_j, temp_j, seed_j) in enumerate(meta.tolist()):
-                        seq = _Seq(ids[j, :n].tolist(), GenParams(mnt_j, topk_j, temp_j / 1000.0, seed_j), None)
+                    for j, (slot, n, mnt_j, topk_j, temp_j, seed_j, ad_j) in enumerate(meta.tolist()):
+                        seq = _Seq(ids[j, :n].tolist(), GenParams(mnt_j, topk_j, temp_j / 1000.0, seed_j, ad_j), None)
                         seq.slot = slot
                         admit.append(seq)
                 t1 = time.perf_counter()
@@ -406,7 +443,7 @@ class LlamaPlugin(ModelPlugin):
             lens = torch.zeros(B, dtype=torch.int32, device=self.comm_dev)
             dist.broadcast(ids, src=0)
             dist.broadcast(lens, src=0)
-            self.model.generate(ids, lens, GenParams(mnt, topk, temp / 1000.0, seed),
+            self.model.generate(ids, lens, GenParams(mnt, topk, temp / 1000.0, seed, adapter),
                                 prefill_chunk=self.prefill_chunk, speculate=self.speculate, drafter=self._drafter(),
                                 **self._spec_device_kw())
 
@@ -427,7 +464,7 @@ class LlamaPlugin(ModelPlugin):
             d.update({"tp": self.model.tp, "backend": self.model.backend, "max_batch": self.model.max_batch,
                       "max_seq": self.model.max_seq, "speculate": self.speculate,
                       "speculate_ngram": self.speculate_ngram, "speculate_device": self.speculate_device,
-                      "prefix_cache": self.prefix_cache,
+                      "prefix_cache": self.prefix_cache, "adapters": sorted(self.adapters),
                       "kv_dtype": self.model.kv_dtype, "kv_prefill": self.model.kv_prefill,
                       "kv_pages": self.kv_pages, "prefill_chunk": self.prefill_chunk})
         return d

@@ -123,3 +123,67 @@ def load_validated(path: str, spec: Spec, rename: Optional[Callable[[str], Optio
 
 def spec_of(state: Dict[str, torch.Tensor]) -> Spec:
     return {k: (tuple(v.shape), v.dtype) for k, v in state.items()}
+
+
+_PEFT_KEY = r"(?:^|\.)layers\.(\d+)\.(self_attn|mlp)\.(\w+)\.lora_(A|B)(?:\.[^.]+)?\.weight$"
+_NATIVE_KEY = r"^l(\d+)\.(\w+)\.lora_(A|B)$"
+
+
+def load_lora_adapter(path: str, layers: int) -> Tuple[Dict[str, torch.Tensor], dict]:
+    """A LoRA adapter from a PEFT directory: ``adapter_config.json`` + ``adapter_model.safetensors`` (safetensors
+    only: a directory that holds just ``adapter_model.bin`` is refused, nothing is unpickled).  Returns
+    ``(tensors, config)`` for ``LlamaTP.load_adapter``: tensors under the native names
+    ``l{i}.{q,k,v}.lora_A`` / ``.lora_B`` (PEFT's ``...layers.{i}.self_attn.{q,k,v}_proj.lora_{A,B}.weight``,
+    with or without an adapter name before ``.weight``, or the native names themselves), fp32.  The config is
+    validated (``models.llama.parse_lora_config``) and every tensor's rank against it; a tensor of a module
+    other than q / k / v, a layer outside the model, or a missing A / B of a target module is an error."""
+    import json
+    import re
+
+    from ..models.llama import LORA_TARGETS, parse_lora_config
+
+    cfg_file = os.path.join(path, "adapter_config.json")
+    st_file = os.path.join(path, "adapter_model.safetensors")
+    if not os.path.isdir(path) or not os.path.isfile(cfg_file):
+        raise CheckpointError(f"{path!r} is not a PEFT adapter directory (no adapter_config.json)")
+    if not os.path.isfile(st_file):
+        if os.path.isfile(os.path.join(path, "adapter_model.bin")):
+            raise CheckpointError(f"{path!r} holds adapter_model.bin only: pickled weights are refused, convert the "
+                                  f"adapter to adapter_model.safetensors")
+        raise CheckpointError(f"{path!r}: no adapter_model.safetensors")
+    with open(cfg_file) as f:
+        config = json.load(f)
+    mods, r, _alpha, _rs = parse_lora_config(config)
+    ck = Checkpoint(st_file)
+    tensors: Dict[str, torch.Tensor] = {}
+    for key in ck.keys():
+        m = re.search(_PEFT_KEY, key)
+        if m is not None:
+            i, module, ab = int(m.group(1)), m.group(3), m.group(4)
+            if m.group(2) != "self_attn" or module not in LORA_TARGETS:
+                raise CheckpointError(f"{path}: {key!r} adapts {module}, which is not served: only q_proj, k_proj and "
+                                      f"v_proj are")
+            p = LORA_TARGETS[module]
+        else:
+            m = re.match(_NATIVE_KEY, key)
+            if m is None:
+                raise CheckpointError(f"{path}: {key!r} is not a LoRA tensor of a q / k / v projection")
+            i, p, ab = int(m.group(1)), m.group(2), m.group(3)
+            if p not in LORA_TARGETS.values():
+                raise CheckpointError(f"{path}: {key!r} adapts {p}, which is not served: only q, k and v are")
+        if p not in mods:
+            raise CheckpointError(f"{path}: {key!r} is outside the config's target_modules {list(mods)}")
+        if not 0 <= i < layers:
+            raise CheckpointError(f"{path}: {key!r} names layer {i}, the model has {layers}")
+        name = f"l{i}.{p}.lora_{ab}"
+        if name in tensors:
+            raise CheckpointError(f"{path}: two tensors for {name}")
+        t = ck.get(key).to(torch.float32)
+        if t.dim() != 2 or t.shape[0 if ab == "A" else 1] != r:
+            raise CheckpointError(f"{path}: {key!r} has shape {tuple(t.shape)}, the config's rank is {r}")
+        tensors[name] = t
+    missing = [f"l{i}.{p}.lora_{ab}" for i in range(layers) for p in mods for ab in "AB"
+               if f"l{i}.{p}.lora_{ab}" not in tensors]
+    if missing:
+        raise CheckpointError(f"{path}: missing {missing[:4]} ({len(missing)} tensors)")
+    return tensors, config

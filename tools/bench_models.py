@@ -257,6 +257,8 @@ def bench_llama(args):
 
     if args.shared_prefix:
         return bench_llama_prefix(args)
+    if args.lora:
+        return bench_llama_lora(args)
 
     dev = torch.device("cuda:0")
     t0 = time.time()
@@ -308,6 +310,98 @@ def bench_llama(args):
                           "decode_ms_per_step": round(dec * 1e3, 3), "decode_tok_s": round(B / dec, 1)}), flush=True)
         for K in args.speculate:
             _bench_speculate(m, args, K, B, S, ids, lens, tok, cur)
+
+
+def bench_llama_lora(args):
+    """``--lora N --lora-rank R --lora-mix none same distinct``: Llama-3-8B with N random rank-R q/k/v adapters
+    against a model built without ``lora=`` (arm ``plain``: the default path), the arms interleaved ``--reps``
+    times in this process (medians).  Decode ms/step per batch, prefill of ``8 x --prompt``, and the two LoRA
+    launches of one layer alone (events over 200 calls)."""
+    import statistics
+
+    from mlmicroservicetemplate_amd import ops
+    from mlmicroservicetemplate_amd.models.llama import LLAMA3_8B, LlamaTP, init_llama_shard, random_lora_adapter
+
+    dev, cfg = torch.device("cuda:0"), LLAMA3_8B
+    t0 = time.time()
+    p = init_llama_shard(cfg, 1, 0, seed=0, device=dev)
+    kw = dict(backend="fused", device=dev, max_batch=max(max(args.batches), 8), max_seq=args.max_seq,
+              kv_pages=args.kv_pages, kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, kv_prefill=args.kv_prefill)
+    plain = LlamaTP(p, cfg, **kw)
+    m = LlamaTP(p, cfg, lora={"max_adapters": args.lora, "max_rank": args.lora_rank}, **kw)
+    for a in range(args.lora):
+        m.load_adapter(a, *random_lora_adapter(cfg, args.lora_rank, seed=100 + a, device=dev))
+    head = {"bench": "llama3-8b-lora", "adapters": args.lora, "rank": args.lora_rank, "weight_dtype": args.weight_dtype,
+            "kv_dtype": args.kv_dtype, "kv_pages": args.kv_pages}
+    print(json.dumps(dict(head, init_s=round(time.time() - t0, 1))), flush=True)
+    mixes = {"none": lambda b: -1, "same": lambda b: 0, "distinct": lambda b: b % args.lora}
+    arms = [("plain", plain, None)] + [(mix, m, mixes[mix]) for mix in args.lora_mix]
+
+    def set_arm(model, f):
+        if f is not None:
+            for b in range(model.max_batch):
+                model.set_slot_adapter(b, f(b))
+
+    def timed(fn, n):
+        t = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) / n
+
+    S = args.prompt
+    for B in args.batches:
+        tok = torch.randint(1000, 100000, (B, 1), device=dev, dtype=torch.int32)
+        cur = torch.full((B, 1), S, device=dev, dtype=torch.int32)
+        res = {name: [] for name, _, _ in arms}
+        for rep in range(args.reps + 1):  # round 0 warms every arm (graph capture) and is dropped
+            for name, model, f in arms:
+                set_arm(model, f)
+                step = lambda model=model: model.decode_step(tok, cur, 1, max_ctx=S + 1)  # noqa: E731
+                _warm(lambda: (step(), torch.cuda.synchronize()), args.warm_ms if rep else 0)
+                dt = timed(step, args.steps)
+                if rep:
+                    res[name].append(dt * 1e3)
+        print(json.dumps(dict(head, what="decode", batch=B, ctx=S, **{f"{k}_ms_per_step": round(statistics.median(v), 4)
+                                                                      for k, v in res.items()})), flush=True)
+    B = 8
+    ids = torch.randint(1000, 100000, (B, S), device=dev, dtype=torch.int32)
+    lens = torch.full((B,), S, device=dev, dtype=torch.int32)
+    pos = torch.arange(S, device=dev, dtype=torch.int32).unsqueeze(0).expand(B, S).contiguous()
+    res = {name: [] for name, _, _ in arms}
+    for rep in range(args.reps + 1):
+        for name, model, f in arms:
+            set_arm(model, f)
+            dt = timed(lambda model=model: model.step(ids, pos, lens, decode=False, k=1), 3)
+            if rep:
+                res[name].append(dt * 1e3)
+    print(json.dumps(dict(head, what="prefill", batch=B, prompt=S, **{f"{k}_ms": round(statistics.median(v), 3)
+                                                                      for k, v in res.items()})), flush=True)
+    # the two launches of one layer alone, every row on its own adapter (distinct) / on adapter 0 (same)
+    pack, N = m.lora_pack, m.qkv_width
+    for rows_B, rows_S in [(b, 1) for b in args.batches] + [(8, S)]:
+        if rows_B > m.max_batch:
+            continue
+        qkv = torch.randn(rows_B * rows_S, N, device=dev).to(torch.bfloat16)
+        r = torch.randn(rows_B * rows_S, cfg.hidden, device=dev).to(torch.bfloat16)
+        ns = ops.lora_split(rows_B, rows_S, cfg.hidden, pack.rcap)
+        ws = torch.empty(pack.workspace_elems(rows_B * rows_S, ns), device=dev)
+        for mix in ("same", "distinct"):
+            set_arm(m, mixes[mix])
+            out = {}
+            for name, fn in (("shrink", lambda: ops.lora_shrink(r, pack, 0, m.lora_slot, rows_B, rows_S, workspace=ws)),
+                             ("expand", lambda: ops.lora_expand_(qkv, pack, 0, m.lora_slot, rows_B, rows_S,
+                                                                 workspace=ws, eps=cfg.eps))):
+                for _ in range(20):
+                    fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(200):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                out[f"{name}_us"] = round(e0.elapsed_time(e1) * 1e3 / 200, 2)
+            print(json.dumps(dict(head, what="kernels", B=rows_B, S=rows_S, mix=mix, nsplit=ns, **out)), flush=True)
 
 
 def _bench_speculate(m, args, K, B, S, ids, lens, tok, cur):
@@ -494,6 +588,10 @@ def main():
     ap.add_argument("--suffix", type=int, nargs="+", default=[32, 128], help="llama --shared-prefix: suffix tokens LO HI")
     ap.add_argument("--prefix-cache", action="store_true", help="llama --shared-prefix: add the prefix_cache arms")
     ap.add_argument("--prefill-chunk", type=int, default=0, help="llama --shared-prefix: chunked prefill width")
+    ap.add_argument("--lora", type=int, default=0, help="llama: N random LoRA adapters on q/k/v (0: off)")
+    ap.add_argument("--lora-rank", type=int, default=16, help="llama --lora: their rank")
+    ap.add_argument("--lora-mix", nargs="+", choices=["none", "same", "distinct"], default=["none", "same", "distinct"],
+                    help="llama --lora: slots on the base model / all on adapter 0 / slot b on adapter b %% N")
     ap.add_argument("--reps", type=int, default=3, help="llama --shared-prefix: alternations of the arms")
     args = ap.parse_args()
     if args.skinny_max_split:
