@@ -177,20 +177,31 @@ def qkv_row_slices(cfg: LlamaConfig, tp: int, rank: int) -> Tuple[slice, slice]:
 
 
 LORA_TARGETS = {"q_proj": "q", "k_proj": "k", "v_proj": "v"}
+LORA_TARGETS_ALL = {**LORA_TARGETS, "o_proj": "o", "gate_proj": "gate", "up_proj": "up", "down_proj": "down"}
+LORA_TARGET_SETS = ("qkv", "all")  # what a model's lora={"targets": ...} may name
 
 
-def parse_lora_config(config: dict) -> Tuple[Tuple[str, ...], int, float, bool]:
+def parse_lora_config(config: dict, targets: str = "qkv") -> Tuple[Tuple[str, ...], int, float, bool]:
     """``(modules, r, alpha, use_rslora)`` of a PEFT ``adapter_config.json`` dict (or the native form of
-    the same keys); ``ValueError`` for everything the q/k/v LoRA path does not serve -- nothing is dropped."""
-    targets = config.get("target_modules")
-    if isinstance(targets, str) or not targets:
-        raise ValueError(f"LoRA config: target_modules must be a list of module names, got {targets!r}")
+    the same keys); ``ValueError`` for everything the LoRA path does not serve -- nothing is dropped.
+    ``targets``: the model's -- ``"qkv"`` serves q_proj, k_proj, v_proj alone, ``"all"`` the seven linear
+    projections (PEFT's ``"all-linear"`` is those seven)."""
+    if targets not in LORA_TARGET_SETS:
+        raise ValueError(f"LoRA targets must be one of {LORA_TARGET_SETS}, got {targets!r}")
+    served = LORA_TARGETS if targets == "qkv" else LORA_TARGETS_ALL
+    names = config.get("target_modules")
+    if names == "all-linear" and targets == "all":
+        names = list(LORA_TARGETS_ALL)
+    if isinstance(names, str) or not names:
+        raise ValueError(f"LoRA config: target_modules must be a list of module names, got {names!r}")
     mods = []
-    for t in targets:
+    for t in names:
         name = str(t).rsplit(".", 1)[-1]
-        if name not in LORA_TARGETS and name not in LORA_TARGETS.values():
-            raise ValueError(f"LoRA target module {t!r} is not served: only q_proj, k_proj and v_proj are")
-        mods.append(LORA_TARGETS.get(name, name))
+        if name not in served and name not in served.values():
+            if targets == "qkv":
+                raise ValueError(f"LoRA target module {t!r} is not served: only q_proj, k_proj and v_proj are")
+            raise ValueError(f"LoRA target module {t!r} is not served: only {', '.join(served)} are")
+        mods.append(served.get(name, name))
     if config.get("modules_to_save"):
         raise ValueError(f"LoRA config: modules_to_save {config['modules_to_save']!r} is not served")
     if config.get("bias", "none") not in ("none", None):
@@ -206,21 +217,29 @@ def parse_lora_config(config: dict) -> Tuple[Tuple[str, ...], int, float, bool]:
     if not isinstance(r, int) or not 1 <= r <= R.LORA_MAX_RANK:
         raise ValueError(f"LoRA config: rank r={r!r} outside 1..{R.LORA_MAX_RANK}")
     alpha = float(config.get("lora_alpha", r))
-    return tuple(p for p in R.LORA_MODULES if p in mods), r, alpha, bool(config.get("use_rslora", False))
+    return tuple(p for p in R.LORA_ALL_MODULES if p in mods), r, alpha, bool(config.get("use_rslora", False))
+
+
+def lora_module_dims(cfg: LlamaConfig) -> Dict[str, Tuple[int, int]]:
+    """``{module: (out, in)}`` of the unsharded projections a LoRA adapter may target."""
+    H, D = cfg.hidden, cfg.head_dim
+    return {"q": (cfg.heads * D, H), "k": (cfg.kv_heads * D, H), "v": (cfg.kv_heads * D, H), "o": (H, cfg.heads * D),
+            "gate": (cfg.intermediate, H), "up": (cfg.intermediate, H), "down": (H, cfg.intermediate)}
 
 
 def random_lora_adapter(cfg: LlamaConfig, rank: int, seed: int = 0, modules=("q", "k", "v"), alpha: float = 32.0,
                         b_std: float = 0.02, device="cpu") -> Tuple[Dict[str, torch.Tensor], dict]:
     """A random adapter for tests and benchmarks, ``(tensors, config)`` for :meth:`LlamaTP.load_adapter`:
-    drawn from :class:`RandomSource` under ``l{i}.{q,k,v}.lora_A/B``.  B is normal, not training's zero
-    init: a zero delta would make every test of it vacuous."""
+    drawn from :class:`RandomSource` under ``l{i}.{module}.lora_A/B``, ``modules`` any of q, k, v, o, gate, up,
+    down.  B is normal, not training's zero init: a zero delta would make every test of it vacuous."""
     src = RandomSource(seed, device)
-    out = {"q": cfg.heads * cfg.head_dim, "k": cfg.kv_heads * cfg.head_dim, "v": cfg.kv_heads * cfg.head_dim}
+    dims = lora_module_dims(cfg)
     t: Dict[str, torch.Tensor] = {}
     for i in range(cfg.layers):
         for p in modules:
-            t[f"l{i}.{p}.lora_A"] = src.region(f"l{i}.{p}.lora_A", (rank, cfg.hidden)) * (50.0 / cfg.hidden ** 0.5)
-            t[f"l{i}.{p}.lora_B"] = src.region(f"l{i}.{p}.lora_B", (out[p], rank)) * (b_std / 0.02)
+            n, k = dims[p]
+            t[f"l{i}.{p}.lora_A"] = src.region(f"l{i}.{p}.lora_A", (rank, k)) * (50.0 / k ** 0.5)
+            t[f"l{i}.{p}.lora_B"] = src.region(f"l{i}.{p}.lora_B", (n, rank)) * (b_std / 0.02)
     return t, {"r": rank, "lora_alpha": alpha, "target_modules": [f"{p}_proj" for p in modules]}
 
 
@@ -499,6 +518,7 @@ class _Forward:
     o: Optional[torch.Tensor] = None
     gu: Optional[torch.Tensor] = None
     lora_sid: Optional[torch.Tensor] = None  # cache slot of each sequence for the LoRA hook (None: the batch row)
+    tiles: Optional[object] = None  # ops.LoraTiles of the step (rt.lora_tail): its rows grouped by adapter, built once
 
     def take_xn(self) -> Optional[torch.Tensor]:
         xn, self.xn = self.xn, None
@@ -582,8 +602,13 @@ class LlamaTP:
         # LoRA: adapter of every cache slot (-1: base), read in place by the captured steps
         self.lora_slot = torch.full((max_batch,), -1, dtype=torch.int32, device=self.device)
         self.lora_cfg = None if lora is None else {"max_adapters": int(lora.get("max_adapters", 8)),
-                                                   "max_rank": int(lora.get("max_rank", 16))}
+                                                   "max_rank": int(lora.get("max_rank", 16)),
+                                                   "targets": lora.get("targets", "qkv")}
         self.lora_loaded: set = set()  # adapter indices in use
+        self.lora_wide: set = set()  # ... of those, the ones that target o / gate / up / down (targets "all")
+        self.lora_lin = None  # fused: ops.LoraLinearPack
+        self._lora_ref_lin: List[Dict[int, dict]] = [dict() for _ in range(cfg.layers)]  # as _lora_ref, o .. down
+        self._mlp_gain: List[torch.Tensor] = []
         self.lora_pack = None  # fused: ops.LoraPack
         self._lora_ref: List[Dict[int, dict]] = [dict() for _ in range(cfg.layers)]  # reference: layer -> index -> modules
         self._attn_gain: List[torch.Tensor] = []
@@ -593,6 +618,10 @@ class LlamaTP:
                                  f"got {self.lora_cfg}")
             # the gains as given: both backends fold or overwrite them below
             self._attn_gain = [self.p[f"l{i}.attn_norm"].float().clone() for i in range(cfg.layers)]
+            if self.lora_cfg["targets"] not in LORA_TARGET_SETS:
+                raise ValueError(f"lora: targets must be one of {LORA_TARGET_SETS}, got {self.lora_cfg['targets']!r}")
+            if self.lora_cfg["targets"] == "all":
+                self._mlp_gain = [self.p[f"l{i}.mlp_norm"].float().clone() for i in range(cfg.layers)]
         # int4: name -> (packed codes, scales) of the layer projections (fused backend only)
         self.w4: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
         self.w4_max_rows = self.w4_variant = 0
@@ -638,6 +667,16 @@ class LlamaTP:
                 # split-K slabs of every step up to 4096 rows (more rows run one split from a buffer of their own)
                 self.lora_ws = torch.empty(self.lora_pack.workspace_elems(4096, 1), device=self.device,
                                            dtype=torch.float32)
+                if self.lora_cfg["targets"] == "all":
+                    H, I = cfg.hidden, self.sd.inter
+                    self.lora_lin = ops.pack_lora_linear(
+                        cfg.layers, {"o": (H, self.sd.hq * D), "gate": (I, H), "up": (I, H), "down": (H, I)},
+                        self.lora_cfg["max_adapters"], self.lora_cfg["max_rank"], self.device)
+                    # the tile table and split-K slabs of every step up to 4096 rows (256 tiles at one split; a
+                    # decode step's few tiles at 16); larger steps take buffers of their own
+                    self.lora_tab = torch.empty(16 + 18 * 4096, device=self.device, dtype=torch.int32)
+                    self.lora_lin_ws = torch.empty(self.lora_lin.workspace_elems(256, 1), device=self.device,
+                                                   dtype=torch.float32)
             self.ver_ws: Optional[torch.Tensor] = None  # split-KV partials of the uncaptured verify steps
             self._ver_ws_graph: Optional[torch.Tensor] = None  # ... of the verify graph being warmed up / captured
         self._alloc_kv_cache(kv_pages)
@@ -928,6 +967,8 @@ class LlamaTP:
                                     slot_ids=slots_b, page_table=table)
             else:
                 a = R.attention(qkv_r, B, S, sd.hq, sd.hkv, D, kv_lens=lens, causal=True)
+        if self.lora_wide:
+            return self._ref_tail_lora(i, x, a, B, S, slots_b)
         if w8:
             x = x + self.comm.all_reduce_(self._ref_w8(f"l{i}.o", a))
             h = F.silu(self._ref_w8(f"l{i}.gate", x, norm=True)) * self._ref_w8(f"l{i}.up", x, norm=True)
@@ -938,6 +979,24 @@ class LlamaTP:
         h = F.silu(xn @ p[f"l{i}.gate"].float().T) * (xn @ p[f"l{i}.up"].float().T)
         d = self.comm.all_reduce_(h @ p[f"l{i}.down"].float().T)
         return x + d
+
+    def _ref_tail_lora(self, i: int, x: torch.Tensor, a: torch.Tensor, B: int, S: int, slots_b) -> torch.Tensor:
+        """The layer tail while an adapter on o / gate / up / down is loaded: each rank adds its share of the
+        delta (o, down: its K slice of A; gate, up: its rows of B) to its partial product, in fp32."""
+        cfg, p, w8 = self.cfg, self.p, self.weight_dtype == "w8a8"
+        n = self.lora_cfg["max_adapters"]
+        ads = [self._lora_ref_lin[i].get(k, {}) for k in range(n)]
+        rows = (self.lora_slot, B, S, slots_b)
+        o = self._ref_w8(f"l{i}.o", a) if w8 else a @ p[f"l{i}.o"].float().T
+        x = x + self.comm.all_reduce_(R.lora_linear(o, a, [ad.get("o") for ad in ads], *rows))
+        if w8:
+            gu = torch.cat([self._ref_w8(f"l{i}.gate", x, norm=True), self._ref_w8(f"l{i}.up", x, norm=True)], dim=1)
+        else:
+            xn = R.layernorm(x, p[f"l{i}.mlp_norm"], None, eps=cfg.eps, rms=True)[0]
+            gu = torch.cat([xn @ p[f"l{i}.gate"].float().T, xn @ p[f"l{i}.up"].float().T], dim=1)
+        h = R.lora_gate_up(gu, x, self._mlp_gain[i], ads, *rows, eps=cfg.eps)
+        d = self._ref_w8(f"l{i}.down", h) if w8 else h @ p[f"l{i}.down"].float().T
+        return x + self.comm.all_reduce_(R.lora_linear(d, h, [ad.get("down") for ad in ads], *rows))
 
     def _ref_w8(self, name: str, x: torch.Tensor, norm: bool = False) -> torch.Tensor:
         """The W8A8 projection of the rows ``x`` (rounded to bf16) by W_name; ``norm``: of RMSNorm(x), its gain
@@ -975,6 +1034,7 @@ class LlamaTP:
             w4_max_rows=self.w4_max_rows, pk_fold=self.pk_fold, prefill_fold=self.prefill_fold,
             fuse_combine=self.fuse_combine, fuse_add_norm=self.fuse_add_norm, ar_fuse=self.ar_fuse,
             tp_overlap=self.tp_overlap and not self.lora_loaded, verify_attn=self.verify_attn,
+            lora_tail=bool(self.lora_wide),
             spec_max_tokens=self.spec_max_tokens,
             dec_chunk=self.dec_chunk, ar_fusable=car is not None and car.fusable(B * S * cfg.hidden),
             capturing=self.tp > 1 and self.device.type == "cuda" and torch.cuda.is_current_stream_capturing())
@@ -1189,6 +1249,11 @@ class LlamaTP:
         else:
             h = self._proj(tr, a, f"l{i}.o", residual=st.r)
         st.o = h
+        if st.rt.lora_tail:
+            self._lora_lin_add(i, "o", h, a, st)
+            st.gu = gu = self._lora_gate_up(i, self._norm_proj(tr, h, f"l{i}.gate_up")[0], h, st)
+            st.r = self._lora_lin_add(i, "down", self._proj(tr, gu, f"l{i}.down", residual=h), gu, st)
+            return
         gu, _ = self._norm_proj(tr, h, f"l{i}.gate_up", act=self.ops.ACT_SILU_MUL)
         st.gu = gu
         st.r = self._proj(tr, gu, f"l{i}.down", residual=h)
@@ -1212,6 +1277,12 @@ class LlamaTP:
         """The all-reduce pair: o and down each summed over the ranks, each added to r by the pre-norm
         of the projection after it (delta)."""
         rt = st.rt
+        if rt.lora_tail:  # each rank's share of a delta joins its partial product ahead of the all-reduce
+            st.o = o = self.comm.all_reduce_(self._lora_lin_add(i, "o", self._proj(rt.proj, a, f"l{i}.o"), a, st))
+            pre, st.r = self._norm_proj(rt.proj, st.r, f"l{i}.gate_up", o)
+            st.gu = gu = self._lora_gate_up(i, pre, st.r, st)
+            st.delta = self.comm.all_reduce_(self._lora_lin_add(i, "down", self._proj(rt.proj, gu, f"l{i}.down"), gu, st))
+            return
         if parts is None:
             o = self._row_parallel(rt, a, f"l{i}.o")
         else:
@@ -1248,6 +1319,8 @@ class LlamaTP:
         st = _Forward(rt, B, S, decode, pos, lens, past, slots, r=self._embed(ids.reshape(-1)))
         if self.lora_loaded and slot_ids is not None and not decode:
             st.lora_sid = slot_ids.to(torch.int32)
+        if rt.lora_tail:
+            st.tiles = self._lora_tiles(st)
         if rt.overlap:
             st.r, st.delta = self._prefill_overlapped(rt, st.r, pos, lens, B, S, slots)
         else:
@@ -1338,24 +1411,60 @@ class LlamaTP:
         ops.lora_qkv_(qkv, st.r, pack, i, self.lora_slot, st.B, st.S, st.lora_sid, eps=self.cfg.eps, workspace=ws,
                       nsplit=nsplit)
 
+    # -- o / gate / up / down (targets "all"): csrc/lora_linear.hip on the step's tile table
+    def _lora_tiles(self, st: "_Forward"):
+        """The step's rows grouped by adapter, once per forward (every layer's six launches read it)."""
+        ops, n = self.ops, self.lora_cfg["max_adapters"]
+        tab = self.lora_tab
+        if ops.lora_table_elems(st.B, st.S, n) > tab.numel():
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"LoRA: a captured step of {st.B * st.S} rows exceeds the model's tile table")
+            tab = None
+        return ops.lora_tiles(self.lora_slot, st.B, st.S, st.lora_sid, n_adapters=n, out=tab)
+
+    def _lora_lin_kw(self, module: str, st: "_Forward") -> dict:
+        pack, group = self.lora_lin, self.lora_lin.group_of(module)
+        nsplit = self.ops.lora_linear_split(st.tiles, pack.dims[group][1], pack.dims[group][2])
+        ws = self.lora_lin_ws
+        if pack.workspace_elems(st.tiles.max_tiles, nsplit, group) > ws.numel():
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"LoRA: a captured step of {st.B * st.S} rows exceeds the model's split-K workspace")
+            ws = None
+        return dict(eps=self.cfg.eps, workspace=ws, nsplit=nsplit)
+
+    def _lora_lin_add(self, i: int, module: str, y: torch.Tensor, x: torch.Tensor, st: "_Forward") -> torch.Tensor:
+        """``y += s B (A . x)`` in place on the rows whose slot names an adapter with ``module`` (o or down)."""
+        return self.ops.lora_linear_(y, x, self.lora_lin, module, i, st.tiles, **self._lora_lin_kw(module, st))
+
+    def _lora_gate_up(self, i: int, pre: torch.Tensor, r: torch.Tensor, st: "_Forward") -> torch.Tensor:
+        """``silu(g + dg) * (u + du)`` from the pre-activation gate / up of the post-add residual ``r``."""
+        return self.ops.lora_gate_up(pre, r, self.lora_lin, i, st.tiles, **self._lora_lin_kw("gate", st))
+
     def load_adapter(self, index: int, tensors: Dict[str, torch.Tensor], config: dict) -> None:
         """Load LoRA adapter ``index`` in place (fixed addresses: steps captured with an adapter loaded stay
         valid; the first load drops the steps captured before it, which hold no LoRA launches).  ``tensors``:
-        the unsharded ``l{i}.{q,k,v}.lora_A [r, hidden]`` / ``.lora_B [out, r]`` of every layer; ``config``:
-        PEFT's keys (``r``, ``lora_alpha``, ``use_rslora``, ``target_modules``).  Each rank keeps A whole and
-        the rows of B that it holds of the base matrices.  ``ValueError`` for whatever is not served
+        the unsharded ``l{i}.{module}.lora_A [r, in]`` / ``.lora_B [out, r]`` of every layer, modules q, k, v
+        and, on a model built with ``lora={"targets": "all"}``, o, gate, up, down; ``config``: PEFT's keys
+        (``r``, ``lora_alpha``, ``use_rslora``, ``target_modules``).  Each rank keeps its share as the base
+        matrices are sharded: of q, k, v, gate, up (column-parallel) A whole and its rows of B; of o and down
+        (row-parallel) its K slice of A and all of B, its partial delta joining its partial product ahead of
+        the all-reduce.  ``ValueError`` for whatever is not served
         (:func:`parse_lora_config`), a bad index, shapes that disagree with the config."""
         if self.lora_cfg is None:
             raise ValueError("this model was built without lora=...: no room for adapters")
         if not isinstance(index, int) or not 0 <= index < self.lora_cfg["max_adapters"]:
             raise ValueError(f"adapter index {index!r} outside [0, {self.lora_cfg['max_adapters']}): more adapters "
                              f"than max_adapters")
-        mods, r, alpha, rslora = parse_lora_config(config)
+        mods, r, alpha, rslora = parse_lora_config(config, targets=self.lora_cfg["targets"])
         if r > self.lora_cfg["max_rank"]:
             raise ValueError(f"adapter rank {r} exceeds the model's lora max_rank {self.lora_cfg['max_rank']}")
         cfg, D = self.cfg, self.cfg.head_dim
         qs, ks = qkv_row_slices(cfg, self.tp, self.rank)
-        full = {"q": cfg.heads * D, "k": cfg.kv_heads * D, "v": cfg.kv_heads * D}
+        full = lora_module_dims(cfg)
+        sl = slice(self.rank * self.sd.inter, (self.rank + 1) * self.sd.inter)
+        # this rank's share: the rows of B it holds of a column-parallel matrix, its K slice of A of a row-parallel one
+        b_rows = {"q": qs, "k": ks, "v": ks, "gate": sl, "up": sl}
+        a_cols = {"o": qs, "down": sl}
         local: Dict[str, torch.Tensor] = {}
         for i in range(cfg.layers):
             for p in mods:
@@ -1363,22 +1472,39 @@ class LlamaTP:
                     A, Bm = tensors[f"l{i}.{p}.lora_A"], tensors[f"l{i}.{p}.lora_B"]
                 except KeyError as e:
                     raise ValueError(f"adapter has no tensor {e.args[0]!r} (target module {p}_proj)") from None
-                if tuple(A.shape) != (r, cfg.hidden) or tuple(Bm.shape) != (full[p], r):
+                if tuple(A.shape) != (r, full[p][1]) or tuple(Bm.shape) != (full[p][0], r):
                     raise ValueError(f"l{i}.{p}: lora_A {tuple(A.shape)} / lora_B {tuple(Bm.shape)} do not match the "
-                                     f"config: expected ({r}, {cfg.hidden}) / ({full[p]}, {r})")
-                local[f"l{i}.{p}.lora_A"] = A
-                local[f"l{i}.{p}.lora_B"] = Bm[qs if p == "q" else ks]
+                                     f"config: expected ({r}, {full[p][1]}) / ({full[p][0]}, {r})")
+                local[f"l{i}.{p}.lora_A"] = A[:, a_cols[p]] if p in a_cols else A
+                local[f"l{i}.{p}.lora_B"] = Bm[b_rows[p]] if p in b_rows else Bm
         extra = [k for k in tensors if k not in local]
         if extra:
             raise ValueError(f"adapter tensors outside the config's target modules: {sorted(extra)[:4]}")
-        scales = {p: R.lora_scale(alpha, r, rslora) for p in mods}
+        s = R.lora_scale(alpha, r, rslora)
+        qkv_mods = [p for p in mods if p in R.LORA_MODULES]
+        lin_mods = [p for p in mods if p in R.LORA_LINEAR_MODULES]
         if self.backend == "fused":
-            self.lora_pack.load(index, local, scales, gains=self._attn_gain)
+            if qkv_mods:
+                self.lora_pack.load(index, local, {p: s for p in qkv_mods}, gains=self._attn_gain)
+            else:
+                self.lora_pack.seg[index].zero_()  # whatever the slot held before serves no row
+            if lin_mods:
+                self.lora_lin.load(index, local, {p: s for p in lin_mods},
+                                   gains={"gate": self._mlp_gain, "up": self._mlp_gain})
+            elif self.lora_lin is not None:
+                self.lora_lin.seg[index].zero_()
         else:
             for i in range(cfg.layers):
-                self._lora_ref[i][index] = {p: (local[f"l{i}.{p}.lora_A"].to(self.device, torch.float32),
-                                                local[f"l{i}.{p}.lora_B"].to(self.device, torch.float32), scales[p])
-                                            for p in mods}
+                for ref, ms in ((self._lora_ref, qkv_mods), (self._lora_ref_lin, lin_mods)):
+                    ref[i][index] = {p: (local[f"l{i}.{p}.lora_A"].to(self.device, torch.float32),
+                                         local[f"l{i}.{p}.lora_B"].to(self.device, torch.float32), s) for p in ms}
+        was_wide = bool(self.lora_wide)
+        (self.lora_wide.add if lin_mods else self.lora_wide.discard)(index)
+        if bool(self.lora_wide) != was_wide:
+            # the captured steps ran the other layer tail (llama_route: lora_tail): capture again
+            self._graphs.clear()
+            self._ver_graphs.clear()
+            self._dev_graphs.clear()
         if not self.lora_loaded:
             # steps captured so far hold no LoRA launches (nothing new runs while no adapter is loaded): drop
             # them, the next step captures again with the hook in.  Later loads rewrite fixed addresses only.

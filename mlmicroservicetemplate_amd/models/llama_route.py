@@ -67,6 +67,7 @@ class StepRoute:
     multi: bool         # verify step on ops.decode_attention_multi
     overlap: bool       # TP prefill as two interleaved batch halves
     dec_chunk: int      # decode split rows
+    lora_tail: bool = False  # a loaded adapter targets o / gate / up / down: the tail runs unfused around the deltas
 
     @property
     def fuse(self) -> bool:
@@ -90,11 +91,15 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
                o_fp8: bool, w4_max_rows: int, pk_fold: bool, prefill_fold: bool, fuse_combine: bool,
                fuse_add_norm: bool, ar_fuse: bool, tp_overlap: bool, verify_attn: str, spec_max_tokens: int,
                dec_chunk: int, ar_fusable: bool, capturing: bool, kv_fp8: bool = False,
-               have_w8: bool = False) -> StepRoute:
+               have_w8: bool = False, lora_tail: bool = False) -> StepRoute:
     """``have_*``: the model holds such copies at all; ``o_packed`` / ``o_fp8``: of ``l0.o``;
     ``ar_fusable``: the comm's one-shot all-reduce can ride in a GEMM producing ``B * S * hidden``
     outputs; ``capturing``: the current stream is capturing a graph.  The rest are the model's
-    dimensions on this rank and its switches under their own names; ``kv_fp8``: the cache is e4m3."""
+    dimensions on this rank and its switches under their own names; ``kv_fp8``: the cache is e4m3.
+    ``lora_tail``: a loaded LoRA adapter targets o, gate, up or down -- a delta cannot pass through the split-KV
+    combine prologue, the fused all-reduce, ``linear_add_rmsnorm`` or the overlapped TP prefill, so those are
+    off and the tail runs o -> + delta -> gate / up without activation -> ``lora_gate_up`` -> down -> + delta
+    (csrc/lora_linear.hip).  Off (q / k / v adapters only, or none): every decision below is as before."""
     T = B * S
     proj = proj_tiers(T, have_packed, have_w4, have_fp8, w4_max_rows, have_w8)
     # TP = 1: the residual add rides in the o / down epilogues (h = r + a Wo^T, r' = h + g Wd^T), so
@@ -136,5 +141,7 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
     # From batch 32 up the grid is already >= 4k blocks and 128-row splits halve the combine
     # traffic: -3 % step time at batch 128 (profiles/r2_llama8b_decode_chunk_sweep.jsonl).
     chunk = dec_chunk if dec_chunk > 0 else (128 if B >= 32 else 64)
+    if lora_tail:
+        combine = ar = fuse_rn = overlap = False
     return StepRoute(proj=proj, fold=bool(fold), fuse_combine=bool(combine), ar_fuse=bool(ar), fuse_rn=bool(fuse_rn),
-                     multi=bool(multi), overlap=bool(overlap), dec_chunk=chunk)
+                     multi=bool(multi), overlap=bool(overlap), dec_chunk=chunk, lora_tail=bool(lora_tail))

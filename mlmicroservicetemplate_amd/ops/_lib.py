@@ -127,6 +127,12 @@ _SIGS = {
     "mls_lora_split": [I, I, I, I],
     "mls_lora_shrink": [P, I, P, P, P, P, P, SZ, I, I, I, I, I, I, I, P],
     "mls_lora_expand": [P, I, P, P, P, P, P, P, SZ, I, I, I, F, I, I, I, I, I, I, I, I, P],
+    "mls_lora_max_tiles": [I, I, I],
+    "mls_lora_table_elems": [I, I, I],
+    "mls_lora_tiles": [P, P, P, SZ, I, I, I, I, P],
+    "mls_lora_shrink_x": [P, I, P, P, P, P, SZ, I, I, I, I, I, I, I, I, I, I, P],
+    "mls_lora_expand_add": [P, I, P, P, P, P, P, SZ, I, I, I, F, I, I, I, I, I, I, I, P],
+    "mls_lora_expand_silu": [P, P, P, P, P, P, P, SZ, I, I, I, F, I, I, I, I, I, I, I, P],
     "mls_stream_create_cumask": [P, I, _c.POINTER(P)],
     "mls_stream_get_cumask": [P, P, I],
     "mls_stream_destroy": [P],
@@ -161,7 +167,7 @@ def _bind(lib: ctypes.CDLL) -> None:
 
 DEBUG = os.environ.get("MLS_DEBUG", "0") == "1"
 DEBUG_TUS = ("attention", "norm_ops", "stem_pool", "conv3x3_halo", "kv_fp8", "flash_ctx", "decode_verify",
-             "decode_pick", "spec_step", "lora")  # translation units with MLS_CHECK bounds
+             "decode_pick", "spec_step", "lora", "lora_linear")  # translation units with MLS_CHECK bounds
 DEBUG_CODES = {
     101: "rope/KV append: cache slot beyond the cache",
     102: "rope/KV append: position beyond the RoPE table",
@@ -186,6 +192,10 @@ DEBUG_CODES = {
     501: "lora: a sequence's cache slot lies outside lora_slot",
     502: "lora: lora_slot names an adapter outside [-1, max_adapters)",
     503: "lora: an adapter's rank table does not fit the pack (not written by LoraPack.load)",
+    511: "lora_linear: the tile table's count lies outside [0, max_tiles] (not written by mls_lora_tiles)",
+    512: "lora_linear: a tile names an adapter outside [0, max_adapters)",
+    513: "lora_linear: a tile names a row outside [-1, rows)",
+    514: "lora_linear: an adapter's rank table does not fit the pack (not written by LoraLinearPack.load)",
 }
 
 

@@ -245,3 +245,44 @@ def lora_qkv(qkv: torch.Tensor, x: torch.Tensor, gain: torch.Tensor, adapters, l
             t = xn[rows] @ A.float().T
             out[rows, starts[j]: starts[j] + widths[j]] += float(s) * (t @ Bm.float().T)
     return out
+
+
+# ------------------------------------------------------------------ LoRA on o, gate / up and down
+LORA_LINEAR_MODULES = ("o", "gate", "up", "down")
+LORA_ALL_MODULES = LORA_MODULES + LORA_LINEAR_MODULES
+
+
+def _lora_rows(lora_slot, B: int, S: int, slot_ids):
+    """``(rows of sequence b, its adapter)`` for the sequences that have one."""
+    for b in range(B):
+        a = int(lora_slot[b if slot_ids is None else int(slot_ids[b])])
+        if a >= 0:
+            yield slice(b * S, (b + 1) * S), a
+
+
+def lora_linear(y: torch.Tensor, x: torch.Tensor, adapters, lora_slot, B: int, S: int, slot_ids=None, gain=None,
+                eps: float = 1e-5) -> torch.Tensor:
+    """The per-request LoRA rule on one projection, in fp32: row m of sequence b takes adapter ``a =
+    lora_slot[slot_ids[b] or b]`` (-1: the row stays) and ``y[m] += s * B (A . x[m])`` with ``adapters[a] =
+    (A [r, K], B [N, r], s)`` or None (the adapter lacks the module).  Plain form: ``x`` is the projection's
+    input; with ``gain`` the input is ``RMSNorm(x) * gain`` (the normed form).  Returns a new tensor."""
+    out = y.float().clone()
+    xf = x.float()
+    if gain is not None:
+        xf = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * gain.float().view(1, -1)
+    for rows, a in _lora_rows(lora_slot, B, S, slot_ids):
+        if adapters[a] is not None:
+            A, Bm, s = adapters[a]
+            out[rows] += float(s) * ((xf[rows] @ A.float().T) @ Bm.float().T)
+    return out
+
+
+def lora_gate_up(gu_pre: torch.Tensor, x: torch.Tensor, gain: torch.Tensor, adapters, lora_slot, B: int, S: int,
+                 slot_ids=None, eps: float = 1e-5) -> torch.Tensor:
+    """``silu(g + dg) * (u + du)`` ``[M, I]`` in fp32 from the pre-activation ``gu_pre [M, 2I]`` (gate columns,
+    then up columns: not interleaved), ``d = s * B (A . RMSNorm(x) * gain)`` of ``adapters[a] = {"gate": (A, B,
+    s), "up": ...}`` (either may be missing) for the row's adapter as in :func:`lora_linear`."""
+    I = gu_pre.shape[1] // 2
+    g = lora_linear(gu_pre[:, :I], x, [ad.get("gate") for ad in adapters], lora_slot, B, S, slot_ids, gain, eps)
+    u = lora_linear(gu_pre[:, I:], x, [ad.get("up") for ad in adapters], lora_slot, B, S, slot_ids, gain, eps)
+    return F.silu(g) * u

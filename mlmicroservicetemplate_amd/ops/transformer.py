@@ -1008,3 +1008,256 @@ def lora_qkv_(qkv: torch.Tensor, resid: torch.Tensor, pack: LoraPack, layer: int
         workspace = torch.empty(pack.workspace_elems(B * S, max(ns, 1)), device=qkv.device, dtype=torch.float32)
     nsplit = lora_shrink(resid, pack, layer, lora_slot, B, S, slot_ids, workspace=workspace, nsplit=nsplit)
     return lora_expand_(qkv, pack, layer, lora_slot, B, S, slot_ids, eps=eps, workspace=workspace, nsplit=nsplit)
+
+
+# ------------------------------------------------------------------ LoRA on o, gate / up and down
+LORA_LINEAR_MODULES = ("o", "gate", "up", "down")
+_LL_GROUPS = {"o": ("o",), "gate_up": ("gate", "up"), "down": ("down",)}  # modules that share a pass over x
+_LL_HDR = 16  # ints of the tile table before tile_adapter
+
+
+class LoraLinearPack:
+    """The o / gate / up / down adapters of one model as csrc/lora_linear.hip reads them: fixed-address device
+    arrays sized for ``max_adapters x max_rank`` at construction (a captured graph stays valid across
+    :meth:`load`).  ``shapes``: ``{module: (out, in)}`` of the modules held, this rank's; gate and up come
+    together.  Per group g in o, gate_up, down:
+
+    ``A[g] [layers][max_adapters][acap][in]`` bf16, the group's segments at the adapter's own padded rank (multiples
+    of 16) end to end, ``acap = segments * padded max_rank``; ``B[g] [layers][max_adapters][out * bcap]`` bf16, of
+    which the first ``out * rpad`` hold ``[out][rpad]`` rows, ``rpad`` the adapter's padded rank -- gate and up
+    rows interleaved by 8 like the fused weights.  ``seg`` / ``scale`` ``[max_adapters][4]`` over (o, gate, up, down):
+    padded ranks (0: absent) and ``s``.  A slot whose ``seg`` row is 0 is never read, whatever it holds."""
+
+    def __init__(self, layers: int, shapes, max_adapters: int, max_rank: int, device):
+        if not 1 <= int(max_rank) <= LORA_MAX_RANK:
+            raise ValueError(f"max_rank must be in 1..{LORA_MAX_RANK}, got {max_rank}")
+        if int(max_adapters) < 1:
+            raise ValueError(f"max_adapters must be positive, got {max_adapters}")
+        shapes = {p: (int(n), int(k)) for p, (n, k) in shapes.items()}
+        if not shapes or any(p not in LORA_LINEAR_MODULES for p in shapes) or ("gate" in shapes) != ("up" in shapes):
+            raise ValueError(f"modules must be a non-empty subset of {LORA_LINEAR_MODULES} (gate and up together), "
+                             f"got {sorted(shapes)}")
+        if "gate" in shapes and (shapes["gate"] != shapes["up"] or shapes["gate"][0] % 8):
+            raise ValueError(f"gate {shapes['gate']} and up {shapes['up']} must agree, rows a multiple of 8")
+        for p, (n, k) in shapes.items():
+            if k % LORA_K_GRAN or k <= 0:
+                raise ValueError(f"{p}: in-features {k} are not a multiple of the LoRA kernels' K granule {LORA_K_GRAN}")
+            if n <= 0 or (n % 16 and p not in ("gate", "up")):
+                raise ValueError(f"{p}: out-features {n} must be a multiple of 16")
+        self.layers, self.shapes = int(layers), shapes
+        self.max_adapters, self.max_rank = int(max_adapters), int(max_rank)
+        self.bcap = -(-self.max_rank // LORA_GRAN) * LORA_GRAN
+        self.device = torch.device(device)
+        dev, n, L = self.device, self.max_adapters, self.layers
+        self.A, self.B, self.dims = {}, {}, {}
+        for g, mods in _LL_GROUPS.items():
+            if mods[0] not in shapes:
+                continue
+            out, k = shapes[mods[0]]
+            N = out * len(mods)
+            self.dims[g] = (N, k, len(mods) * self.bcap)
+            self.A[g] = torch.zeros(L, n, len(mods) * self.bcap, k, device=dev, dtype=torch.bfloat16)
+            self.B[g] = torch.zeros(L, n, N * self.bcap, device=dev, dtype=torch.bfloat16)
+        self.seg = torch.zeros(n, 4, device=dev, dtype=torch.int32)
+        self.scale = torch.zeros(n, 4, device=dev, dtype=torch.float32)
+        self.loaded = [False] * n
+
+    @staticmethod
+    def group_of(module: str) -> str:
+        return "gate_up" if module in ("gate", "up", "gate_up") else module
+
+    def workspace_elems(self, max_tiles: int, nsplit: int, group: Optional[str] = None) -> int:
+        """fp32 elements of split-K slabs for ``max_tiles`` tiles (``group`` None: the widest group held)."""
+        acap = max(d[2] for d in self.dims.values()) if group is None else self.dims[self.group_of(group)][2]
+        return int(nsplit) * int(max_tiles) * 16 * (acap + 1)
+
+    def load(self, index: int, tensors, scales, gains=None) -> None:
+        """Write adapter ``index`` in place.  ``tensors``: ``l{i}.{module}.lora_A [r, in]`` / ``.lora_B [out, r]``
+        (this rank's slices) for every layer and every module of ``scales = {module: s}``; ``gains``:
+        ``{module: [per layer gain [in]]}`` folded into that module's A (the normed input form)."""
+        if not 0 <= int(index) < self.max_adapters:
+            raise ValueError(f"adapter index {index} outside [0, {self.max_adapters})")
+        mods = [p for p in LORA_LINEAR_MODULES if p in scales]
+        if not mods or len(mods) != len(scales) or any(p not in self.shapes for p in mods):
+            raise ValueError(f"LoRA modules must be a non-empty subset of {tuple(self.shapes)}, got {sorted(scales)}")
+        ranks = {}
+        for p in mods:
+            N, K = self.shapes[p]
+            for i in range(self.layers):
+                A, Bm = tensors[f"l{i}.{p}.lora_A"], tensors[f"l{i}.{p}.lora_B"]
+                r = A.shape[0]
+                if not 1 <= r <= self.max_rank:
+                    raise ValueError(f"l{i}.{p}: rank {r} outside 1..{self.max_rank} (the pack's max_rank)")
+                if ranks.setdefault(p, r) != r:
+                    raise ValueError(f"l{i}.{p}: rank {r} differs from layer 0's {ranks[p]} (per-layer ranks)")
+                if tuple(A.shape) != (r, K) or tuple(Bm.shape) != (N, r):
+                    raise ValueError(f"l{i}.{p}: lora_A {tuple(A.shape)} / lora_B {tuple(Bm.shape)}; expected "
+                                     f"({r}, {K}) / ({N}, {r})")
+        pad = {p: -(-ranks[p] // LORA_GRAN) * LORA_GRAN for p in mods}
+        dev = self.device
+        self.seg[index].zero_()  # the slot serves as base while its rows change
+        for g, gm in _LL_GROUPS.items():
+            have = [p for p in gm if p in pad]
+            if not have:
+                continue
+            stride = max(pad[p] for p in have)
+            out = self.shapes[gm[0]][0]
+            for i in range(self.layers):
+                off = 0
+                Bs = []
+                for p in gm:
+                    Bp = torch.zeros(out, stride, device=dev, dtype=torch.bfloat16)
+                    if p in pad:
+                        A = tensors[f"l{i}.{p}.lora_A"].to(dev, torch.float32)
+                        if gains is not None and p in gains:
+                            A = A * gains[p][i].to(dev, torch.float32).view(1, -1)
+                        self.A[g][i, index, off: off + pad[p]].zero_()
+                        self.A[g][i, index, off: off + ranks[p]] = A.to(torch.bfloat16)
+                        Bp[:, : ranks[p]] = tensors[f"l{i}.{p}.lora_B"].to(dev, torch.bfloat16)
+                        off += pad[p]
+                    Bs.append(Bp)
+                Bw = Bs[0] if len(Bs) == 1 else torch.stack(
+                    [Bs[0].view(out // 8, 8, stride), Bs[1].view(out // 8, 8, stride)], dim=1)
+                self.B[g][i, index, : Bw.numel()] = Bw.reshape(-1)
+        self.scale[index] = torch.tensor([float(scales.get(p, 0.0)) for p in LORA_LINEAR_MODULES], dtype=torch.float32)
+        self.seg[index] = torch.tensor([pad.get(p, 0) for p in LORA_LINEAR_MODULES], dtype=torch.int32)
+        self.loaded[index] = True
+
+
+def pack_lora_linear(layers: int, shapes, max_adapters: int, max_rank: int, device) -> LoraLinearPack:
+    """An empty :class:`LoraLinearPack` for ``shapes = {module: (out, in)}``."""
+    return LoraLinearPack(layers, shapes, max_adapters, max_rank, device)
+
+
+class LoraTiles:
+    """The tile table of one forward (``mls_lora_tiles``): ``tab`` int32 -- ``[0]`` the tile count, from word 16
+    ``tile_adapter[max_tiles]``, ``tile_rows[max_tiles][16]``, ``row_flag[B * S]``."""
+
+    def __init__(self, tab: torch.Tensor, B: int, S: int, n_adapters: int, max_tiles: int):
+        self.tab, self.B, self.S, self.n_adapters, self.max_tiles = tab, B, S, n_adapters, max_tiles
+
+    @property
+    def rows(self) -> int:
+        return self.B * self.S
+
+
+def lora_max_tiles(B: int, S: int, n_adapters: int) -> int:
+    """The host worst case every grid is sized for: ``min(B, n_adapters + B // 16)`` at S == 1."""
+    return int(lib().mls_lora_max_tiles(int(B), int(S), int(n_adapters)))
+
+
+def lora_table_elems(B: int, S: int, n_adapters: int) -> int:
+    return int(lib().mls_lora_table_elems(int(B), int(S), int(n_adapters)))
+
+
+def lora_tiles(lora_slot: torch.Tensor, B: int, S: int, slot_ids: Optional[torch.Tensor] = None, *, n_adapters: int,
+               out: Optional[torch.Tensor] = None) -> LoraTiles:
+    """Group the step's rows by adapter, once per forward: S == 1 by a counting sort (adapters ascending, rows
+    ascending, 16 per tile), S > 1 as runs of <= 16 rows of a sequence.  Reads device arrays only: a captured
+    graph regroups on every replay.  ``out``: int32, ``lora_table_elems(B, S, n_adapters)`` words."""
+    dev = lora_slot.device
+    _need(lora_slot, "lora_slot", torch.int32, dev)
+    if slot_ids is not None:
+        _need(slot_ids, "slot_ids", torch.int32, dev)
+        if slot_ids.numel() != B:
+            raise ValueError(f"slot_ids has {slot_ids.numel()} entries for {B} sequences")
+    elif B > lora_slot.numel():
+        raise ValueError(f"{B} sequences but lora_slot has {lora_slot.numel()} slots")
+    need = lora_table_elems(B, S, n_adapters)
+    if need <= 0:
+        raise ValueError(f"lora_tiles: {B} x {S} rows are more than the LoRA kernels take")
+    if out is None:
+        out = torch.empty(need, device=dev, dtype=torch.int32)
+    _need(out, "out", torch.int32, dev)
+    if out.numel() < need:
+        raise ValueError(f"the tile table holds {out.numel()} words, {B} x {S} rows need {need}")
+    check(lib().mls_lora_tiles(lora_slot.data_ptr(), _ptr(slot_ids), out.data_ptr(), out.numel() * 4, B, S,
+                               int(n_adapters), lora_slot.numel(), stream_ptr(dev)), "mls_lora_tiles")
+    return LoraTiles(out, B, S, int(n_adapters), lora_max_tiles(B, S, n_adapters))
+
+
+def lora_linear_split(tiles: LoraTiles, K: int, acap: int) -> int:
+    """:func:`lora_split` over the table's worst-case tile count (host values only)."""
+    return lora_split(tiles.max_tiles, 1, K, acap)
+
+
+def _ll_args(pack: LoraLinearPack, group: str, layer: int, tiles: LoraTiles, x: torch.Tensor, workspace, nsplit: int):
+    dev = x.device
+    if group not in pack.dims:
+        raise ValueError(f"the pack holds no {group} adapters (it holds {sorted(pack.dims)})")
+    N, K, acap = pack.dims[group]
+    _need(x, "x", torch.bfloat16, dev)
+    if x.dim() != 2 or tuple(x.shape) != (tiles.rows, K):
+        raise ValueError(f"x is {tuple(x.shape)}, expected ({tiles.rows}, {K})")
+    if pack.seg.device != dev or tiles.tab.device != dev:
+        raise ValueError(f"pack on {pack.seg.device}, tile table on {tiles.tab.device}, the rows on {dev}")
+    if tiles.n_adapters != pack.max_adapters:
+        raise ValueError(f"the tile table was built for {tiles.n_adapters} adapters, the pack holds {pack.max_adapters}")
+    if not 0 <= int(layer) < pack.layers:
+        raise ValueError(f"layer {layer} outside the pack's {pack.layers}")
+    nsplit = int(nsplit) or lora_linear_split(tiles, K, acap)
+    if nsplit < 1 or nsplit > 64 or K % (nsplit * LORA_K_GRAN):
+        raise ValueError(f"nsplit {nsplit}: K {K} must be a multiple of nsplit * {LORA_K_GRAN}")
+    need = pack.workspace_elems(tiles.max_tiles, nsplit, group)
+    if workspace is None:
+        workspace = torch.empty(need, device=dev, dtype=torch.float32)
+    _need(workspace, "workspace", torch.float32, dev)
+    if workspace.numel() < need:
+        raise ValueError(f"workspace holds {workspace.numel()} floats, {nsplit} splits of {tiles.max_tiles} tiles "
+                         f"need {need}")
+    return N, K, acap, nsplit, workspace
+
+
+def _ll_shrink(pack, group, layer, tiles, x, ws, K, acap, nsplit, normed):
+    s0 = LORA_LINEAR_MODULES.index(_LL_GROUPS[group][0])
+    check(lib().mls_lora_shrink_x(x.data_ptr(), K, pack.A[group][layer].data_ptr(), pack.seg.data_ptr(),
+                                  tiles.tab.data_ptr(), ws.data_ptr(), ws.numel() * 4, tiles.rows, K, acap, pack.bcap,
+                                  s0, len(_LL_GROUPS[group]), pack.max_adapters, tiles.max_tiles, nsplit, int(normed),
+                                  stream_ptr(x.device)), "mls_lora_shrink_x")
+    return s0
+
+
+def lora_linear_(y: torch.Tensor, x: torch.Tensor, pack: LoraLinearPack, module: str, layer: int, tiles: LoraTiles, *,
+                 normed: bool = False, eps: float = 1e-5, workspace: Optional[torch.Tensor] = None,
+                 nsplit: int = 0, ct: int = 0) -> torch.Tensor:
+    """``y[m] += s B[a] (A[a] . x[m])`` in place on the rows ``tiles`` gathered, ``module`` ``"o"`` or ``"down"``
+    of layer ``layer``: ``mls_lora_shrink_x`` then ``mls_lora_expand_add``.  ``normed``: x is the residual and the
+    product takes ``RMSNorm(x) * gain`` (the gain folded into A at load).  Rows outside every tile are untouched.
+    ``ct``: 64-column groups a block of the expand walks with one staged operand (0: the kernel's rule of N)."""
+    if module not in ("o", "down"):
+        raise ValueError(f"lora_linear_ serves o and down, got {module!r} (gate / up: lora_gate_up)")
+    _need(y, "y", torch.bfloat16, x.device)
+    N, K, acap, nsplit, ws = _ll_args(pack, module, layer, tiles, x, workspace, nsplit)
+    if y.dim() != 2 or tuple(y.shape) != (tiles.rows, N):
+        raise ValueError(f"y is {tuple(y.shape)}, expected ({tiles.rows}, {N})")
+    s0 = _ll_shrink(pack, module, layer, tiles, x, ws, K, acap, nsplit, normed)
+    check(lib().mls_lora_expand_add(y.data_ptr(), N, pack.B[module][layer].data_ptr(), pack.seg.data_ptr(),
+                                    pack.scale.data_ptr(), tiles.tab.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                    tiles.rows, N, K, float(eps), pack.bcap, s0, pack.max_adapters, tiles.max_tiles,
+                                    nsplit, int(normed), int(ct), stream_ptr(x.device)), "mls_lora_expand_add")
+    return y
+
+
+def lora_gate_up(gu_pre: torch.Tensor, x: torch.Tensor, pack: LoraLinearPack, layer: int, tiles: LoraTiles, *,
+                 normed: bool = True, eps: float = 1e-5, workspace: Optional[torch.Tensor] = None, nsplit: int = 0,
+                 ct: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``silu(g + dg) * (u + du)`` ``[M, I]`` from the pre-activation gate / up ``gu_pre [M, 2I]`` in the
+    interleave-by-8 layout (:func:`interleave_gate_up`), the deltas ``s B (A . RMSNorm(x) * gain)`` added on the
+    fp32 accumulator.  Every row is written; rows outside every tile get :func:`silu_mul_interleaved`'s result,
+    bit for bit."""
+    _need(gu_pre, "gu_pre", torch.bfloat16, x.device)
+    N, K, acap, nsplit, ws = _ll_args(pack, "gate_up", layer, tiles, x, workspace, nsplit)
+    if gu_pre.dim() != 2 or tuple(gu_pre.shape) != (tiles.rows, N):
+        raise ValueError(f"gu_pre is {tuple(gu_pre.shape)}, expected ({tiles.rows}, {N})")
+    if out is None:
+        out = torch.empty(tiles.rows, N // 2, device=x.device, dtype=torch.bfloat16)
+    _need(out, "out", torch.bfloat16, x.device)
+    if tuple(out.shape) != (tiles.rows, N // 2) or out.data_ptr() == gu_pre.data_ptr():
+        raise ValueError(f"out must be a separate ({tiles.rows}, {N // 2}) tensor")
+    s0 = _ll_shrink(pack, "gate_up", layer, tiles, x, ws, K, acap, nsplit, normed)
+    check(lib().mls_lora_expand_silu(gu_pre.data_ptr(), out.data_ptr(), pack.B["gate_up"][layer].data_ptr(),
+                                     pack.seg.data_ptr(), pack.scale.data_ptr(), tiles.tab.data_ptr(), ws.data_ptr(),
+                                     ws.numel() * 4, tiles.rows, N, K, float(eps), pack.bcap, s0, pack.max_adapters,
+                                     tiles.max_tiles, nsplit, int(normed), int(ct), stream_ptr(x.device)),
+          "mls_lora_expand_silu")
+    return out

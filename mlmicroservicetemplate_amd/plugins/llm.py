@@ -86,10 +86,10 @@ class LlamaPlugin(ModelPlugin):
         self.model = llama.LlamaTP(params, cfg, tp=tp, rank=ctx.rank, comm=llama.TPComm(None, tp, device=dev), backend=backend,
                                    device=dev, max_batch=max_batch, max_seq=max_seq, kv_pages=kv_pages,
                                    kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_prefill=kv_prefill, lora=lora_kw)
-        for index, (name, path) in enumerate(lora_paths.items()):  # every rank reads the adapter and keeps its B rows
+        for index, (name, path) in enumerate(lora_paths.items()):  # every rank reads the adapter and keeps its share (load_adapter)
             from ..utils.checkpoint import load_lora_adapter
 
-            tensors, acfg = load_lora_adapter(path, cfg.layers)
+            tensors, acfg = load_lora_adapter(path, cfg.layers, targets=lora_kw.get("targets", "qkv"))
             self.model.load_adapter(index, tensors, acfg)
             self.adapters[name] = index
         if self.speculate:  # refused at start-up on the lockstep path too (the engine below checks for itself)
@@ -130,7 +130,8 @@ class LlamaPlugin(ModelPlugin):
 
     @staticmethod
     def parse_lora(extra: dict, prefix_cache: bool = False):
-        """MODEL_CONFIG ``lora: {name: PEFT directory, ...}`` (+ optional ``lora_max_rank``, default 64):
+        """MODEL_CONFIG ``lora: {name: PEFT directory, ...}`` (+ optional ``lora_max_rank``, default 64, and
+        ``lora_targets``: ``qkv`` (default) or ``all``, the projections an adapter may target):
         ``(paths, LlamaTP's lora=...)``, ``({}, None)`` without adapters.  Refused together with
         ``prefix_cache: true`` (cached pages hold adapter-specific K / V)."""
         paths = extra.get("lora") or {}
@@ -141,7 +142,12 @@ class LlamaPlugin(ModelPlugin):
         if prefix_cache:
             raise ValueError("prefix_cache: true is not available together with lora adapters (cached pages hold "
                              "adapter-specific K / V; the prefix index is not keyed by adapter)")
-        return dict(paths), {"max_adapters": len(paths), "max_rank": int(extra.get("lora_max_rank", 64))}
+        kw = {"max_adapters": len(paths), "max_rank": int(extra.get("lora_max_rank", 64))}
+        if "lora_targets" in extra:
+            if extra["lora_targets"] not in ("qkv", "all"):
+                raise ValueError(f"lora_targets must be qkv or all, got {extra['lora_targets']!r}")
+            kw["targets"] = extra["lora_targets"]
+        return dict(paths), kw
 
     @staticmethod
     def parse_prefix_cache(extra: dict) -> bool:

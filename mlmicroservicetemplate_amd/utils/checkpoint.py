@@ -129,18 +129,22 @@ _PEFT_KEY = r"(?:^|\.)layers\.(\d+)\.(self_attn|mlp)\.(\w+)\.lora_(A|B)(?:\.[^.]
 _NATIVE_KEY = r"^l(\d+)\.(\w+)\.lora_(A|B)$"
 
 
-def load_lora_adapter(path: str, layers: int) -> Tuple[Dict[str, torch.Tensor], dict]:
+def load_lora_adapter(path: str, layers: int, targets: str = "qkv") -> Tuple[Dict[str, torch.Tensor], dict]:
     """A LoRA adapter from a PEFT directory: ``adapter_config.json`` + ``adapter_model.safetensors`` (safetensors
     only: a directory that holds just ``adapter_model.bin`` is refused, nothing is unpickled).  Returns
     ``(tensors, config)`` for ``LlamaTP.load_adapter``: tensors under the native names
-    ``l{i}.{q,k,v}.lora_A`` / ``.lora_B`` (PEFT's ``...layers.{i}.self_attn.{q,k,v}_proj.lora_{A,B}.weight``,
-    with or without an adapter name before ``.weight``, or the native names themselves), fp32.  The config is
-    validated (``models.llama.parse_lora_config``) and every tensor's rank against it; a tensor of a module
-    other than q / k / v, a layer outside the model, or a missing A / B of a target module is an error."""
+    ``l{i}.{module}.lora_A`` / ``.lora_B`` (PEFT's ``...layers.{i}.{self_attn,mlp}.{module}_proj.lora_{A,B}.weight``,
+    with or without an adapter name before ``.weight``, or the native names themselves), fp32.  ``targets``: the
+    model's (``lora={"targets": ...}``) -- ``"qkv"`` serves the modules q, k, v; ``"all"`` also ``self_attn.o_proj``,
+    ``mlp.gate_proj``, ``mlp.up_proj`` and ``mlp.down_proj`` (native: o, gate, up, down).  The config is validated
+    (``models.llama.parse_lora_config``) and every tensor's rank against it; a tensor of a module outside
+    ``targets``, a layer outside the model, or a missing A / B of a target module is an error."""
     import json
     import re
 
-    from ..models.llama import LORA_TARGETS, parse_lora_config
+    from ..models.llama import LORA_TARGETS, LORA_TARGETS_ALL, parse_lora_config
+
+    served = LORA_TARGETS if targets == "qkv" else LORA_TARGETS_ALL
 
     cfg_file = os.path.join(path, "adapter_config.json")
     st_file = os.path.join(path, "adapter_model.safetensors")
@@ -153,24 +157,27 @@ def load_lora_adapter(path: str, layers: int) -> Tuple[Dict[str, torch.Tensor], 
         raise CheckpointError(f"{path!r}: no adapter_model.safetensors")
     with open(cfg_file) as f:
         config = json.load(f)
-    mods, r, _alpha, _rs = parse_lora_config(config)
+    mods, r, _alpha, _rs = parse_lora_config(config, targets=targets)
     ck = Checkpoint(st_file)
     tensors: Dict[str, torch.Tensor] = {}
     for key in ck.keys():
         m = re.search(_PEFT_KEY, key)
         if m is not None:
             i, module, ab = int(m.group(1)), m.group(3), m.group(4)
-            if m.group(2) != "self_attn" or module not in LORA_TARGETS:
-                raise CheckpointError(f"{path}: {key!r} adapts {module}, which is not served: only q_proj, k_proj and "
-                                      f"v_proj are")
-            p = LORA_TARGETS[module]
+            block = "mlp" if module in ("gate_proj", "up_proj", "down_proj") else "self_attn"
+            if m.group(2) != block or module not in served:
+                raise CheckpointError(f"{path}: {key!r} adapts {module}, which is not served: only "
+                                      f"{', '.join(list(served)[:-1])} and {list(served)[-1]} are")
+            p = served[module]
         else:
             m = re.match(_NATIVE_KEY, key)
             if m is None:
-                raise CheckpointError(f"{path}: {key!r} is not a LoRA tensor of a q / k / v projection")
+                raise CheckpointError(f"{path}: {key!r} is not a LoRA tensor of a {' / '.join(served.values())} "
+                                      f"projection")
             i, p, ab = int(m.group(1)), m.group(2), m.group(3)
-            if p not in LORA_TARGETS.values():
-                raise CheckpointError(f"{path}: {key!r} adapts {p}, which is not served: only q, k and v are")
+            if p not in served.values():
+                raise CheckpointError(f"{path}: {key!r} adapts {p}, which is not served: only "
+                                      f"{', '.join(list(served.values())[:-1])} and {list(served.values())[-1]} are")
         if p not in mods:
             raise CheckpointError(f"{path}: {key!r} is outside the config's target_modules {list(mods)}")
         if not 0 <= i < layers:

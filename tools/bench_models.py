@@ -328,10 +328,15 @@ def bench_llama_lora(args):
     kw = dict(backend="fused", device=dev, max_batch=max(max(args.batches), 8), max_seq=args.max_seq,
               kv_pages=args.kv_pages, kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, kv_prefill=args.kv_prefill)
     plain = LlamaTP(p, cfg, **kw)
-    m = LlamaTP(p, cfg, lora={"max_adapters": args.lora, "max_rank": args.lora_rank}, **kw)
+    lora = {"max_adapters": args.lora, "max_rank": args.lora_rank}
+    mods = ("q", "k", "v")
+    if args.lora_targets == "all":  # adapters on all seven projections: the layer tail runs csrc/lora_linear.hip
+        lora["targets"], mods = "all", ops.reference.LORA_ALL_MODULES
+    m = LlamaTP(p, cfg, lora=lora, **kw)
     for a in range(args.lora):
-        m.load_adapter(a, *random_lora_adapter(cfg, args.lora_rank, seed=100 + a, device=dev))
+        m.load_adapter(a, *random_lora_adapter(cfg, args.lora_rank, seed=100 + a, modules=mods, device=dev))
     head = {"bench": "llama3-8b-lora", "adapters": args.lora, "rank": args.lora_rank, "weight_dtype": args.weight_dtype,
+            "targets": args.lora_targets,
             "kv_dtype": args.kv_dtype, "kv_pages": args.kv_pages}
     print(json.dumps(dict(head, init_s=round(time.time() - t0, 1))), flush=True)
     mixes = {"none": lambda b: -1, "same": lambda b: 0, "distinct": lambda b: b % args.lora}
@@ -362,8 +367,9 @@ def bench_llama_lora(args):
                 dt = timed(step, args.steps)
                 if rep:
                     res[name].append(dt * 1e3)
-        print(json.dumps(dict(head, what="decode", batch=B, ctx=S, **{f"{k}_ms_per_step": round(statistics.median(v), 4)
-                                                                      for k, v in res.items()})), flush=True)
+        print(json.dumps(dict(head, what="decode", batch=B, ctx=S, reps=args.reps,
+                              **{f"{k}_ms_per_step": round(statistics.median(v), 4) for k, v in res.items()},
+                              **{f"{k}_spread_ms": round(max(v) - min(v), 4) for k, v in res.items()})), flush=True)
     B = 8
     ids = torch.randint(1000, 100000, (B, S), device=dev, dtype=torch.int32)
     lens = torch.full((B,), S, device=dev, dtype=torch.int32)
@@ -375,8 +381,9 @@ def bench_llama_lora(args):
             dt = timed(lambda model=model: model.step(ids, pos, lens, decode=False, k=1), 3)
             if rep:
                 res[name].append(dt * 1e3)
-    print(json.dumps(dict(head, what="prefill", batch=B, prompt=S, **{f"{k}_ms": round(statistics.median(v), 3)
-                                                                      for k, v in res.items()})), flush=True)
+    print(json.dumps(dict(head, what="prefill", batch=B, prompt=S, reps=args.reps,
+                          **{f"{k}_ms": round(statistics.median(v), 3) for k, v in res.items()},
+                          **{f"{k}_spread_ms": round(max(v) - min(v), 3) for k, v in res.items()})), flush=True)
     # the two launches of one layer alone, every row on its own adapter (distinct) / on adapter 0 (same)
     pack, N = m.lora_pack, m.qkv_width
     for rows_B, rows_S in [(b, 1) for b in args.batches] + [(8, S)]:
@@ -590,6 +597,8 @@ def main():
     ap.add_argument("--prefill-chunk", type=int, default=0, help="llama --shared-prefix: chunked prefill width")
     ap.add_argument("--lora", type=int, default=0, help="llama: N random LoRA adapters on q/k/v (0: off)")
     ap.add_argument("--lora-rank", type=int, default=16, help="llama --lora: their rank")
+    ap.add_argument("--lora-targets", choices=["qkv", "all"], default="qkv",
+                    help="llama --lora: adapters on q/k/v, or on all seven linear projections")
     ap.add_argument("--lora-mix", nargs="+", choices=["none", "same", "distinct"], default=["none", "same", "distinct"],
                     help="llama --lora: slots on the base model / all on adapter 0 / slot b on adapter b %% N")
     ap.add_argument("--reps", type=int, default=3, help="llama --shared-prefix: alternations of the arms")
