@@ -532,7 +532,8 @@ class LlamaTP:
     def __init__(self, params: Dict[str, torch.Tensor], cfg: LlamaConfig, tp: int = 1, rank: int = 0,
                  comm: Optional[TPComm] = None, backend: str = "reference", device="cpu", max_batch: int = 8,
                  max_seq: int = 1024, top_k_max: int = 50, kv_pages: int = 0, kv_dtype: str = "bf16",
-                 weight_dtype: str = "bf16", kv_prefill: str = "rows", lora: Optional[dict] = None):
+                 weight_dtype: str = "bf16", kv_prefill: str = "rows", lora: Optional[dict] = None,
+                 w4_rows: str = "decode"):
         """``lora={"max_adapters": n, "max_rank": r}``: room for n LoRA adapters of rank <= r on the q / k / v
         projections, chosen per cache slot (:meth:`load_adapter`, :meth:`set_slot_adapter`,
         ``GenParams.adapter``); until one is loaded neither backend computes anything new.
@@ -560,6 +561,12 @@ class LlamaTP:
         ``w4_max_rows`` rows (``ops.skinny_w4``), larger steps run the bf16 rounding of the same
         weights.  Every quantised matrix needs K % 128 == 0 on this rank (row-parallel shards
         then cut K at group boundaries, so every TP degree sees the same groups).  Changes numerics.
+        ``w4_rows="all"`` (with ``weight_dtype="int4"`` only; default ``"decode"``): the fused backend keeps the
+        codes + scales and nothing else of a layer matrix, and steps above ``w4_max_rows`` rows -- prefill,
+        chunked prefill, verify steps, large decode batches -- run a gain-free RMSNorm + the tiled
+        ``ops.gemm_w4a16`` on the same codes (one launch per projection while its input stays under 2 GiB, row blocks
+        above); the two-half overlapped TP prefill is off.  The reference
+        backend, which holds the dequantised weights anyway, accepts and ignores it.
         ``weight_dtype="w8a8"``: FP8 (e4m3) layer projections with e4m3 activations -- one fp32 scale per
         output channel (``ops.reference.w8_quant``, on the weights as held: gains folded, gate / up
         interleaved on the fused backend) and one dynamic scale per activation row
@@ -579,6 +586,10 @@ class LlamaTP:
             raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
         if weight_dtype not in ("bf16", "int4", "w8a8"):
             raise ValueError(f"weight_dtype must be 'bf16', 'int4' or 'w8a8', got {weight_dtype!r}")
+        if w4_rows not in ("decode", "all"):
+            raise ValueError(f"w4_rows must be 'decode' or 'all', got {w4_rows!r}")
+        if w4_rows != "decode" and weight_dtype != "int4":
+            raise ValueError(f"w4_rows={w4_rows!r} is for weight_dtype='int4' only, got {weight_dtype!r}")
         if kv_prefill not in ("rows", "cache"):
             raise ValueError(f"kv_prefill must be 'rows' or 'cache', got {kv_prefill!r}")
         if kv_prefill == "cache" and kv_dtype != "fp8":
@@ -587,6 +598,7 @@ class LlamaTP:
         self.kv_dtype = kv_dtype
         self.kv_prefill = kv_prefill
         self.weight_dtype = weight_dtype
+        self.w4_rows = w4_rows
         self.cfg = cfg
         self.sd = shard_dims(cfg, tp, rank)
         self.tp, self.rank = tp, rank
@@ -624,6 +636,7 @@ class LlamaTP:
                 self._mlp_gain = [self.p[f"l{i}.mlp_norm"].float().clone() for i in range(cfg.layers)]
         # int4: name -> (packed codes, scales) of the layer projections (fused backend only)
         self.w4: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self.w4_n: Dict[str, int] = {}  # name -> output rows N of the matrix behind self.w4[name]
         self.w4_max_rows = self.w4_variant = 0
         if weight_dtype == "int4":
             self._check_int4_shapes()
@@ -822,8 +835,12 @@ class LlamaTP:
         for i in range(cfg.layers):
             for n in ("qkv", "o", "gate_up", "down"):
                 q, sc = R.w4_quant(self.p[f"l{i}.{n}"])
-                self.p[f"l{i}.{n}"] = R.w4_dequant(q, sc).to(torch.bfloat16)
+                if self.w4_rows == "all":  # the codes serve every row count: nothing else of the matrix stays
+                    del self.p[f"l{i}.{n}"]
+                else:
+                    self.p[f"l{i}.{n}"] = R.w4_dequant(q, sc).to(torch.bfloat16)
                 self.w4[f"l{i}.{n}"] = ops.pack_skinny_w4_codes(q, sc)
+                self.w4_n[f"l{i}.{n}"] = q.shape[0]
                 del q, sc
         # decode steps up to this many rows stream the int4 codes: the kernel's own limit (the
         # measurements behind it: llama_route.proj_tiers)
@@ -837,7 +854,7 @@ class LlamaTP:
         if self.device.type != "cuda":
             return
         names = [f"l{i}.{n}" for i in range(cfg.layers) for n in ("qkv", "o", "gate_up", "down")] + ["lm_head"]
-        names = [n for n in names if n in self.p]  # w8a8: the layer matrices live in self.w8 alone
+        names = [n for n in names if n in self.p]  # w8a8, int4 w4_rows="all": the layer matrices live as codes alone
         # Decode (<= 24 tokens per step) streams a second, granule-packed copy of every projection
         # (ops.pack_skinny: each wave reads contiguous 1 KiB granules, non-temporal): 3.4-4.5 ->
         # 4.6-6.2 TB/s on the Llama-3-8B shapes (profiles/r2_decode_packed_weight_probe.jsonl).
@@ -880,6 +897,7 @@ class LlamaTP:
             if name.rsplit(".", 1)[-1] in ("qkv", "o", "gate", "up", "gate_up", "down"):
                 held = self.w4.get(name, (w,))
                 total += sum(t.numel() * t.element_size() for t in held)
+        total += sum(t.numel() * t.element_size() for name, held in self.w4.items() if name not in self.p for t in held)
         return total
 
     def _embed(self, ids: torch.Tensor) -> torch.Tensor:
@@ -1029,7 +1047,7 @@ class LlamaTP:
         return step_route(
             B=B, S=S, decode=decode, has_past=has_past, all_rows=all_rows, tp=self.tp, hq=sd.hq, hkv=sd.hkv,
             head_dim=cfg.head_dim, hidden=cfg.hidden, have_packed=bool(self.packed), have_w4=bool(self.w4),
-            have_w8=bool(self.w8),
+            have_w8=bool(self.w8), w4_all=self.w4_rows == "all",
             have_fp8=bool(self.fp8), o_packed="l0.o" in self.packed, o_fp8="l0.o" in self.fp8, kv_fp8=self.kv_fp8,
             w4_max_rows=self.w4_max_rows, pk_fold=self.pk_fold, prefill_fold=self.prefill_fold,
             fuse_combine=self.fuse_combine, fuse_add_norm=self.fuse_add_norm, ar_fuse=self.ar_fuse,
@@ -1050,9 +1068,16 @@ class LlamaTP:
             if not tr.w8:
                 raise RuntimeError(f"{name} is held as w8a8 codes only, and the route has no w8a8 tier")
             return self._w8_proj(name)
+        if name in self.w4:
+            N = self.w4_n[name]
+            if tr.w4:
+                return lambda x, **kw: ops.skinny_w4(x, *self.w4[name], N, variant=self.w4_variant, **kw)
+            if tr.w4g:
+                return self._w4_proj(name)
+            if name not in self.p:
+                raise RuntimeError(f"{name} is held as int4 codes only, and the route has no int4 tier for {tr.rows} rows")
+            return None
         N = self.p[name].shape[0]
-        if tr.w4 and name in self.w4:
-            return lambda x, **kw: ops.skinny_w4(x, *self.w4[name], N, variant=self.w4_variant, **kw)
         if tr.fp8_for(K) and name in self.fp8:
             return lambda x, **kw: ops.skinny_fp8(x, *self.fp8[name], N, **kw)
         if tr.packed and name in self.packed:
@@ -1065,6 +1090,20 @@ class LlamaTP:
         def run(x, delta=None, resid_out=None, norm=False, act=ops.ACT_NONE, eps=1e-5, residual=None):
             xq, xs = ops.quant_rows_fp8(x, delta, resid_out, norm=norm, eps=eps)
             return ops.gemm_w8a8(xq, xs, wq, ws, N, act=act, residual=residual, workspace=self.workspace)
+
+        return run
+
+    def _w4_proj(self, name: str):
+        """``w4_rows="all"`` above ``w4_max_rows`` rows: the gain-free RMSNorm the projection's prologue would
+        be, as its own launch, then the tiled W4A16 GEMM on the codes ``ops.skinny_w4`` streams below."""
+        ops, (wq, sc), N = self.ops, self.w4[name], self.w4_n[name]
+
+        def run(x, delta=None, resid_out=None, norm=False, act=ops.ACT_NONE, eps=1e-5, residual=None):
+            if norm and delta is not None:
+                x = ops.rmsnorm(delta, self.ones, residual=x, residual_out=resid_out, eps=eps)
+            elif norm:
+                x = ops.rmsnorm(x, self.ones, eps=eps)
+            return ops.gemm_w4a16(x, wq, sc, N, act=act, residual=residual, workspace=self.workspace)
 
         return run
 

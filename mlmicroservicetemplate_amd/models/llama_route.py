@@ -20,6 +20,7 @@ class ProjTiers:
     packed: bool
     fuse: bool
     w8: bool = False  # weight_dtype="w8a8": the only copy of a layer matrix, at every row count
+    w4g: bool = False  # w4_rows="all": the int4 codes above w4_max_rows too, on the tiled ops.gemm_w4a16
 
     def fp8_for(self, K: int) -> bool:
         """The e4m3 tier for a projection of inner size K: ops.skinny_fp8 takes rows * K bf16 activations
@@ -28,8 +29,12 @@ class ProjTiers:
 
 
 def proj_tiers(rows: int, have_packed: bool, have_w4: bool, have_fp8: bool, w4_max_rows: int,
-               have_w8: bool = False) -> ProjTiers:
+               have_w8: bool = False, w4_all: bool = False) -> ProjTiers:
     return ProjTiers(
+        # w4_rows="all": the int4 codes are the only copy of a layer matrix; steps of <= w4_max_rows rows keep
+        # ops.skinny_w4 (the tier below), every larger one runs a gain-free RMSNorm + ops.gemm_w4a16 on the
+        # same codes -- no layer projection reaches ops.linear
+        w4g=w4_all and have_w4 and rows > w4_max_rows,
         # weight_dtype="w8a8": every layer projection, at every row count, is ops.quant_rows_fp8 +
         # ops.gemm_w8a8 on the e4m3 codes (the model holds nothing else of those matrices); the all-reduce
         # and the split-KV combine run as their own launches, as with int4.  Steps of <= 4 rows stay on it
@@ -91,7 +96,7 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
                o_fp8: bool, w4_max_rows: int, pk_fold: bool, prefill_fold: bool, fuse_combine: bool,
                fuse_add_norm: bool, ar_fuse: bool, tp_overlap: bool, verify_attn: str, spec_max_tokens: int,
                dec_chunk: int, ar_fusable: bool, capturing: bool, kv_fp8: bool = False,
-               have_w8: bool = False, lora_tail: bool = False) -> StepRoute:
+               have_w8: bool = False, lora_tail: bool = False, w4_all: bool = False) -> StepRoute:
     """``have_*``: the model holds such copies at all; ``o_packed`` / ``o_fp8``: of ``l0.o``;
     ``ar_fusable``: the comm's one-shot all-reduce can ride in a GEMM producing ``B * S * hidden``
     outputs; ``capturing``: the current stream is capturing a graph.  The rest are the model's
@@ -99,15 +104,16 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
     ``lora_tail``: a loaded LoRA adapter targets o, gate, up or down -- a delta cannot pass through the split-KV
     combine prologue, the fused all-reduce, ``linear_add_rmsnorm`` or the overlapped TP prefill, so those are
     off and the tail runs o -> + delta -> gate / up without activation -> ``lora_gate_up`` -> down -> + delta
-    (csrc/lora_linear.hip).  Off (q / k / v adapters only, or none): every decision below is as before."""
+    (csrc/lora_linear.hip).  Off (q / k / v adapters only, or none): every decision below is as before.
+    ``w4_all``: ``w4_rows="all"`` -- the int4 codes serve every row count (``ProjTiers.w4g``)."""
     T = B * S
-    proj = proj_tiers(T, have_packed, have_w4, have_fp8, w4_max_rows, have_w8)
+    proj = proj_tiers(T, have_packed, have_w4, have_fp8, w4_max_rows, have_w8, w4_all)
     # TP = 1: the residual add rides in the o / down epilogues (h = r + a Wo^T, r' = h + g Wd^T), so
     # the next pre-norm GEMM reads one activation stream instead of two (r + delta) and writes no
     # residual copy.  With TP > 1 the add has to wait for the all-reduce.  prefill_fold: prefill at
     # TP = 1 with the residual add in the o / down GEMM epilogues too (the following RMSNorm then reads
     # one stream and writes one: 64 instead of 128 B per element)
-    fold = tp == 1 and (((proj.packed or proj.w4 or proj.w8) and pk_fold) or (not decode and prefill_fold))
+    fold = tp == 1 and (((proj.packed or proj.w4 or proj.w8 or proj.w4g) and pk_fold) or (not decode and prefill_fold))
     # decode: the o-projection merges the split-KV partials in its prologue (one launch instead of
     # two) while every block's share of partials is small -- B x local q heads <= 32: one emulated
     # TP = 8 rank 1.166 -> 1.125 ms/token at batch 1, 1.294 -> 1.254 at 4; TP = 1 batch 1 level,
@@ -124,6 +130,7 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
     # projection (ops.linear_add_rmsnorm) -- one launch instead of reduce + RMSNorm, bit-identical.
     # A projection it cannot take (no split on that shape) runs the plain pair.
     fuse_rn = tp == 1 and not proj.packed and not proj.fuse and not fold and fuse_add_norm and not proj.w8
+    fuse_rn = fuse_rn and not w4_all  # linear_add_rmsnorm reads the bf16 matrix, which w4_rows="all" does not hold
     # a verify step (all_rows: every row's candidates) of a few positions per sequence: its attention
     # runs split-KV on the matrix cores with the T positions x G heads of a KV head on one MFMA's lane
     # columns (ops.decode_attention_multi); MLS_VERIFY_ATTN=ctx keeps the chunk kernel (the A/B arm).
@@ -143,5 +150,7 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
     chunk = dec_chunk if dec_chunk > 0 else (128 if B >= 32 else 64)
     if lora_tail:
         combine = ar = fuse_rn = overlap = False
+    if w4_all:  # the two-half TP prefill was not run in this mode: the plain layer loop serves it
+        overlap = False
     return StepRoute(proj=proj, fold=bool(fold), fuse_combine=bool(combine), ar_fuse=bool(ar), fuse_rn=bool(fuse_rn),
                      multi=bool(multi), overlap=bool(overlap), dec_chunk=chunk, lora_tail=bool(lora_tail))

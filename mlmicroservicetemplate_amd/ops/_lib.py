@@ -121,6 +121,8 @@ _SIGS = {
     "mls_skinny_fp8": [P, P, P, P, P, P, P, P, I, I, I, I, I, F, I, P],
     "mls_skinny_w4": [P, P, P, P, P, P, P, P, I, I, I, I, I, F, I, P],
     "mls_skinny_w4_num_variants": [],
+    "mls_gemm_w4a16": [P, P, P, P, P, P, I, I, I, I, I, I, P, _c.c_longlong, P, I, P],
+    "mls_gemm_w4a16_num_variants": [],
     "mls_gemm_w8a8": [P, P, P, P, P, P, P, I, I, I, I, I, I, P, _c.c_longlong, P, I, P],
     "mls_gemm_w8a8_num_variants": [],
     "mls_quant_rows_fp8": [P, P, P, P, P, I, I, I, F, P],

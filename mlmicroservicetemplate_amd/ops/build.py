@@ -67,8 +67,13 @@ def _flags(debug: bool) -> List[str]:
     return CXXFLAGS + (["-DMLS_DEBUG"] if debug else [])
 
 
+# per-source flags: gemm_w4.hip's expansion and fold are runs of independent fp32 FMAs -- selected as scalar v_fma_f32,
+# never paired into packed-fp32 ops (register report with / without: docs/PERF_NOTES.md, "W4A16 at every row count")
+SRC_FLAGS = {"gemm_w4.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def _compile(src: str, hdr_hash: str, obj_dir: str, verbose: bool, debug: bool = False) -> str:
-    flags = _flags(debug)
+    flags = _flags(debug) + SRC_FLAGS.get(os.path.basename(src), [])
     key = _digest([src], hdr_hash + " ".join(flags))
     obj = os.path.join(obj_dir, os.path.basename(src).replace(".hip", f".{key}.o"))
     if os.path.exists(obj):

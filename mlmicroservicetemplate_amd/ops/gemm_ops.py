@@ -536,6 +536,73 @@ def skinny_w4(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, N: int, *
     return out
 
 
+W4_GEMM_CFGS = {1: (64, 128), 2: (128, 128), 3: (256, 128), 4: (64, 128), 5: (128, 128)}  # variant -> (BM, BN)
+W4_GEMM_VARIANTS = 6  # tiles of csrc/gemm_w4.hip (0: by shape; 4 / 5: 1 / 2 with the other nibble expansion)
+_W4_WORKSPACE: Dict[int, StreamWorkspace] = {}
+
+
+def gemm_w4a16(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, N: int, *, act=ACT_NONE,
+               bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None, variant: int = 0, splitk: int = 0,
+               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """W4A16 projection at any row count (csrc/gemm_w4.hip): ``act(x @ dequant(W)^T + bias) (+ residual)`` as bf16
+    ``[M, N]`` with ``(wq, scales)`` from :func:`pack_skinny_w4` -- the copy :func:`skinny_w4` streams for <= 32
+    rows; ``act="silu_mul"``: gate / up rows interleaved in groups of 8 (:func:`interleave_gate_up`), output
+    ``[M, N / 2]``.  Any M >= 1 (one launch while ``x`` stays under 2 GiB, row blocks of launches above), N % 16 ==
+    0, K % 128 == 0, N K / 2 < 2 GiB.  ``variant``: the tile (:data:`W4_GEMM_CFGS`, 0: by
+    shape); ``splitk``: K splits (<= K / 128, uneven allowed) combined inside the launch, deterministically (0:
+    the launcher's pick), through fp32 slabs in ``workspace`` (default: a per-stream buffer of this module)."""
+    dev = x.device
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or not x.is_contiguous():
+        raise ValueError("gemm_w4a16: x contiguous bf16 [M, K]")
+    M, K = x.shape
+    N = int(N)
+    if M < 1 or N < 1 or K % 128 or N % 16:
+        raise ValueError(f"gemm_w4a16: M >= 1, N ({N}) % 16 == 0, K ({K}) % 128 == 0")
+    if not 0 <= int(variant) < W4_GEMM_VARIANTS:
+        raise ValueError(f"gemm_w4a16: variant in 0..{W4_GEMM_VARIANTS - 1}")
+    _w8_bytes(wq, "wq", dev, N * K // 2)
+    if (scales.dtype != torch.bfloat16 or scales.device != dev or not scales.is_contiguous()
+            or scales.numel() * 128 != N * K):
+        raise ValueError(f"scales: contiguous bf16 of {N * K // 128} elements on {dev}")
+    code = _act(act)
+    if code not in (ACT_NONE, ACT_SILU_MUL):
+        raise ValueError("gemm_w4a16: act none or silu_mul")
+    if bias is not None:
+        _w8_f32(bias, "bias", dev, N)
+    if residual is not None:
+        if code == ACT_SILU_MUL:
+            raise ValueError("silu_mul takes no residual")
+        _w8_bf16(residual, "residual", dev, (M, N))
+    n_out = N // 2 if code == ACT_SILU_MUL else N
+    if out is None:
+        out = torch.empty(M, n_out, device=dev, dtype=torch.bfloat16)
+    else:
+        _w8_bf16(out, "out", dev, (M, n_out))
+    if workspace is None:
+        pool = _W4_WORKSPACE.get(dev.index or 0)
+        if pool is None:
+            # one resident wave of split units x the 128 x 128 tile: 256 x 16k fp32, twice
+            pool = _W4_WORKSPACE[dev.index or 0] = StreamWorkspace(8 << 20, dev)
+        workspace = pool.get()
+    elif workspace.dtype != torch.float32 or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("workspace: contiguous fp32 on the operands' device")
+    rows = ((1 << 31) - 1) // (K * 2) // 256 * 256  # the kernel's offsets into x are 32-bit: larger M runs in row blocks
+    if int(splitk) > 1:
+        bm, bn = W4_GEMM_CFGS[int(variant) or 1]  # variant 0 runs tile 1 at every M
+        if int(splitk) > K // 128 or -(-min(M, rows) // bm) * -(-N // bn) * int(splitk) * bm * bn > workspace.numel():
+            raise ValueError("gemm_w4a16: splitk <= K / 128 and slabs that fit the workspace")
+    for r0 in range(0, M, rows):  # one launch, unless x is 2 GiB or more
+        r1 = min(M, r0 + rows)
+        rc = lib().mls_gemm_w4a16(x[r0:r1].data_ptr(), wq.data_ptr(), scales.data_ptr(), _ptr(bias),
+                                  None if residual is None else residual[r0:r1].data_ptr(), out[r0:r1].data_ptr(),
+                                  r1 - r0, N, K, code, int(variant), int(splitk), workspace.data_ptr(),
+                                  workspace.numel(), split_counters(workspace).data_ptr(), SPLIT_COUNTER_ELEMS,
+                                  stream_ptr(dev))
+        check(rc, "mls_gemm_w4a16")
+    return out
+
+
 W8A8_CFGS = {1: (256, 256), 2: (256, 128), 3: (128, 128), 4: (64, 128), 5: (32, 128)}  # variant -> (BM, BN)
 W8A8_VARIANTS = 6  # launch shapes of csrc/gemm_w8a8.hip (0: the launcher's pick; 4 / 5: decode-shaped, split-K)
 _W8_WORKSPACE: Dict[int, StreamWorkspace] = {}

@@ -51,6 +51,7 @@ class LlamaPlugin(ModelPlugin):
         s = ctx.settings
         extra = s.model_yaml() if hasattr(s, "model_yaml") else {}
         weight_dtype = self.parse_weight_dtype(extra)  # before any weight is read or allocated
+        w4_rows = self.parse_w4_rows(extra, weight_dtype)
         self.speculate, self.speculate_ngram = self.parse_speculate(extra)
         self.speculate_device = self.parse_speculate_device(extra, self.speculate)
         self.prefix_cache = self.parse_prefix_cache(extra)
@@ -85,7 +86,8 @@ class LlamaPlugin(ModelPlugin):
             kv_pages = int(-mdist.max_over_ranks(-float(kv_pages)))
         self.model = llama.LlamaTP(params, cfg, tp=tp, rank=ctx.rank, comm=llama.TPComm(None, tp, device=dev), backend=backend,
                                    device=dev, max_batch=max_batch, max_seq=max_seq, kv_pages=kv_pages,
-                                   kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_prefill=kv_prefill, lora=lora_kw)
+                                   kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_prefill=kv_prefill, lora=lora_kw,
+                                   w4_rows=w4_rows)
         for index, (name, path) in enumerate(lora_paths.items()):  # every rank reads the adapter and keeps its share (load_adapter)
             from ..utils.checkpoint import load_lora_adapter
 
@@ -114,8 +116,8 @@ class LlamaPlugin(ModelPlugin):
                 self.engine.start()
         self.kv_pages = kv_pages
         logger.info("llama ready: tp=%d rank=%d backend=%s device=%s kv_dtype=%s kv_prefill=%s kv_bytes_per_token=%d "
-                    "weight_dtype=%s layer_weight_bytes=%d prefix_cache=%s", tp, ctx.rank, backend, dev, kv_dtype,
-                    kv_prefill, self.kv_page_bytes(cfg, tp, backend, kv_dtype) // 64, weight_dtype,
+                    "weight_dtype=%s w4_rows=%s layer_weight_bytes=%d prefix_cache=%s", tp, ctx.rank, backend, dev,
+                    kv_dtype, kv_prefill, self.kv_page_bytes(cfg, tp, backend, kv_dtype) // 64, weight_dtype, w4_rows,
                     self.model.layer_weight_bytes(), self.prefix_cache)
 
     @staticmethod
@@ -127,6 +129,18 @@ class LlamaPlugin(ModelPlugin):
         if wd not in ("bf16", "int4", "w8a8"):
             raise ValueError(f"weight_dtype must be 'bf16', 'int4' or 'w8a8', got {wd!r}")
         return wd
+
+    @staticmethod
+    def parse_w4_rows(extra: dict, weight_dtype: str) -> str:
+        """MODEL_CONFIG ``w4_rows`` (with ``weight_dtype: int4`` only): ``decode`` (default: the codes serve steps
+        of <= 32 rows, a bf16 copy the rest) | ``all`` (the codes serve every row count and are all the model
+        holds of a layer matrix; :class:`~..models.llama.LlamaTP`)."""
+        rows = str(extra.get("w4_rows", "decode"))
+        if rows not in ("decode", "all"):
+            raise ValueError(f"w4_rows must be 'decode' or 'all', got {rows!r}")
+        if rows != "decode" and weight_dtype != "int4":
+            raise ValueError(f"w4_rows: {rows} is for weight_dtype: int4 only, got {weight_dtype!r}")
+        return rows
 
     @staticmethod
     def parse_lora(extra: dict, prefix_cache: bool = False):
