@@ -533,7 +533,7 @@ class LlamaTP:
                  comm: Optional[TPComm] = None, backend: str = "reference", device="cpu", max_batch: int = 8,
                  max_seq: int = 1024, top_k_max: int = 50, kv_pages: int = 0, kv_dtype: str = "bf16",
                  weight_dtype: str = "bf16", kv_prefill: str = "rows", lora: Optional[dict] = None,
-                 w4_rows: str = "decode"):
+                 w4_rows: str = "decode", w8_decode: str = "tile"):
         """``lora={"max_adapters": n, "max_rank": r}``: room for n LoRA adapters of rank <= r on the q / k / v
         projections, chosen per cache slot (:meth:`load_adapter`, :meth:`set_slot_adapter`,
         ``GenParams.adapter``); until one is loaded neither backend computes anything new.
@@ -581,7 +581,13 @@ class LlamaTP:
         all-reduce and the split-KV combine run as their own launches.  Every layer matrix needs
         K % 128 == 0 and N % 16 == 0 on this rank (``ValueError`` otherwise: nothing falls back).  Changes
         numerics (e4m3 keeps 3 mantissa bits of weights AND activations); at TP > 1 a row-parallel projection
-        quantises each rank's K slice with its own row scale, so logits differ slightly from TP = 1."""
+        quantises each rank's K slice with its own row scale, so logits differ slightly from TP = 1.
+        ``w8_decode="skinny"`` (with ``weight_dtype="w8a8"`` only; default ``"tile"``): fused-backend steps of
+        <= ``self.w8_skinny_rows`` (16) rows run the weight-streaming ``ops.skinny_w8`` on the same codes -- one
+        launch with the row quantiser in its prologue where ``ops.skinny_w8_fused_fits`` holds,
+        ``ops.quant_rows_fp8`` + ``ops.skinny_w8_codes`` otherwise; larger steps keep ``ops.gemm_w8a8``.  Same
+        rule and codes, so the numerics are ``tile``'s up to fp32 summation order.  The reference backend accepts
+        and ignores it."""
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
         if weight_dtype not in ("bf16", "int4", "w8a8"):
@@ -590,6 +596,10 @@ class LlamaTP:
             raise ValueError(f"w4_rows must be 'decode' or 'all', got {w4_rows!r}")
         if w4_rows != "decode" and weight_dtype != "int4":
             raise ValueError(f"w4_rows={w4_rows!r} is for weight_dtype='int4' only, got {weight_dtype!r}")
+        if w8_decode not in ("tile", "skinny"):
+            raise ValueError(f"w8_decode must be 'tile' or 'skinny', got {w8_decode!r}")
+        if w8_decode != "tile" and weight_dtype != "w8a8":
+            raise ValueError(f"w8_decode={w8_decode!r} is for weight_dtype='w8a8' only, got {weight_dtype!r}")
         if kv_prefill not in ("rows", "cache"):
             raise ValueError(f"kv_prefill must be 'rows' or 'cache', got {kv_prefill!r}")
         if kv_prefill == "cache" and kv_dtype != "fp8":
@@ -599,6 +609,8 @@ class LlamaTP:
         self.kv_prefill = kv_prefill
         self.weight_dtype = weight_dtype
         self.w4_rows = w4_rows
+        self.w8_decode = w8_decode
+        self.w8_skinny_rows = 16  # ops.skinny_w8's limit
         self.cfg = cfg
         self.sd = shard_dims(cfg, tp, rank)
         self.tp, self.rank = tp, rank
@@ -1048,6 +1060,7 @@ class LlamaTP:
             B=B, S=S, decode=decode, has_past=has_past, all_rows=all_rows, tp=self.tp, hq=sd.hq, hkv=sd.hkv,
             head_dim=cfg.head_dim, hidden=cfg.hidden, have_packed=bool(self.packed), have_w4=bool(self.w4),
             have_w8=bool(self.w8), w4_all=self.w4_rows == "all",
+            w8_skinny=self.w8_decode == "skinny", w8_skinny_rows=self.w8_skinny_rows,
             have_fp8=bool(self.fp8), o_packed="l0.o" in self.packed, o_fp8="l0.o" in self.fp8, kv_fp8=self.kv_fp8,
             w4_max_rows=self.w4_max_rows, pk_fold=self.pk_fold, prefill_fold=self.prefill_fold,
             fuse_combine=self.fuse_combine, fuse_add_norm=self.fuse_add_norm, ar_fuse=self.ar_fuse,
@@ -1067,7 +1080,7 @@ class LlamaTP:
         if name in self.w8:
             if not tr.w8:
                 raise RuntimeError(f"{name} is held as w8a8 codes only, and the route has no w8a8 tier")
-            return self._w8_proj(name)
+            return self._w8_proj(name, skinny=tr.w8s)
         if name in self.w4:
             N = self.w4_n[name]
             if tr.w4:
@@ -1084,11 +1097,18 @@ class LlamaTP:
             return lambda x, **kw: ops.skinny_packed(x, self.packed[name], N, variant=self.pk_variant, **kw)
         return None
 
-    def _w8_proj(self, name: str):
+    def _w8_proj(self, name: str, skinny: bool = False):
+        """``skinny`` (``ProjTiers.w8s``): the weight-streaming kernel -- the rows quantised in its prologue where
+        they fit it, else by ``ops.quant_rows_fp8`` as for the tile."""
         ops, (wq, ws, N) = self.ops, self.w8[name]
 
         def run(x, delta=None, resid_out=None, norm=False, act=ops.ACT_NONE, eps=1e-5, residual=None):
+            if skinny and ops.skinny_w8_fused_fits(*x.shape):
+                return ops.skinny_w8(x, wq, ws, N, delta=delta, resid_out=resid_out, norm=norm, eps=eps, act=act,
+                                     residual=residual)
             xq, xs = ops.quant_rows_fp8(x, delta, resid_out, norm=norm, eps=eps)
+            if skinny:
+                return ops.skinny_w8_codes(xq, xs, wq, ws, N, act=act, residual=residual)
             return ops.gemm_w8a8(xq, xs, wq, ws, N, act=act, residual=residual, workspace=self.workspace)
 
         return run

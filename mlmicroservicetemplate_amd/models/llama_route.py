@@ -21,6 +21,7 @@ class ProjTiers:
     fuse: bool
     w8: bool = False  # weight_dtype="w8a8": the only copy of a layer matrix, at every row count
     w4g: bool = False  # w4_rows="all": the int4 codes above w4_max_rows too, on the tiled ops.gemm_w4a16
+    w8s: bool = False  # w8_decode="skinny": the w8a8 codes on the weight-streaming ops.skinny_w8 / skinny_w8_codes
 
     def fp8_for(self, K: int) -> bool:
         """The e4m3 tier for a projection of inner size K: ops.skinny_fp8 takes rows * K bf16 activations
@@ -29,8 +30,13 @@ class ProjTiers:
 
 
 def proj_tiers(rows: int, have_packed: bool, have_w4: bool, have_fp8: bool, w4_max_rows: int,
-               have_w8: bool = False, w4_all: bool = False) -> ProjTiers:
+               have_w8: bool = False, w4_all: bool = False, w8_skinny: bool = False,
+               w8_skinny_rows: int = 16) -> ProjTiers:
     return ProjTiers(
+        # w8_decode="skinny": steps of <= w8_skinny_rows rows (the kernel's limit is 16) stream the same e4m3 codes
+        # global -> VGPR (ops.skinny_w8 with the row quantiser in its prologue where ops.skinny_w8_fused_fits
+        # holds, ops.quant_rows_fp8 + ops.skinny_w8_codes otherwise); larger steps keep the tier below
+        w8s=have_w8 and w8_skinny and rows <= w8_skinny_rows,
         # w4_rows="all": the int4 codes are the only copy of a layer matrix; steps of <= w4_max_rows rows keep
         # ops.skinny_w4 (the tier below), every larger one runs a gain-free RMSNorm + ops.gemm_w4a16 on the
         # same codes -- no layer projection reaches ops.linear
@@ -96,7 +102,8 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
                o_fp8: bool, w4_max_rows: int, pk_fold: bool, prefill_fold: bool, fuse_combine: bool,
                fuse_add_norm: bool, ar_fuse: bool, tp_overlap: bool, verify_attn: str, spec_max_tokens: int,
                dec_chunk: int, ar_fusable: bool, capturing: bool, kv_fp8: bool = False,
-               have_w8: bool = False, lora_tail: bool = False, w4_all: bool = False) -> StepRoute:
+               have_w8: bool = False, lora_tail: bool = False, w4_all: bool = False, w8_skinny: bool = False,
+               w8_skinny_rows: int = 16) -> StepRoute:
     """``have_*``: the model holds such copies at all; ``o_packed`` / ``o_fp8``: of ``l0.o``;
     ``ar_fusable``: the comm's one-shot all-reduce can ride in a GEMM producing ``B * S * hidden``
     outputs; ``capturing``: the current stream is capturing a graph.  The rest are the model's
@@ -105,9 +112,11 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
     combine prologue, the fused all-reduce, ``linear_add_rmsnorm`` or the overlapped TP prefill, so those are
     off and the tail runs o -> + delta -> gate / up without activation -> ``lora_gate_up`` -> down -> + delta
     (csrc/lora_linear.hip).  Off (q / k / v adapters only, or none): every decision below is as before.
-    ``w4_all``: ``w4_rows="all"`` -- the int4 codes serve every row count (``ProjTiers.w4g``)."""
+    ``w4_all``: ``w4_rows="all"`` -- the int4 codes serve every row count (``ProjTiers.w4g``).
+    ``w8_skinny`` / ``w8_skinny_rows``: ``w8_decode="skinny"`` and its row bound (``ProjTiers.w8s``); no other
+    decision reads them."""
     T = B * S
-    proj = proj_tiers(T, have_packed, have_w4, have_fp8, w4_max_rows, have_w8, w4_all)
+    proj = proj_tiers(T, have_packed, have_w4, have_fp8, w4_max_rows, have_w8, w4_all, w8_skinny, w8_skinny_rows)
     # TP = 1: the residual add rides in the o / down epilogues (h = r + a Wo^T, r' = h + g Wd^T), so
     # the next pre-norm GEMM reads one activation stream instead of two (r + delta) and writes no
     # residual copy.  With TP > 1 the add has to wait for the all-reduce.  prefill_fold: prefill at

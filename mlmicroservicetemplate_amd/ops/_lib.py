@@ -126,6 +126,8 @@ _SIGS = {
     "mls_gemm_w8a8": [P, P, P, P, P, P, P, I, I, I, I, I, I, P, _c.c_longlong, P, I, P],
     "mls_gemm_w8a8_num_variants": [],
     "mls_quant_rows_fp8": [P, P, P, P, P, I, I, I, F, P],
+    "mls_skinny_w8": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, I, P],
+    "mls_skinny_w8_num_variants": [],
     "mls_lora_split": [I, I, I, I],
     "mls_lora_shrink": [P, I, P, P, P, P, P, SZ, I, I, I, I, I, I, I, P],
     "mls_lora_expand": [P, I, P, P, P, P, P, P, SZ, I, I, I, F, I, I, I, I, I, I, I, I, P],

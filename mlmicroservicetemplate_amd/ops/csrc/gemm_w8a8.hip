@@ -23,16 +23,14 @@
 //    kernel's at the same register tiling (32 B per lane per 16x16x128 step against 16 B per 16x16x32);
 //  * the short-M configurations split K so the weights stream once over the chip.
 #include "gemm_ring.h"
+#include "w8_quant.h"
 
 namespace {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
-constexpr float W8_FP8_MAX = 448.f;
-constexpr float W8_AMAX_FLOOR = 9.094947017729282e-13f;  // 2^-40
-constexpr int W8_ROWB = 128;                             // bytes (= k values) of one k-step row
-constexpr int W8_E8M0_ONE = 0x7F7F7F7F;                  // block scale 2^0 in every byte
+constexpr int W8_ROWB = 128;  // bytes (= k values) of one k-step row
 
 struct W8Args {
   const uint8_t* a;   // [M][K] e4m3
@@ -273,20 +271,12 @@ __global__ __launch_bounds__(1024) void quant_rows_fp8_kernel(const bf16* __rest
     ss = block_sum(ss, red + 16);
     rstd = rsqrtf(ss / (float)K + eps);
   }
-  const float sc = fmaxf(amax, W8_AMAX_FLOOR) / W8_FP8_MAX;
+  const float sc = w8_row_scale(amax);
   const float inv = 1.f / sc;
 #pragma unroll
   for (int c = 0; c < QR_MAXC; ++c) {
     const int ch = c * nt + tid;
-    if (ch < nchunk) {
-      float f[8];
-      unpack8(h[c], f);
-      int lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, 0, false);
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, lo, true);
-      int hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * inv, f[5] * inv, 0, false);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * inv, f[7] * inv, hi, true);
-      reinterpret_cast<int2*>(q + row * K)[ch] = int2{lo, hi};
-    }
+    if (ch < nchunk) reinterpret_cast<int2*>(q + row * K)[ch] = w8_codes8(h[c], inv);
   }
   if (tid == 0) scale[row] = norm ? sc * rstd : sc;
 }

@@ -92,13 +92,16 @@ struct NoColScale {};
 // multiply by the scale, emit.  row_scale(m): rstd (times the activation scale); col_scale(n): the
 // weight's per-channel scale, NoColScale{} for none -- the product of the two is formed first.
 // ALL_ROWS: walk the ROWS of red[] and skip those past M (a trip count known at compile time), instead of M rows.
-template <int NWV, int ROWS, int COLS, bool ALL_ROWS = false, class RowScale, class ColScale = NoColScale>
+// N_GUARD: the last block's COLS may run past N (skinny_w8: N / 16 need not divide by the tiles per block).
+template <int NWV, int ROWS, int COLS, bool ALL_ROWS = false, bool N_GUARD = false, class RowScale,
+          class ColScale = NoColScale>
 MLS_DEV void sk_reduce_store(const float (&red)[NWV][ROWS][COLS + 1], const SkEpi& e, int n0, RowScale row_scale,
                              ColScale col_scale = {}) {
   const bool glu = e.act == ACT_SILU_MUL;
   for (int q = threadIdx.x; q < (ALL_ROWS ? ROWS : e.M) * COLS; q += NWV * 64) {
     const int m = q / COLS, c = q % COLS;
     if (ALL_ROWS && m >= e.M) continue;
+    if (N_GUARD && n0 + c >= e.N) continue;
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < NWV; ++w) v += red[w][m][c];

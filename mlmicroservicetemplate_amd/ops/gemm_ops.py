@@ -731,6 +731,85 @@ def gemm_w8a8(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Te
     return out
 
 
+W8S_VARIANTS = 7  # launch shapes of csrc/skinny_w8.hip (0: by shape; 1-2 / 3-4 / 5-6: 2 / 4 / 1 tiles per block)
+W8S_MAX_ROWS = 16
+W8S_FUSED_ELEMS = 32768  # M * K the fused prologue keeps in registers between its two passes
+
+
+def skinny_w8_fused_fits(M: int, K: int) -> bool:
+    """Whether :func:`skinny_w8` takes ``M`` bf16 rows of ``K``: M <= 16 and M * K <= 32768 (Llama-3-8B: 8 rows
+    of 4096, 2 of 14336); above, :func:`quant_rows_fp8` + :func:`skinny_w8_codes` serve up to 16 rows of any K."""
+    return 1 <= M <= W8S_MAX_ROWS and K >= 128 and K % 128 == 0 and M * K <= W8S_FUSED_ELEMS
+
+
+def _skinny_w8(name, x, xs, delta, resid_out, wq, ws, N, norm, eps, act, bias, residual, out, variant):
+    dev = x.device
+    M, K = x.shape
+    N = int(N)
+    if not 1 <= M <= W8S_MAX_ROWS or N < 1 or K % 128 or N % 16:
+        raise ValueError(f"{name}: 1 <= M ({M}) <= {W8S_MAX_ROWS}, N ({N}) % 16 == 0, K ({K}) % 128 == 0")
+    if not 0 <= int(variant) < W8S_VARIANTS:
+        raise ValueError(f"{name}: variant in 0..{W8S_VARIANTS - 1}")
+    _w8_bytes(wq, "wq", dev, N * K)
+    _w8_f32(ws, "ws", dev, N)
+    code = _act(act)
+    if code not in (ACT_NONE, ACT_SILU_MUL):
+        raise ValueError(f"{name}: act none or silu_mul")
+    if bias is not None:
+        _w8_f32(bias, "bias", dev, N)
+    if residual is not None:
+        if code == ACT_SILU_MUL:
+            raise ValueError("silu_mul takes no residual")
+        _w8_bf16(residual, "residual", dev, (M, N))
+    n_out = N // 2 if code == ACT_SILU_MUL else N
+    if out is None:
+        out = torch.empty(M, n_out, device=dev, dtype=torch.bfloat16)
+    else:
+        _w8_bf16(out, "out", dev, (M, n_out))
+    rc = lib().mls_skinny_w8(x.data_ptr(), _ptr(xs), _ptr(delta), _ptr(resid_out), wq.data_ptr(), ws.data_ptr(),
+                             _ptr(bias), _ptr(residual), out.data_ptr(), M, N, K, code, int(bool(norm)), float(eps),
+                             int(variant), stream_ptr(dev))
+    check(rc, "mls_skinny_w8")
+    return out
+
+
+def skinny_w8(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, N: int, *, delta: Optional[torch.Tensor] = None,
+              resid_out: Optional[torch.Tensor] = None, norm: bool = False, eps: float = 1e-5, act=ACT_NONE,
+              bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None, variant: int = 0) -> torch.Tensor:
+    """W8A8 decode projection of bf16 rows in one launch (csrc/skinny_w8.hip, the fused form): what
+    :func:`quant_rows_fp8` + :func:`gemm_w8a8` compute -- ``h = bf16(x + delta)`` (to ``resid_out`` when given),
+    its codes and row scale by ``reference.a8_quant``'s rule, ``norm``: the scale times ``rsqrt(mean(h^2) + eps)``,
+    then ``act((hq . wq^T) * hs[m] * ws[n] + bias) (+ residual)`` -- with ``pack_w8``'s ``(wq, ws)`` streamed global
+    -> VGPR, no LDS ring and no K split across blocks.  ``(M, K)`` inside :func:`skinny_w8_fused_fits`."""
+    if x.dim() != 2:
+        raise ValueError("skinny_w8: x [M, K]")
+    M, K = x.shape
+    _w8_bf16(x, "x", x.device, (M, K))
+    if not skinny_w8_fused_fits(M, K):
+        raise ValueError(f"skinny_w8: ({M}, {K}) is outside skinny_w8_fused_fits (M <= {W8S_MAX_ROWS}, K % 128 == 0, "
+                         f"M * K <= {W8S_FUSED_ELEMS}); quantise the rows and call skinny_w8_codes")
+    if resid_out is not None and delta is None:
+        raise ValueError("resid_out needs delta")
+    for name, t in (("delta", delta), ("resid_out", resid_out)):
+        if t is not None:
+            _w8_bf16(t, name, x.device, (M, K))
+    if resid_out is not None and resid_out.data_ptr() in (x.data_ptr(), delta.data_ptr()):
+        raise ValueError("resid_out must not alias x or delta: every block reads them")
+    return _skinny_w8("skinny_w8", x, None, delta, resid_out, wq, ws, N, norm, eps, act, bias, residual, out, variant)
+
+
+def skinny_w8_codes(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, N: int, *, act=ACT_NONE,
+                    bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None, variant: int = 0) -> torch.Tensor:
+    """:func:`gemm_w8a8`'s product for M <= 16 rows of any K on the weight-streaming kernel (csrc/skinny_w8.hip, the
+    codes form): ``(xq, xs)`` from :func:`quant_rows_fp8`, the rows :func:`skinny_w8` cannot hold."""
+    if xq.dim() != 2 or xq.dtype != torch.uint8 or not xq.is_contiguous():
+        raise ValueError("skinny_w8_codes: xq contiguous uint8 [M, K]")
+    _w8_f32(xs, "xs", xq.device, xq.shape[0])
+    return _skinny_w8("skinny_w8_codes", xq, xs, None, None, wq, ws, N, False, 0.0, act, bias, residual, out, variant)
+
+
 def fold_norm(w: torch.Tensor, gain: torch.Tensor) -> torch.Tensor:
     """``W[:, k] * gain[k]`` in fp32, rounded once to bf16: RMSNorm(x) @ W^T == rstd * (x @ fold^T)."""
     return (w.float() * gain.float().view(1, -1)).to(w.dtype)

@@ -52,6 +52,7 @@ class LlamaPlugin(ModelPlugin):
         extra = s.model_yaml() if hasattr(s, "model_yaml") else {}
         weight_dtype = self.parse_weight_dtype(extra)  # before any weight is read or allocated
         w4_rows = self.parse_w4_rows(extra, weight_dtype)
+        w8_decode = self.parse_w8_decode(extra, weight_dtype)
         self.speculate, self.speculate_ngram = self.parse_speculate(extra)
         self.speculate_device = self.parse_speculate_device(extra, self.speculate)
         self.prefix_cache = self.parse_prefix_cache(extra)
@@ -87,7 +88,7 @@ class LlamaPlugin(ModelPlugin):
         self.model = llama.LlamaTP(params, cfg, tp=tp, rank=ctx.rank, comm=llama.TPComm(None, tp, device=dev), backend=backend,
                                    device=dev, max_batch=max_batch, max_seq=max_seq, kv_pages=kv_pages,
                                    kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_prefill=kv_prefill, lora=lora_kw,
-                                   w4_rows=w4_rows)
+                                   w4_rows=w4_rows, w8_decode=w8_decode)
         for index, (name, path) in enumerate(lora_paths.items()):  # every rank reads the adapter and keeps its share (load_adapter)
             from ..utils.checkpoint import load_lora_adapter
 
@@ -116,9 +117,9 @@ class LlamaPlugin(ModelPlugin):
                 self.engine.start()
         self.kv_pages = kv_pages
         logger.info("llama ready: tp=%d rank=%d backend=%s device=%s kv_dtype=%s kv_prefill=%s kv_bytes_per_token=%d "
-                    "weight_dtype=%s w4_rows=%s layer_weight_bytes=%d prefix_cache=%s", tp, ctx.rank, backend, dev,
-                    kv_dtype, kv_prefill, self.kv_page_bytes(cfg, tp, backend, kv_dtype) // 64, weight_dtype, w4_rows,
-                    self.model.layer_weight_bytes(), self.prefix_cache)
+                    "weight_dtype=%s w4_rows=%s w8_decode=%s layer_weight_bytes=%d prefix_cache=%s", tp, ctx.rank, backend,
+                    dev, kv_dtype, kv_prefill, self.kv_page_bytes(cfg, tp, backend, kv_dtype) // 64, weight_dtype,
+                    w4_rows, w8_decode, self.model.layer_weight_bytes(), self.prefix_cache)
 
     @staticmethod
     def parse_weight_dtype(extra: dict) -> str:
@@ -141,6 +142,18 @@ class LlamaPlugin(ModelPlugin):
         if rows != "decode" and weight_dtype != "int4":
             raise ValueError(f"w4_rows: {rows} is for weight_dtype: int4 only, got {weight_dtype!r}")
         return rows
+
+    @staticmethod
+    def parse_w8_decode(extra: dict, weight_dtype: str) -> str:
+        """MODEL_CONFIG ``w8_decode`` (with ``weight_dtype: w8a8`` only): ``tile`` (default: every step on
+        ``quant_rows_fp8`` + ``gemm_w8a8``) | ``skinny`` (steps of <= 16 rows on the weight-streaming
+        ``skinny_w8`` kernel; :class:`~..models.llama.LlamaTP`)."""
+        mode = str(extra.get("w8_decode", "tile"))
+        if mode not in ("tile", "skinny"):
+            raise ValueError(f"w8_decode must be 'tile' or 'skinny', got {mode!r}")
+        if mode != "tile" and weight_dtype != "w8a8":
+            raise ValueError(f"w8_decode: {mode} is for weight_dtype: w8a8 only, got {weight_dtype!r}")
+        return mode
 
     @staticmethod
     def parse_lora(extra: dict, prefix_cache: bool = False):

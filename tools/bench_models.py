@@ -195,7 +195,7 @@ def bench_llama_prefix(args):
         raise SystemExit("--shared-prefix measures the paged cache: give --kv-pages")
     p = init_llama_shard(LLAMA3_8B, 1, 0, seed=0, device=dev)
     m = LlamaTP(p, LLAMA3_8B, backend="fused", device=dev, max_batch=B, max_seq=args.max_seq, kv_pages=args.kv_pages,
-                kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows,
+                kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows, w8_decode=args.w8_decode,
                 kv_prefill=args.kv_prefill)
     del p
     shared = np.random.default_rng(1).integers(1000, 100000, N).tolist()
@@ -266,7 +266,7 @@ def bench_llama(args):
     p = init_llama_shard(LLAMA3_8B, tp, 0, seed=0, device=dev)
     comm = ShardEmulationComm(tp) if tp > 1 else None
     m = LlamaTP(p, LLAMA3_8B, tp=tp, rank=0, comm=comm, backend="fused", device=dev, max_batch=max(args.batches),
-                max_seq=args.max_seq, kv_pages=args.kv_pages, kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows,
+                max_seq=args.max_seq, kv_pages=args.kv_pages, kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows, w8_decode=args.w8_decode,
                 kv_prefill=args.kv_prefill)
     if m.pages is not None and args.shuffle_pages:  # pages scattered as in a long-running server
         import random
@@ -275,7 +275,7 @@ def bench_llama(args):
     print(json.dumps({"bench": "llama3-8b", "tp": tp, "collectives": "stubbed" if tp > 1 else "none",
                       "skinny_max_split": args.skinny_max_split, "kv_pages": args.kv_pages, "kv_dtype": args.kv_dtype,
                       "kv_prefill": args.kv_prefill,
-                      "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows, "layer_weight_bytes": m.layer_weight_bytes(),
+                      "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows, "w8_decode": args.w8_decode, "layer_weight_bytes": m.layer_weight_bytes(),
                       "init_s": round(time.time() - t0, 1)}), flush=True)
     for B in args.batches:
         S = args.prompt
@@ -306,7 +306,7 @@ def bench_llama(args):
         torch.cuda.synchronize()
         dec = (time.perf_counter() - t2) / n
         print(json.dumps({"bench": "llama3-8b", "tp": tp, "batch": B, "prompt": S, "kv_pages": args.kv_pages,
-                          "kv_dtype": args.kv_dtype, "kv_prefill": args.kv_prefill, "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows, "prefill_ms": round(pre * 1e3, 2), "prefill_tok_s": round(B * S / pre, 1),
+                          "kv_dtype": args.kv_dtype, "kv_prefill": args.kv_prefill, "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows, "w8_decode": args.w8_decode, "prefill_ms": round(pre * 1e3, 2), "prefill_tok_s": round(B * S / pre, 1),
                           "decode_ms_per_step": round(dec * 1e3, 3), "decode_tok_s": round(B / dec, 1)}), flush=True)
         for K in args.speculate:
             _bench_speculate(m, args, K, B, S, ids, lens, tok, cur)
@@ -326,7 +326,7 @@ def bench_llama_lora(args):
     t0 = time.time()
     p = init_llama_shard(cfg, 1, 0, seed=0, device=dev)
     kw = dict(backend="fused", device=dev, max_batch=max(max(args.batches), 8), max_seq=args.max_seq,
-              kv_pages=args.kv_pages, kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows, kv_prefill=args.kv_prefill)
+              kv_pages=args.kv_pages, kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows, w8_decode=args.w8_decode, kv_prefill=args.kv_prefill)
     plain = LlamaTP(p, cfg, **kw)
     lora = {"max_adapters": args.lora, "max_rank": args.lora_rank}
     mods = ("q", "k", "v")
@@ -335,7 +335,7 @@ def bench_llama_lora(args):
     m = LlamaTP(p, cfg, lora=lora, **kw)
     for a in range(args.lora):
         m.load_adapter(a, *random_lora_adapter(cfg, args.lora_rank, seed=100 + a, modules=mods, device=dev))
-    head = {"bench": "llama3-8b-lora", "adapters": args.lora, "rank": args.lora_rank, "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows,
+    head = {"bench": "llama3-8b-lora", "adapters": args.lora, "rank": args.lora_rank, "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows, "w8_decode": args.w8_decode,
             "targets": args.lora_targets,
             "kv_dtype": args.kv_dtype, "kv_pages": args.kv_pages}
     print(json.dumps(dict(head, init_s=round(time.time() - t0, 1))), flush=True)
@@ -445,7 +445,7 @@ def _bench_speculate(m, args, K, B, S, ids, lens, tok, cur):
     m.verify_attn = "multi"
     med = {a: float(np.median(v)) for a, v in times.items()}
     print(json.dumps({"bench": "llama3-8b-verify", "batch": B, "prompt": S, "T": T, "kv_pages": args.kv_pages,
-                      "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows, "kv_dtype": args.kv_dtype, "kv_prefill": args.kv_prefill,
+                      "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows, "w8_decode": args.w8_decode, "kv_dtype": args.kv_dtype, "kv_prefill": args.kv_prefill,
                       **{a + "_ms": round(v, 3) for a, v in med.items()},
                       **{a + "_ms_min": round(min(times[a]), 3) for a in times},
                       # accepted drafts per step above which a verify step yields more tokens per ms than a decode step
@@ -481,7 +481,7 @@ def _bench_speculate(m, args, K, B, S, ids, lens, tok, cur):
         if name != "plain":
             print(json.dumps({"bench": "llama3-8b-speculate", "batch": B, "prompt": S, "new_tokens": args.new,
                               "speculate": K, "spec_accept": float(name.split("_")[1]), "kv_pages": args.kv_pages,
-                              "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows, "plain_tok_s": round(max(res["plain"]), 1),
+                              "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows, "w8_decode": args.w8_decode, "plain_tok_s": round(max(res["plain"]), 1),
                               "speculative_tok_s": round(max(res[name]), 1), **stats[name]}), flush=True)
     if m.pages is not None:
         for b in range(B):
@@ -513,7 +513,7 @@ def _bench_spec_device(m, args, K, B, S, ids, lens):
                 stats[name], toks[name] = dict(m.spec_stats), out.to(torch.int32).cpu()
         print(json.dumps({"bench": "llama3-8b-spec-device", "batch": B, "prompt": S, "prompts": kind,
                           "new_tokens": args.new, "speculate": K, "kv_pages": args.kv_pages,
-                          "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows, "kv_dtype": args.kv_dtype,
+                          "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows, "w8_decode": args.w8_decode, "kv_dtype": args.kv_dtype,
                           **{a + "_tok_s": round(float(np.median(v)), 1) for a, v in res.items()},
                           **{a + "_tok_s_max": round(max(v), 1) for a, v in res.items()},
                           "host_stats": stats["host"], "device_stats": stats["device"],
@@ -533,7 +533,7 @@ def bench_llama_serve(args):
     B = args.batches[0]
     p = init_llama_shard(LLAMA3_8B, 1, 0, seed=0, device=dev)
     m = LlamaTP(p, LLAMA3_8B, backend="fused", device=dev, max_batch=B, max_seq=args.max_seq, kv_pages=args.kv_pages,
-                kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows,
+                kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows, w8_decode=args.w8_decode,
                 kv_prefill=args.kv_prefill)
     eng = ContinuousLlama(m).start()
     rng = np.random.default_rng(0)
@@ -550,7 +550,7 @@ def bench_llama_serve(args):
     toks = sum(len(f.result()) for f in futs)
     eng.stop()
     print(json.dumps({"bench": "llama3-8b-continuous", "max_batch": B, "kv_pages": args.kv_pages,
-                      "kv_dtype": args.kv_dtype, "kv_prefill": args.kv_prefill, "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows, "requests": args.requests,
+                      "kv_dtype": args.kv_dtype, "kv_prefill": args.kv_prefill, "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows, "w8_decode": args.w8_decode, "requests": args.requests,
                       "prompt": args.prompt, "new_tokens": args.new, "tokens_per_s": round(toks / dt, 1),
                       "requests_per_s": round(args.requests / dt, 2), "p50_latency_s": round(float(np.median(lat)), 3),
                       "iterations": eng.iterations}), flush=True)
@@ -582,6 +582,9 @@ def main():
     ap.add_argument("--w4-rows", choices=["decode", "all"], default="decode",
                     help="llama, --weight-dtype int4: the codes serve steps of <= 32 rows (a bf16 copy the rest), or "
                          "every row count on the tiled W4A16 GEMM (codes only in HBM)")
+    ap.add_argument("--w8-decode", choices=["tile", "skinny"], default="tile",
+                    help="llama, --weight-dtype w8a8: steps of <= 16 rows on quant_rows_fp8 + gemm_w8a8, or on the "
+                         "weight-streaming skinny_w8 kernel")
     ap.add_argument("--weight-dtype", choices=["bf16", "int4", "w8a8"], default="bf16",
                     help="llama: layer projections in bf16, W4A16 (4-bit codes, one bf16 scale per row and 128 k), or "
                          "W8A8 (e4m3 weights per channel, e4m3 activations per row, block-scaled MFMA)")

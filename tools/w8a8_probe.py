@@ -2,13 +2,16 @@
 
 ``kernel``: the four Llama-3-8B TP = 1 layer projections (qkv, o, gate_up + SiLU-mul, down) at M = 16 .. 4096:
 ``ops.gemm_w8a8`` alone, ``ops.quant_rows_fp8 + ops.gemm_w8a8``, and what the bf16 model runs at that row
-count (``ops.skinny_packed`` on the granule-packed copy up to 24 rows, ``ops.linear`` above).  us per call from
+count (``ops.skinny_packed`` on the granule-packed copy up to 24 rows, ``ops.linear`` above); up to 16 rows also
+what ``w8_decode="skinny"`` runs (``ops.skinny_w8``, or the quantiser + ``ops.skinny_w8_codes``), with the
+achieved TB/s of weight bytes.  us per call from
 device events around back-to-back launches, median and minimum of 5 interleaved windows, and TFLOP/s of the
 median.  Up to 256 rows every arm rotates over enough copies of its weights to exceed the 256 MB infinity cache,
 so the weight stream comes from HBM as in a model step; above, one copy (compute-bound).
 
 ``model``: ``LlamaTP`` (Llama-3-8B, TP = 1, random weights) with bf16 and with w8a8 weights side by side: prefill
-at ``--prefill B`` x 512 tokens and ms per decode step at ``--batches``, interleaved windows.
+at ``--prefill B`` x 512 tokens and ms per decode step at ``--batches``, interleaved windows; ``--skinny`` adds a
+w8a8 model with ``w8_decode="skinny"`` as a third arm.
 
 One JSON line per measurement on stdout (kept in profiles/w8a8_ab.jsonl)."""
 import argparse
@@ -43,14 +46,30 @@ def _window(fn, n):
     return e0.elapsed_time(e1) * 1e3 / n
 
 
-def _ab(arms, warm_ms, windows=5):
-    """us per call of every arm: ``windows`` interleaved windows of >= ~20 ms each after a warm floor."""
+def _graphed(f, calls):
+    """``calls`` launches of ``f`` captured once: a replay costs the device what they cost and the host one launch."""
+    f()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(calls):
+            f()
+    return g.replay
+
+
+def _ab(arms, warm_ms, windows=5, graph_calls=0):
+    """us per call of every arm: ``windows`` interleaved windows of >= ~20 ms each after a warm floor.
+    ``graph_calls``: every arm as a captured graph of that many calls (device time; eager back-to-back launches of
+    kernels under ~10 us measure the host's launch rate)."""
+    per = max(graph_calls, 1)
+    if graph_calls:
+        arms = {a: _graphed(f, graph_calls) for a, f in arms.items()}
     _warm(lambda: [f() for f in arms.values()], warm_ms)
-    n = {a: max(10, min(400, int(2e4 / max(_window(f, 5), 1.0)))) for a, f in arms.items()}
+    n = {a: max(10 // per + 1, min(400, int(2e4 / max(_window(f, 5), 1.0)) + 1)) for a, f in arms.items()}
     times = {a: [] for a in arms}
     for _ in range(windows):
         for a, f in arms.items():
-            times[a].append(_window(f, n[a]))
+            times[a].append(_window(f, n[a]) / per)
     return {a: (float(np.median(v)), float(min(v))) for a, v in times.items()}
 
 
@@ -92,9 +111,23 @@ def bench_kernel(args):
                 q, s = ops.quant_rows_fp8(x)
                 return ops.gemm_w8a8(q, s, w8[it["q"] % n8], wsc, N, act=act, variant=args.variant, workspace=ws)
 
-            res = _ab({"bf16": bf16, "gemm_w8a8": gemm, "quant_gemm_w8a8": quant_gemm}, args.warm_ms)
+            arms = {"bf16": bf16, "gemm_w8a8": gemm, "quant_gemm_w8a8": quant_gemm}
+            fused = M <= 16 and ops.skinny_w8_fused_fits(M, K)
+            if M <= 16:  # what w8_decode="skinny" runs: the fused form, or the quantiser + the codes form
+                it["s"] = 0
+
+                def skinny():
+                    it["s"] += 1
+                    wt = w8[it["s"] % n8]
+                    if fused:
+                        return ops.skinny_w8(x, wt, wsc, N, act=act, variant=args.skinny_variant)
+                    q, s = ops.quant_rows_fp8(x)
+                    return ops.skinny_w8_codes(q, s, wt, wsc, N, act=act, variant=args.skinny_variant)
+
+                arms["skinny_w8"] = skinny
+            res = _ab(arms, args.warm_ms, graph_calls=args.graph_calls)
             flop = 2.0 * M * N * K
-            line = {"bench": "w8a8-kernel", "proj": name, "M": M, "N": N, "K": K, "variant": args.variant,
+            line = {"bench": "w8a8-kernel", "proj": name, "M": M, "N": N, "K": K, "variant": args.variant, "graph_calls": args.graph_calls,
                     "bf16_route": "skinny_packed" if packed else "linear", "weights_from": "hbm" if stream else "cache"}
             for a, (med, mn) in res.items():
                 line[a + "_us"] = round(med, 2)
@@ -102,6 +135,13 @@ def bench_kernel(args):
                 line[a + "_tflops"] = round(flop / med / 1e6, 1)
             line["speedup_gemm"] = round(res["bf16"][0] / res["gemm_w8a8"][0], 3)
             line["speedup_quant_gemm"] = round(res["bf16"][0] / res["quant_gemm_w8a8"][0], 3)
+            if "skinny_w8" in res:
+                line.update(skinny_form="fused" if fused else "quant+codes", skinny_variant=args.skinny_variant,
+                            skinny_w8_tb_s=round(N * K / res["skinny_w8"][0] / 1e6, 3),
+                            quant_gemm_w8a8_tb_s=round(N * K / res["quant_gemm_w8a8"][0] / 1e6, 3),
+                            bf16_tb_s=round(2 * N * K / res["bf16"][0] / 1e6, 3),
+                            speedup_skinny=round(res["bf16"][0] / res["skinny_w8"][0], 3),
+                            skinny_vs_tile=round(res["quant_gemm_w8a8"][0] / res["skinny_w8"][0], 3))
             print(json.dumps(line), flush=True)
             del w16, w8
 
@@ -115,6 +155,9 @@ def bench_model(args):
     B_max = max(args.batches + args.prefill)
     models = {wd: LlamaTP(dict(p), LLAMA3_8B, backend="fused", device=dev, max_batch=B_max, max_seq=args.max_seq,
                           weight_dtype=wd) for wd in ("bf16", "w8a8")}
+    if args.skinny:  # a third arm: the same codes with w8_decode="skinny"
+        models["w8a8_skinny"] = LlamaTP(dict(p), LLAMA3_8B, backend="fused", device=dev, max_batch=B_max,
+                                        max_seq=args.max_seq, weight_dtype="w8a8", w8_decode="skinny")
     del p
     print(json.dumps({"bench": "w8a8-model", "init_s": round(time.time() - t0, 1),
                       **{wd + "_layer_weight_bytes": m.layer_weight_bytes() for wd, m in models.items()}}), flush=True)
@@ -142,7 +185,10 @@ def bench_model(args):
         print(json.dumps({"bench": "w8a8-model", "phase": "decode", "batch": B, "context": S,
                           **{wd + "_ms_per_step": round(v[0] / 1e3, 3) for wd, v in res.items()},
                           **{wd + "_ms_per_step_min": round(v[1] / 1e3, 3) for wd, v in res.items()},
-                          "speedup": round(res["bf16"][0] / res["w8a8"][0], 3)}), flush=True)
+                          "speedup": round(res["bf16"][0] / res["w8a8"][0], 3),
+                          **({"speedup_skinny": round(res["bf16"][0] / res["w8a8_skinny"][0], 3),
+                              "skinny_vs_tile": round(res["w8a8"][0] / res["w8a8_skinny"][0], 3)}
+                             if args.skinny else {})}), flush=True)
 
 
 def main():
@@ -151,6 +197,11 @@ def main():
     ap.add_argument("--rows", type=int, nargs="+", default=[16, 32, 128, 256, 512, 4096])
     ap.add_argument("--projections", nargs="+", default=list(SHAPES), choices=list(SHAPES))
     ap.add_argument("--variant", type=int, default=0, help="kernel: force a gemm_w8a8 tile (0: the launcher's pick)")
+    ap.add_argument("--skinny-variant", type=int, default=0,
+                    help="kernel: force a skinny_w8 launch shape in the <= 16-row arm (0: the launcher's pick)")
+    ap.add_argument("--graph-calls", type=int, default=0,
+                    help="kernel: time every arm as a captured graph of this many calls (0: eager launches)")
+    ap.add_argument("--skinny", action="store_true", help="model: a third arm, w8a8 with w8_decode='skinny'")
     ap.add_argument("--prefill", type=int, nargs="*", default=[1, 8], help="model: prefill batches of --prompt tokens")
     ap.add_argument("--batches", type=int, nargs="*", default=[1, 8, 32, 128], help="model: decode batch sizes")
     ap.add_argument("--prompt", type=int, default=512)
