@@ -533,7 +533,7 @@ class LlamaTP:
                  comm: Optional[TPComm] = None, backend: str = "reference", device="cpu", max_batch: int = 8,
                  max_seq: int = 1024, top_k_max: int = 50, kv_pages: int = 0, kv_dtype: str = "bf16",
                  weight_dtype: str = "bf16", kv_prefill: str = "rows", lora: Optional[dict] = None,
-                 w4_rows: str = "decode", w8_decode: str = "tile"):
+                 w4_rows: str = "decode", w8_decode: str = "tile", verify_fp8: str = "ctx"):
         """``lora={"max_adapters": n, "max_rank": r}``: room for n LoRA adapters of rank <= r on the q / k / v
         projections, chosen per cache slot (:meth:`load_adapter`, :meth:`set_slot_adapter`,
         ``GenParams.adapter``); until one is loaded neither backend computes anything new.
@@ -587,7 +587,14 @@ class LlamaTP:
         launch with the row quantiser in its prologue where ``ops.skinny_w8_fused_fits`` holds,
         ``ops.quant_rows_fp8`` + ``ops.skinny_w8_codes`` otherwise; larger steps keep ``ops.gemm_w8a8``.  Same
         rule and codes, so the numerics are ``tile``'s up to fp32 summation order.  The reference backend accepts
-        and ignores it."""
+        and ignores it.
+        ``verify_fp8="multi"`` (with ``kv_dtype="fp8"`` and ``kv_prefill="cache"`` only; default ``"ctx"``): the
+        fused backend's verify steps attend through ``ops.decode_attention_multi_fp8`` -- one block streams a
+        split's e4m3 rows once for the step's positions and the Hq / Hkv heads of a KV head -- instead of
+        ``ops.flash_attention_ctx_fp8`` split-KV, wherever a bf16 cache would take ``ops.decode_attention_multi``
+        (positions x Hq / Hkv <= 16, ``MLS_VERIFY_ATTN`` not ``ctx``).  Same cache bytes, same scales; P is
+        rounded to bf16 with the V scale folded in, as the decode step does.  The reference backend accepts and
+        ignores it."""
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
         if weight_dtype not in ("bf16", "int4", "w8a8"):
@@ -605,11 +612,17 @@ class LlamaTP:
         if kv_prefill == "cache" and kv_dtype != "fp8":
             raise ValueError("kv_prefill='cache' is for kv_dtype='fp8' only: a bf16 cache already holds the very "
                              "rows prefill attends")
+        if verify_fp8 not in ("ctx", "multi"):
+            raise ValueError(f"verify_fp8 must be 'ctx' or 'multi', got {verify_fp8!r}")
+        if verify_fp8 != "ctx" and (kv_dtype != "fp8" or kv_prefill != "cache"):
+            raise ValueError(f"verify_fp8={verify_fp8!r} is for kv_dtype='fp8' with kv_prefill='cache' only, got "
+                             f"{kv_dtype!r} / {kv_prefill!r}")
         self.kv_dtype = kv_dtype
         self.kv_prefill = kv_prefill
         self.weight_dtype = weight_dtype
         self.w4_rows = w4_rows
         self.w8_decode = w8_decode
+        self.verify_fp8 = verify_fp8
         self.w8_skinny_rows = 16  # ops.skinny_w8's limit
         self.cfg = cfg
         self.sd = shard_dims(cfg, tp, rank)
@@ -716,7 +729,7 @@ class LlamaTP:
             tp == 1 or getattr(self.comm, "graph_safe", False) or self._rccl_graphs
             or getattr(self.comm, "car", None) is not None)
         self._graphs: Dict[Tuple[int, int, int], tuple] = {}
-        self._ver_graphs: Dict[Tuple[int, int, int, int, str], tuple] = {}
+        self._ver_graphs: Dict[Tuple[int, int, int, int, str, str], tuple] = {}
         # speculative decoding: the most positions per sequence a verify step may carry (drafts + 1)
         self.spec_max_tokens = 8
         self.spec_stats = {"steps": 0, "drafted": 0, "accepted": 0}
@@ -1061,6 +1074,7 @@ class LlamaTP:
             head_dim=cfg.head_dim, hidden=cfg.hidden, have_packed=bool(self.packed), have_w4=bool(self.w4),
             have_w8=bool(self.w8), w4_all=self.w4_rows == "all",
             w8_skinny=self.w8_decode == "skinny", w8_skinny_rows=self.w8_skinny_rows,
+            verify_fp8_multi=self.verify_fp8 == "multi",
             have_fp8=bool(self.fp8), o_packed="l0.o" in self.packed, o_fp8="l0.o" in self.fp8, kv_fp8=self.kv_fp8,
             w4_max_rows=self.w4_max_rows, pk_fold=self.pk_fold, prefill_fold=self.prefill_fold,
             fuse_combine=self.fuse_combine, fuse_add_norm=self.fuse_add_norm, ar_fuse=self.ar_fuse,
@@ -1179,7 +1193,7 @@ class LlamaTP:
 
     # -- attention
     def _verify_workspace(self, T: int, chunk: int) -> torch.Tensor:
-        """Split-KV partials of a verify step (``ops.decode_attention_multi``) of T rows."""
+        """Split-KV partials of a verify step (``ops.decode_attention_multi`` / ``_multi_fp8``) of T rows."""
         sd, D = self.sd, self.cfg.head_dim
         cap = self.pages.pages_per_seq * self.page_rows if self.pages is not None else self.max_seq
         return self._verify_ws(T * sd.hq * (-(-min(self._dec_ctx or cap, cap) // chunk)) * (D + 2))
@@ -1266,6 +1280,9 @@ class LlamaTP:
             a = attend(qkv, *caches, st.lens, sd.hq, sd.hkv, D, **st.attn_kw)
             return a if st.rt.fuse_combine else (a, None)
         self._rope_kv(i, qkv, st.pos, st.slots, st.lens, st.S)
+        if st.rt.multi and self.kv_fp8:
+            return ops.decode_attention_multi_fp8(qkv, kc, vc, self.k_scale[i], self.v_scale[i], st.past, st.lens, st.B,
+                                                  st.S, sd.hq, sd.hkv, D, **st.attn_kw), None
         if st.rt.multi:
             return ops.decode_attention_multi(qkv, kc, vc, st.past, st.lens, st.B, st.S, sd.hq, sd.hkv, D,
                                               **st.attn_kw), None
@@ -1669,7 +1686,7 @@ class LlamaTP:
         """Captured verify step for B sequences of T positions under the context bound ctx (static id /
         past / lens / slot buffers, as :meth:`_decode_graph`).  Warm-up and capture run with
         ``lens == past``: every row is padding, so no cache row is written."""
-        key = (B, T, k, ctx, self.verify_attn)  # one graph per attention route (A/B arms)
+        key = (B, T, k, ctx, self.verify_attn, self.verify_fp8)  # one graph per attention route (A/B arms)
         if key in self._ver_graphs:
             return self._ver_graphs[key]
         dev = self.device
@@ -2297,7 +2314,7 @@ class LlamaTP:
         (default the model's).  Warm-up runs the forward on scratch inputs with ``lens == past`` (every
         row is padding: no cache row is written, no slot state touched)."""
         eos = tuple(sorted(self.cfg.eos_ids if eos is None else eos))
-        key = ("serve_spec", Bv, T, k, ctx, self.verify_attn, tuple(ngram), eos)
+        key = ("serve_spec", Bv, T, k, ctx, self.verify_attn, self.verify_fp8, tuple(ngram), eos)
         hit = self._dev_graphs.get(key)
         if hit is not None:
             return hit[0]

@@ -75,7 +75,7 @@ class StepRoute:
     fuse_combine: bool  # split-KV combine in the o-projection's prologue
     ar_fuse: bool       # TP all-reduce in the row-parallel projections' epilogue
     fuse_rn: bool       # o / down through ops.linear_add_rmsnorm
-    multi: bool         # verify step on ops.decode_attention_multi
+    multi: bool         # verify step on ops.decode_attention_multi (an e4m3 cache: ops.decode_attention_multi_fp8)
     overlap: bool       # TP prefill as two interleaved batch halves
     dec_chunk: int      # decode split rows
     lora_tail: bool = False  # a loaded adapter targets o / gate / up / down: the tail runs unfused around the deltas
@@ -103,7 +103,7 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
                fuse_add_norm: bool, ar_fuse: bool, tp_overlap: bool, verify_attn: str, spec_max_tokens: int,
                dec_chunk: int, ar_fusable: bool, capturing: bool, kv_fp8: bool = False,
                have_w8: bool = False, lora_tail: bool = False, w4_all: bool = False, w8_skinny: bool = False,
-               w8_skinny_rows: int = 16) -> StepRoute:
+               w8_skinny_rows: int = 16, verify_fp8_multi: bool = False) -> StepRoute:
     """``have_*``: the model holds such copies at all; ``o_packed`` / ``o_fp8``: of ``l0.o``;
     ``ar_fusable``: the comm's one-shot all-reduce can ride in a GEMM producing ``B * S * hidden``
     outputs; ``capturing``: the current stream is capturing a graph.  The rest are the model's
@@ -114,7 +114,8 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
     (csrc/lora_linear.hip).  Off (q / k / v adapters only, or none): every decision below is as before.
     ``w4_all``: ``w4_rows="all"`` -- the int4 codes serve every row count (``ProjTiers.w4g``).
     ``w8_skinny`` / ``w8_skinny_rows``: ``w8_decode="skinny"`` and its row bound (``ProjTiers.w8s``); no other
-    decision reads them."""
+    decision reads them.  ``verify_fp8_multi``: ``verify_fp8="multi"`` -- an e4m3 cache's verify steps may take
+    ``multi`` (``ops.decode_attention_multi_fp8``); off, or on a bf16 cache, nothing changes."""
     T = B * S
     proj = proj_tiers(T, have_packed, have_w4, have_fp8, w4_max_rows, have_w8, w4_all, w8_skinny, w8_skinny_rows)
     # TP = 1: the residual add rides in the o / down epilogues (h = r + a Wo^T, r' = h + g Wd^T), so
@@ -143,10 +144,11 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
     # a verify step (all_rows: every row's candidates) of a few positions per sequence: its attention
     # runs split-KV on the matrix cores with the T positions x G heads of a KV head on one MFMA's lane
     # columns (ops.decode_attention_multi); MLS_VERIFY_ATTN=ctx keeps the chunk kernel (the A/B arm).
-    # Chunked prefill (all_rows False) stays on flash_attention_ctx.  An e4m3 cache has no verify kernel
-    # of its own: its verify steps take the context kernel too (ops.flash_attention_ctx_fp8, split-KV).
+    # Chunked prefill (all_rows False) stays on flash_attention_ctx.  An e4m3 cache's verify steps take the
+    # context kernel too (ops.flash_attention_ctx_fp8, split-KV) unless verify_fp8="multi" opts into the
+    # verify kernel of that cache (ops.decode_attention_multi_fp8), under the same conditions.
     multi = (has_past and all_rows and verify_attn != "ctx" and S <= spec_max_tokens
-             and S * (hq // max(hkv, 1)) <= 16 and not kv_fp8)
+             and S * (hq // max(hkv, 1)) <= 16 and (not kv_fp8 or verify_fp8_multi))
     # TP prefill: two batch halves interleaved so each o / down all-reduce overlaps the other half's
     # compute (LlamaTP._prefill_overlapped); MLS_TP_OVERLAP=0 runs the plain layer loop
     overlap = not decode and not has_past and tp > 1 and B >= 2 and T >= 64 and tp_overlap and not capturing

@@ -107,6 +107,7 @@ _SIGS = {
     "mls_flash_attention_ctx_fp8_split": [P, P, P, P, P, P, P, L, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F,
                                           P],
     "mls_decode_attention_multi": [P, P, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F, P],
+    "mls_decode_attention_multi_fp8": [P, P, P, P, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F, P],
     "mls_decode_combine": [P, P, P, I, P, I, I, I, I, P],
     "mls_skinny_gemm": [P, P, P, P, P, P, SZ, I, I, I, I, I, P],
     "mls_mgemm": [P, P, P, P, P, P, SZ, I, I, I, I, I, I, P], "mls_mgemm_auto_split": [I, I, I],
@@ -171,7 +172,8 @@ def _bind(lib: ctypes.CDLL) -> None:
 
 DEBUG = os.environ.get("MLS_DEBUG", "0") == "1"
 DEBUG_TUS = ("attention", "norm_ops", "stem_pool", "conv3x3_halo", "kv_fp8", "flash_ctx", "decode_verify",
-             "decode_pick", "spec_step", "lora", "lora_linear")  # translation units with MLS_CHECK bounds
+             "decode_verify_fp8", "decode_pick", "spec_step", "lora",
+             "lora_linear")  # translation units with MLS_CHECK bounds
 DEBUG_CODES = {
     101: "rope/KV append: cache slot beyond the cache",
     102: "rope/KV append: position beyond the RoPE table",
@@ -186,6 +188,10 @@ DEBUG_CODES = {
     321: "decode attention (multi): not 0 <= past[b] <= lens[b] <= the rows of a slot / the split grid (max_len)",
     322: "decode attention (multi): slot outside the cache",
     323: "decode attention (multi): page id outside the pool",
+    324: "decode attention (multi, fp8 cache): not 0 <= past[b] <= lens[b] <= the rows of a slot / the split grid "
+         "(max_len)",
+    325: "decode attention (multi, fp8 cache): slot outside the cache",
+    326: "decode attention (multi, fp8 cache): page id outside the pool",
     401: "decode pick: winning candidate index outside [0, tp * k) (a row of NaN candidates)",
     411: "spec draft: rows[r] is not a serving slot",
     412: "spec draft / accept: token count or history column outside the prompt / history arrays",

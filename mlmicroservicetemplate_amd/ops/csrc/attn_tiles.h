@@ -226,6 +226,25 @@ MLS_DEV void decode_pv(f32x4 (&o)[DecodeDims::DT], bf16x8 pf, const char* V, int
   }
 }
 
+// The e4m3 cache's two conversions (decode_attn_fp8_kernel in kv_fp8.hip, decode_verify_fp8_kernel in
+// decode_verify_fp8.hip).  8 e4m3 bytes -> 8 bf16 (exact)
+MLS_DEV bf16x8 fp8x8_to_bf16(uint32_t d0, uint32_t d1) {
+  const f32x2 f0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, false);
+  const f32x2 f1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, true);
+  const f32x2 f2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, false);
+  const f32x2 f3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, true);
+  bf16x8 r;
+  r[0] = (bf16)f0[0]; r[1] = (bf16)f0[1]; r[2] = (bf16)f1[0]; r[3] = (bf16)f1[1];
+  r[4] = (bf16)f2[0]; r[5] = (bf16)f2[1]; r[6] = (bf16)f3[0]; r[7] = (bf16)f3[1];
+  return r;
+}
+// 16 e4m3 bytes (dims 16 cch .. + 15 of key row krow of the wave) -> 32 B of the wave's padded V image
+MLS_DEV void decode_v_fill_fp8(char* V, int krow, int cch, uint4 v) {
+  *reinterpret_cast<uint4*>(V + krow * DecodeDims::VST + cch * 32) = __builtin_bit_cast(uint4, fp8x8_to_bf16(v.x, v.y));
+  *reinterpret_cast<uint4*>(V + krow * DecodeDims::VST + cch * 32 + 16) =
+      __builtin_bit_cast(uint4, fp8x8_to_bf16(v.z, v.w));
+}
+
 // Merge the block's waves through LDS once each has stored (mt, ls) of column fr in sm_m / sm_l and its O
 // rows (columns 4g + j) in sm_o -- that store stays in the kernels: through this struct one instantiation
 // paired its ds_write_b32 differently.  A sequence that fits one split (`direct`) gets its output row,

@@ -62,18 +62,6 @@ MLS_DEV float kv_fp8_quant_store(const float (&x)[8], int c, uint8_t* row, float
   return scale;
 }
 
-// 8 e4m3 bytes -> 8 bf16 (exact)
-MLS_DEV bf16x8 fp8x8_to_bf16(uint32_t d0, uint32_t d1) {
-  const f32x2 f0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, false);
-  const f32x2 f1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, true);
-  const f32x2 f2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, false);
-  const f32x2 f3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, true);
-  bf16x8 r;
-  r[0] = (bf16)f0[0]; r[1] = (bf16)f0[1]; r[2] = (bf16)f1[0]; r[3] = (bf16)f1[1];
-  r[4] = (bf16)f2[0]; r[5] = (bf16)f2[1]; r[6] = (bf16)f3[0]; r[7] = (bf16)f3[1];
-  return r;
-}
-
 // ------------------------------------------------------------------------------- prefill writer
 // Block = one token.  Phase 1 is rope_kv_kernel's rotation; phase 2 gives each of the token's
 // 2 Hkv head rows to 16 lanes (8 dims each): |max| by DPP, convert, 8-B stores.
@@ -334,8 +322,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_attn_fp8_kernel(const Decod
     const int krow = 8 * i + (lane >> 3), cch = lane & 7;
     uint4 v = vraw[i];
     if (rope && w0 + krow == L - 1) v = *reinterpret_cast<const uint4*>(&newq[1][cch * 16]);
-    *reinterpret_cast<uint4*>(V + krow * VST + cch * 32) = __builtin_bit_cast(uint4, fp8x8_to_bf16(v.x, v.y));
-    *reinterpret_cast<uint4*>(V + krow * VST + cch * 32 + 16) = __builtin_bit_cast(uint4, fp8x8_to_bf16(v.z, v.w));
+    decode_v_fill_fp8(V, krow, cch, v);
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's image, read back by the same wave
   bf16x8 pf;  // P with the key's V scale folded in (a masked key: p = 0 and scale 0)

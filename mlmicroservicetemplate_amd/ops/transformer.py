@@ -267,6 +267,7 @@ def _flash_attention_ctx(op: str, need_caches, qkv, caches, past, lens, batch: i
         raise ValueError("qkv shape does not match batch/seq/heads")
     if past.numel() != batch or lens.numel() != batch:
         raise ValueError(f"past and lens must have {batch} elements")
+    need_caches(*caches, n_kv_heads, head_dim, dev)
     blocks, rows = caches[0].shape[0], caches[0].shape[2]
     if slot_ids is not None:
         _need(slot_ids, "slot_ids", torch.int32, dev)
@@ -343,6 +344,86 @@ def flash_attention_ctx(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
                                 workspace)
 
 
+def _need_kv_multi(k_cache, v_cache, n_kv_heads: int, head_dim: int, dev) -> None:
+    """The bf16 KV cache :func:`decode_attention_multi` reads: head-major ``[blocks, Hkv, R, 128]``."""
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
+        raise ValueError("k_cache and v_cache must be 4-d and of the same shape")
+    if k_cache.shape[1] != n_kv_heads or k_cache.shape[3] != head_dim:
+        raise ValueError(f"decode_attention_multi reads head-major caches [blocks, Hkv={n_kv_heads}, rows, {head_dim}] "
+                         f"only (a row-major cache is not supported), got {tuple(k_cache.shape)}")
+
+
+def _decode_attention_multi(op: str, cache_dtype, need_caches, qkv, caches, past, lens, batch: int, seq: int,
+                            n_q_heads: int, n_kv_heads: int, head_dim: int, slot_ids, page_table, chunk, max_len, scale,
+                            workspace, out):
+    """The body of :func:`decode_attention_multi` and :func:`decode_attention_multi_fp8`: ``op`` names the
+    caller in the messages and the library's entry point ``mls_<op>``, ``caches`` = (k_cache, v_cache[,
+    k_scale, v_scale]) of ``cache_dtype`` as the entry point takes them, ``need_caches(*caches, n_kv_heads,
+    head_dim, dev)`` checks their shapes."""
+    dev = qkv.device
+    _need(qkv, "qkv", torch.bfloat16, dev)
+    _need(caches[0], "k_cache", cache_dtype, dev)
+    _need(caches[1], "v_cache", cache_dtype, dev)
+    _need(past, "past", torch.int32, dev)
+    _need(lens, "lens", torch.int32, dev)
+    if batch <= 0 or seq <= 0 or n_kv_heads <= 0 or n_q_heads % n_kv_heads:
+        raise ValueError("batch, seq > 0 and Hq a multiple of Hkv")
+    if head_dim != 128:
+        raise ValueError(f"{op}: head_dim must be 128, got {head_dim}")
+    G = n_q_heads // n_kv_heads
+    if G not in (1, 2, 4, 8) or seq * G > 16:
+        raise ValueError(f"{op}: Hq / Hkv in 1, 2, 4, 8 and seq * Hq / Hkv <= 16 "
+                         f"(got seq {seq}, Hq / Hkv {n_q_heads} / {n_kv_heads})")
+    W = (n_q_heads + 2 * n_kv_heads) * head_dim
+    if qkv.dim() != 2 or tuple(qkv.shape) != (batch * seq, W):
+        raise ValueError("qkv shape does not match batch/seq/heads")
+    if past.numel() != batch or lens.numel() != batch:
+        raise ValueError(f"past and lens must have {batch} elements")
+    need_caches(*caches, n_kv_heads, head_dim, dev)
+    blocks, rows = caches[0].shape[0], caches[0].shape[2]
+    if slot_ids is not None:
+        _need(slot_ids, "slot_ids", torch.int32, dev)
+        if slot_ids.numel() != batch:
+            raise ValueError(f"slot_ids must have {batch} elements")
+    if chunk not in (64, 128):
+        raise ValueError(f"{op}: splits of 64 or 128 rows, got {chunk}")
+    if page_table is not None:
+        _need(page_table, "page_table", torch.int32, dev)
+        if page_table.dim() != 2:
+            raise ValueError("page_table must be [slots, pages_per_seq]")
+        if rows != 64 or chunk != 64:
+            raise ValueError(f"paged {op}: pages and splits of 64 rows, got {rows} / {chunk}")
+        slots, pps = page_table.shape
+        cap = pps * 64
+    else:
+        slots, pps, cap = blocks, 0, rows
+    if slot_ids is None and batch > slots:
+        raise ValueError("the cache holds fewer slots than the batch")
+    max_len = cap if max_len is None else max(1, min(int(max_len), cap))
+    nsplit = (max_len + chunk - 1) // chunk
+    if nsplit > 1024:
+        raise ValueError(f"{op}: at most 1024 splits (max_len {max_len} / chunk {chunk})")
+    n_o = batch * seq * n_q_heads * nsplit * head_dim
+    need = n_o // head_dim * (head_dim + 2)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=dev, dtype=torch.float32)
+    _need(workspace, "workspace", torch.float32, dev)
+    if out is not None:
+        _need(out, "out", torch.bfloat16, dev)
+        if tuple(out.shape) != (batch * seq, n_q_heads * head_dim) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [B*S, Hq*D]")
+    else:
+        out = torch.empty(batch * seq, n_q_heads * head_dim, device=dev, dtype=torch.bfloat16)
+    scale = head_dim ** -0.5 if scale is None else scale
+    rc = getattr(lib(), f"mls_{op}")(qkv.data_ptr(), *(t.data_ptr() for t in caches), out.data_ptr(),
+                                     workspace.data_ptr(), workspace[n_o:].data_ptr(), W, out.stride(0),
+                                     past.data_ptr(), lens.data_ptr(), _ptr(slot_ids), _ptr(page_table), pps, slots,
+                                     batch, seq, n_q_heads, n_kv_heads, head_dim, blocks, rows, max_len, chunk,
+                                     float(scale), stream_ptr(dev))
+    check(rc, f"mls_{op}")
+    return out
+
+
 def decode_attention_multi(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, past: torch.Tensor,
                            lens: torch.Tensor, batch: int, seq: int, n_q_heads: int, n_kv_heads: int, head_dim: int, *,
                            slot_ids: Optional[torch.Tensor] = None, page_table: Optional[torch.Tensor] = None,
@@ -357,72 +438,9 @@ def decode_attention_multi(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: to
     Hq / Hkv in 1, 2, 4, 8.  ``chunk``: cache rows per split block, 64 or 128 (paged: 64, one page);
     ``max_len``: a host bound on ``lens`` (default: what a slot holds) that sizes the split grid, as
     :func:`decode_attention` takes it.  ``workspace``: fp32, ``B*seq*Hq*nsplit*(D+2)`` elements."""
-    dev = qkv.device
-    _need(qkv, "qkv", torch.bfloat16, dev)
-    _need(k_cache, "k_cache", torch.bfloat16, dev)
-    _need(v_cache, "v_cache", torch.bfloat16, dev)
-    _need(past, "past", torch.int32, dev)
-    _need(lens, "lens", torch.int32, dev)
-    if batch <= 0 or seq <= 0 or n_kv_heads <= 0 or n_q_heads % n_kv_heads:
-        raise ValueError("batch, seq > 0 and Hq a multiple of Hkv")
-    if head_dim != 128:
-        raise ValueError(f"decode_attention_multi: head_dim must be 128, got {head_dim}")
-    G = n_q_heads // n_kv_heads
-    if G not in (1, 2, 4, 8) or seq * G > 16:
-        raise ValueError(f"decode_attention_multi: Hq / Hkv in 1, 2, 4, 8 and seq * Hq / Hkv <= 16 "
-                         f"(got seq {seq}, Hq / Hkv {n_q_heads} / {n_kv_heads})")
-    W = (n_q_heads + 2 * n_kv_heads) * head_dim
-    if qkv.dim() != 2 or tuple(qkv.shape) != (batch * seq, W):
-        raise ValueError("qkv shape does not match batch/seq/heads")
-    if past.numel() != batch or lens.numel() != batch:
-        raise ValueError(f"past and lens must have {batch} elements")
-    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
-        raise ValueError("k_cache and v_cache must be 4-d and of the same shape")
-    if k_cache.shape[1] != n_kv_heads or k_cache.shape[3] != head_dim:
-        raise ValueError(f"decode_attention_multi reads head-major caches [blocks, Hkv={n_kv_heads}, rows, {head_dim}] "
-                         f"only (a row-major cache is not supported), got {tuple(k_cache.shape)}")
-    blocks, rows = k_cache.shape[0], k_cache.shape[2]
-    if slot_ids is not None:
-        _need(slot_ids, "slot_ids", torch.int32, dev)
-        if slot_ids.numel() != batch:
-            raise ValueError(f"slot_ids must have {batch} elements")
-    if chunk not in (64, 128):
-        raise ValueError(f"decode_attention_multi: splits of 64 or 128 rows, got {chunk}")
-    if page_table is not None:
-        _need(page_table, "page_table", torch.int32, dev)
-        if page_table.dim() != 2:
-            raise ValueError("page_table must be [slots, pages_per_seq]")
-        if rows != 64 or chunk != 64:
-            raise ValueError(f"paged decode_attention_multi: pages and splits of 64 rows, got {rows} / {chunk}")
-        slots, pps = page_table.shape
-        cap = pps * 64
-    else:
-        slots, pps, cap = blocks, 0, rows
-    if slot_ids is None and batch > slots:
-        raise ValueError("the cache holds fewer slots than the batch")
-    max_len = cap if max_len is None else max(1, min(int(max_len), cap))
-    nsplit = (max_len + chunk - 1) // chunk
-    if nsplit > 1024:
-        raise ValueError(f"decode_attention_multi: at most 1024 splits (max_len {max_len} / chunk {chunk})")
-    n_o = batch * seq * n_q_heads * nsplit * head_dim
-    need = n_o // head_dim * (head_dim + 2)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, device=dev, dtype=torch.float32)
-    _need(workspace, "workspace", torch.float32, dev)
-    if out is not None:
-        _need(out, "out", torch.bfloat16, dev)
-        if tuple(out.shape) != (batch * seq, n_q_heads * head_dim) or not out.is_contiguous():
-            raise ValueError("out must be a contiguous [B*S, Hq*D]")
-    else:
-        out = torch.empty(batch * seq, n_q_heads * head_dim, device=dev, dtype=torch.bfloat16)
-    scale = head_dim ** -0.5 if scale is None else scale
-    rc = lib().mls_decode_attention_multi(qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(),
-                                          workspace.data_ptr(), workspace[n_o:].data_ptr(), W, out.stride(0),
-                                          past.data_ptr(), lens.data_ptr(), _ptr(slot_ids), _ptr(page_table), pps,
-                                          slots, batch, seq, n_q_heads, n_kv_heads, head_dim, blocks, rows, max_len,
-                                          chunk, float(scale), stream_ptr(dev))
-    check(rc, "mls_decode_attention_multi")
-    return out
+    return _decode_attention_multi("decode_attention_multi", torch.bfloat16, _need_kv_multi, qkv, (k_cache, v_cache),
+                                   past, lens, batch, seq, n_q_heads, n_kv_heads, head_dim, slot_ids, page_table, chunk,
+                                   max_len, scale, workspace, out)
 
 
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, lens: torch.Tensor,
@@ -649,6 +667,26 @@ def decode_attention_fp8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.
     if not combine:
         return out, DecodePartials(ws, ws_ml, nsplit, chunk, lens, n_q_heads, head_dim)
     return out
+
+
+def decode_attention_multi_fp8(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: torch.Tensor,
+                               v_scale: torch.Tensor, past: torch.Tensor, lens: torch.Tensor, batch: int, seq: int,
+                               n_q_heads: int, n_kv_heads: int, head_dim: int, *,
+                               slot_ids: Optional[torch.Tensor] = None, page_table: Optional[torch.Tensor] = None,
+                               chunk: int = 64, max_len: Optional[int] = None, scale: Optional[float] = None,
+                               workspace: Optional[torch.Tensor] = None,
+                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`decode_attention_multi` on an FP8 (e4m3) cache -- the verify step's attention with
+    ``kv_dtype="fp8"``: the contract, arguments, refusals and workspace are that function's; the caches are
+    :func:`rope_kv_fp8_`'s (head-major uint8 ``[slots, Hkv, max_seq, 128]`` or page pools ``[pages, Hkv, 64,
+    128]``, fp32 scales of the same shape without the last dimension), and the step's own rows must have been
+    appended by it first.  One block streams a split's K / V rows once for the ``seq`` positions and the
+    Hq / Hkv heads of a KV head.  A row is attended as its e4m3 values with the K scale on the fp32 score and
+    the V scale folded into P; the oracle is ``reference.attention_ctx`` on ``reference.kv_dequant_fp8`` of the
+    same bytes."""
+    return _decode_attention_multi("decode_attention_multi_fp8", torch.uint8, _need_kv_fp8, qkv,
+                                   (k_cache, v_cache, k_scale, v_scale), past, lens, batch, seq, n_q_heads,
+                                   n_kv_heads, head_dim, slot_ids, page_table, chunk, max_len, scale, workspace, out)
 
 
 def skinny_packed_combine(attn_out: torch.Tensor, parts: DecodePartials, wp: torch.Tensor, N: int, *,

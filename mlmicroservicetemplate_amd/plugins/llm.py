@@ -80,6 +80,7 @@ class LlamaPlugin(ModelPlugin):
         if self.prefill_chunk and kv_dtype == "fp8" and kv_prefill != "cache":  # LlamaTP.check_prefill_chunk's rule
             raise ValueError("prefill_chunk is not available with kv_dtype: fp8 (a chunk would attend e4m3 context "
                              "rows where one-shot prefill attends unquantised ones)")
+        verify_fp8 = self.parse_verify_fp8(extra, kv_dtype, kv_prefill)
         kv_pages = self._kv_pages(extra.get("kv_pages", 0), cfg, tp, max_batch, max_seq, dev, backend, kv_dtype)
         if tp > 1 and kv_pages:  # the scheduler replays rank 0's admissions: every pool must be equal
             from ..parallel import dist as mdist
@@ -88,7 +89,7 @@ class LlamaPlugin(ModelPlugin):
         self.model = llama.LlamaTP(params, cfg, tp=tp, rank=ctx.rank, comm=llama.TPComm(None, tp, device=dev), backend=backend,
                                    device=dev, max_batch=max_batch, max_seq=max_seq, kv_pages=kv_pages,
                                    kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_prefill=kv_prefill, lora=lora_kw,
-                                   w4_rows=w4_rows, w8_decode=w8_decode)
+                                   w4_rows=w4_rows, w8_decode=w8_decode, verify_fp8=verify_fp8)
         for index, (name, path) in enumerate(lora_paths.items()):  # every rank reads the adapter and keeps its share (load_adapter)
             from ..utils.checkpoint import load_lora_adapter
 
@@ -117,9 +118,9 @@ class LlamaPlugin(ModelPlugin):
                 self.engine.start()
         self.kv_pages = kv_pages
         logger.info("llama ready: tp=%d rank=%d backend=%s device=%s kv_dtype=%s kv_prefill=%s kv_bytes_per_token=%d "
-                    "weight_dtype=%s w4_rows=%s w8_decode=%s layer_weight_bytes=%d prefix_cache=%s", tp, ctx.rank, backend,
-                    dev, kv_dtype, kv_prefill, self.kv_page_bytes(cfg, tp, backend, kv_dtype) // 64, weight_dtype,
-                    w4_rows, w8_decode, self.model.layer_weight_bytes(), self.prefix_cache)
+                    "weight_dtype=%s w4_rows=%s w8_decode=%s layer_weight_bytes=%d prefix_cache=%s verify_fp8=%s", tp,
+                    ctx.rank, backend, dev, kv_dtype, kv_prefill, self.kv_page_bytes(cfg, tp, backend, kv_dtype) // 64,
+                    weight_dtype, w4_rows, w8_decode, self.model.layer_weight_bytes(), self.prefix_cache, verify_fp8)
 
     @staticmethod
     def parse_weight_dtype(extra: dict) -> str:
@@ -153,6 +154,19 @@ class LlamaPlugin(ModelPlugin):
             raise ValueError(f"w8_decode must be 'tile' or 'skinny', got {mode!r}")
         if mode != "tile" and weight_dtype != "w8a8":
             raise ValueError(f"w8_decode: {mode} is for weight_dtype: w8a8 only, got {weight_dtype!r}")
+        return mode
+
+    @staticmethod
+    def parse_verify_fp8(extra: dict, kv_dtype: str, kv_prefill: str) -> str:
+        """MODEL_CONFIG ``verify_fp8`` (with ``kv_dtype: fp8`` and ``kv_prefill: cache`` only): ``ctx`` (default: a
+        speculation step's attention on ``flash_attention_ctx_fp8``) | ``multi`` (on the e4m3 verify kernel
+        ``decode_attention_multi_fp8``; :class:`~..models.llama.LlamaTP`)."""
+        mode = str(extra.get("verify_fp8", "ctx"))
+        if mode not in ("ctx", "multi"):
+            raise ValueError(f"verify_fp8 must be 'ctx' or 'multi', got {mode!r}")
+        if mode != "ctx" and (kv_dtype != "fp8" or kv_prefill != "cache"):
+            raise ValueError(f"verify_fp8: {mode} is for kv_dtype: fp8 with kv_prefill: cache only, got "
+                             f"{kv_dtype!r} / {kv_prefill!r}")
         return mode
 
     @staticmethod

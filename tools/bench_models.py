@@ -70,18 +70,30 @@ def bench_verify_attn(args):
     """Kernel alone: ``ops.decode_attention_multi`` at T = 2, 3, 4 against ``ops.decode_attention`` (one query,
     matrix-core kernel, no RoPE / append prologue: q and the cache are used as they are) and
     ``ops.flash_attention_ctx`` at S = T.  Hq 32 / Hkv 8; every arm interleaved after a warm floor; us per call
-    from events around ``--steps`` back-to-back launches, median and minimum of 5 windows.  The same K / V are
-    re-read by every launch, so the numbers are L2-warm."""
+    from events around one replay of a graph of ``--steps`` launches, median and minimum of 5 windows.  The same
+    K / V are re-read by every launch, so the numbers are L2-warm.  ``--kv-dtype fp8`` adds the e4m3 cache's two verify
+    routes on the same rows: ``ops.decode_attention_multi_fp8`` and ``ops.flash_attention_ctx_fp8`` with the
+    split count ``LlamaTP`` gives a verify step."""
     from mlmicroservicetemplate_amd import ops
+    from mlmicroservicetemplate_amd.models.llama import LlamaTP
+    from mlmicroservicetemplate_amd.ops import reference as R
 
     dev = torch.device("cuda:0")
     Hq, Hkv, D, N = 32, 8, 128, args.steps
 
-    def window(fn):
+    def graphed(fn):  # N launches captured once (every buffer is the arm's own: nothing is allocated or cleared)
+        fn()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            for _ in range(N):
+                fn()
+        return graph.replay
+
+    def window(replay):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        for _ in range(N):
-            fn()
+        replay()
         e1.record()
         e1.synchronize()
         return e0.elapsed_time(e1) * 1e3 / N
@@ -99,13 +111,18 @@ def bench_verify_attn(args):
                 else:
                     kc = torch.randn(B, Hkv, rows, D, device=dev, generator=g).to(torch.bfloat16)
                 vc = torch.randn_like(kc)
+                if args.kv_dtype == "fp8":  # the same rows as the e4m3 cache holds them: (k, v, k_scale, v_scale)
+                    (k8, ks8), (v8, vs8) = R.kv_quant_fp8(kc), R.kv_quant_fp8(vc)
+                    c8 = (k8, v8, ks8, vs8)
                 lens = torch.full((B,), ctx, dtype=torch.int32, device=dev)
                 W = (Hq + 2 * Hkv) * D
                 q1 = torch.randn(B, W, device=dev, generator=g).to(torch.bfloat16)
                 ws1 = torch.empty(B * Hq * (rows // 64 + 1) * (D + 2), device=dev, dtype=torch.float32)
                 o1 = torch.empty(B, Hq * D, device=dev, dtype=torch.bfloat16)
+                cnt = torch.zeros(B * Hkv, device=dev, dtype=torch.int32)
                 arms = {"decode_T1": lambda: ops.decode_attention(q1, kc, vc, lens, Hq, Hkv, D, chunk=64, head_major=True,
-                                                                  workspace=ws1, out=o1, max_len=ctx, page_table=table)}
+                                                                  workspace=ws1, out=o1, max_len=ctx, page_table=table,
+                                                                  counters=cnt)}
                 for T in (2, 3, 4):
                     past = torch.full((B,), ctx - T, dtype=torch.int32, device=dev)
                     qT = torch.randn(B * T, W, device=dev, generator=g).to(torch.bfloat16)
@@ -116,6 +133,16 @@ def bench_verify_attn(args):
                         qT, kc, vc, past, lens, B, T, Hq, Hkv, D, page_table=table, max_len=ctx, workspace=wsT, out=oT))
                     arms[f"ctx_S{T}"] = (lambda T=T, past=past, qT=qT, oC=oC: ops.flash_attention_ctx(
                         qT, kc, vc, past, lens, B, T, Hq, Hkv, D, page_table=table, out=oC))
+                    if args.kv_dtype == "fp8":  # the e4m3 cache's two verify routes (LlamaTP.verify_fp8) on the same rows
+                        o8, oC8 = torch.empty_like(oT), torch.empty_like(oT)
+                        arms[f"multi_fp8_T{T}"] = (lambda T=T, past=past, qT=qT, wsT=wsT, o8=o8: ops.decode_attention_multi_fp8(
+                            qT, *c8, past, lens, B, T, Hq, Hkv, D, page_table=table, max_len=ctx, workspace=wsT, out=o8))
+                        ns = LlamaTP.ctx_split_rule(B, T, Hq, ctx)  # as LlamaTP._ctx_split_kw(verify=True) routes it
+                        kw8 = {} if ns <= 1 else dict(splits=ns, max_ctx=ctx, workspace=torch.empty(
+                            ops.flash_ctx_workspace_elems(B, T, Hq, D, ns), device=dev, dtype=torch.float32))
+                        arms[f"ctx_fp8_S{T}"] = (lambda T=T, past=past, qT=qT, oC8=oC8, kw8=kw8: ops.flash_attention_ctx_fp8(
+                            qT, *c8, past, lens, B, T, Hq, Hkv, D, page_table=table, out=oC8, **kw8))
+                arms = {a: graphed(fn) for a, fn in arms.items()}
                 _warm(lambda: [fn() for fn in arms.values()], args.warm_ms)
                 res = {a: [] for a in arms}
                 for _ in range(5):
@@ -195,7 +222,7 @@ def bench_llama_prefix(args):
         raise SystemExit("--shared-prefix measures the paged cache: give --kv-pages")
     p = init_llama_shard(LLAMA3_8B, 1, 0, seed=0, device=dev)
     m = LlamaTP(p, LLAMA3_8B, backend="fused", device=dev, max_batch=B, max_seq=args.max_seq, kv_pages=args.kv_pages,
-                kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows, w8_decode=args.w8_decode,
+                kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows, w8_decode=args.w8_decode, verify_fp8=args.verify_fp8,
                 kv_prefill=args.kv_prefill)
     del p
     shared = np.random.default_rng(1).integers(1000, 100000, N).tolist()
@@ -266,7 +293,7 @@ def bench_llama(args):
     p = init_llama_shard(LLAMA3_8B, tp, 0, seed=0, device=dev)
     comm = ShardEmulationComm(tp) if tp > 1 else None
     m = LlamaTP(p, LLAMA3_8B, tp=tp, rank=0, comm=comm, backend="fused", device=dev, max_batch=max(args.batches),
-                max_seq=args.max_seq, kv_pages=args.kv_pages, kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows, w8_decode=args.w8_decode,
+                max_seq=args.max_seq, kv_pages=args.kv_pages, kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows, w8_decode=args.w8_decode, verify_fp8=args.verify_fp8,
                 kv_prefill=args.kv_prefill)
     if m.pages is not None and args.shuffle_pages:  # pages scattered as in a long-running server
         import random
@@ -326,7 +353,7 @@ def bench_llama_lora(args):
     t0 = time.time()
     p = init_llama_shard(cfg, 1, 0, seed=0, device=dev)
     kw = dict(backend="fused", device=dev, max_batch=max(max(args.batches), 8), max_seq=args.max_seq,
-              kv_pages=args.kv_pages, kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows, w8_decode=args.w8_decode, kv_prefill=args.kv_prefill)
+              kv_pages=args.kv_pages, kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows, w8_decode=args.w8_decode, verify_fp8=args.verify_fp8, kv_prefill=args.kv_prefill)
     plain = LlamaTP(p, cfg, **kw)
     lora = {"max_adapters": args.lora, "max_rank": args.lora_rank}
     mods = ("q", "k", "v")
@@ -425,9 +452,13 @@ def _bench_speculate(m, args, K, B, S, ids, lens, tok, cur):
     feed = torch.randint(1000, 100000, (B, T), device=dev, dtype=torch.int32)
     n = torch.full((B,), T, device=dev, dtype=torch.int32)
     arms = {"decode": lambda: m.decode_step(tok, cur, 1, max_ctx=S + 1)}
+    fp8_arms = m.kv_fp8 and m.kv_prefill == "cache"  # an e4m3 cache: the routes are LlamaTP.verify_fp8's
     for route in ("multi", "ctx"):  # the verify step's two attention routes (LlamaTP.verify_attn; a graph per route)
         def step(route=route):
-            m.verify_attn = route
+            if fp8_arms:
+                m.verify_fp8 = route
+            else:
+                m.verify_attn = route
             return m.verify_step(feed, lens, n, 1, max_ctx=S + T)
 
         step()
@@ -442,14 +473,16 @@ def _bench_speculate(m, args, K, B, S, ids, lens, tok, cur):
                 f()
             torch.cuda.synchronize()
             times[a].append((time.perf_counter() - t0) / args.steps * 1e3)
-    m.verify_attn = "multi"
+    m.verify_attn, m.verify_fp8 = "multi", args.verify_fp8
     med = {a: float(np.median(v)) for a, v in times.items()}
     print(json.dumps({"bench": "llama3-8b-verify", "batch": B, "prompt": S, "T": T, "kv_pages": args.kv_pages,
                       "weight_dtype": args.weight_dtype, "w4_rows": args.w4_rows, "w8_decode": args.w8_decode, "kv_dtype": args.kv_dtype, "kv_prefill": args.kv_prefill,
                       **{a + "_ms": round(v, 3) for a, v in med.items()},
                       **{a + "_ms_min": round(min(times[a]), 3) for a in times},
                       # accepted drafts per step above which a verify step yields more tokens per ms than a decode step
-                      "break_even_accepted_per_step": round(med["verify_multi"] / med["decode"] - 1, 3)}), flush=True)
+                      "verify_fp8": args.verify_fp8,
+                      "break_even_accepted_per_step": round(
+                          med["verify_" + (args.verify_fp8 if fp8_arms else "multi")] / med["decode"] - 1, 3)}), flush=True)
     if args.spec_device:
         _bench_spec_device(m, args, K, B, S, ids, lens)
     if not args.spec_accept:
@@ -533,7 +566,7 @@ def bench_llama_serve(args):
     B = args.batches[0]
     p = init_llama_shard(LLAMA3_8B, 1, 0, seed=0, device=dev)
     m = LlamaTP(p, LLAMA3_8B, backend="fused", device=dev, max_batch=B, max_seq=args.max_seq, kv_pages=args.kv_pages,
-                kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows, w8_decode=args.w8_decode,
+                kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows, w8_decode=args.w8_decode, verify_fp8=args.verify_fp8,
                 kv_prefill=args.kv_prefill)
     eng = ContinuousLlama(m).start()
     rng = np.random.default_rng(0)
@@ -585,6 +618,9 @@ def main():
     ap.add_argument("--w8-decode", choices=["tile", "skinny"], default="tile",
                     help="llama, --weight-dtype w8a8: steps of <= 16 rows on quant_rows_fp8 + gemm_w8a8, or on the "
                          "weight-streaming skinny_w8 kernel")
+    ap.add_argument("--verify-fp8", choices=["ctx", "multi"], default="ctx",
+                    help="llama, --kv-dtype fp8 --kv-prefill cache: a verify step's attention on flash_attention_ctx_fp8, "
+                         "or on the e4m3 verify kernel decode_attention_multi_fp8 (--speculate times both arms)")
     ap.add_argument("--weight-dtype", choices=["bf16", "int4", "w8a8"], default="bf16",
                     help="llama: layer projections in bf16, W4A16 (4-bit codes, one bf16 scale per row and 128 k), or "
                          "W8A8 (e4m3 weights per channel, e4m3 activations per row, block-scaled MFMA)")
