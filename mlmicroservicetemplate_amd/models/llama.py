@@ -1049,16 +1049,21 @@ class LlamaTP:
         wq, ws, _ = self.w8[name]
         return R.w8a8_linear(h, wq, ws, rstd)
 
-    def _ref_forward(self, ids: torch.Tensor, positions: torch.Tensor, lens: torch.Tensor, B: int, S: int,
-                     decode: bool, k: int, slot_ids: Optional[torch.Tensor] = None,
-                     past: Optional[torch.Tensor] = None, all_rows: bool = False):
+    def _ref_trunk(self, ids: torch.Tensor, positions: torch.Tensor, lens: torch.Tensor, B: int, S: int,
+                   decode: bool, slot_ids: Optional[torch.Tensor], past: Optional[torch.Tensor]) -> torch.Tensor:
+        """Embedding, layers and the final RMSNorm of every row (fp32)."""
         x = self._embed(ids.reshape(-1))
         for i in range(self.cfg.layers):
             x = self._ref_layer(i, x, B, S, positions.reshape(-1), lens, slot_ids, decode, past)
-        xn = R.layernorm(x, self.p["final_norm"], None, eps=self.cfg.eps, rms=True)[0]
+        return R.layernorm(x, self.p["final_norm"], None, eps=self.cfg.eps, rms=True)[0]
+
+    def _ref_forward(self, ids: torch.Tensor, positions: torch.Tensor, lens: torch.Tensor, B: int, S: int,
+                     decode: bool, k: int, slot_ids: Optional[torch.Tensor] = None,
+                     past: Optional[torch.Tensor] = None, all_rows: bool = False):
+        xn = self._ref_trunk(ids, positions, lens, B, S, decode, slot_ids, past)
         if not decode and not all_rows:
             n = lens.long() if past is None else lens.long() - past.long()  # valid rows of this forward
-            last = (torch.arange(B, device=x.device) * S + n - 1)
+            last = (torch.arange(B, device=xn.device) * S + n - 1)
             xn = xn[last]
         logits = xn @ self.p["lm_head"].float().T
         return self._local_topk(logits, k)
@@ -1377,6 +1382,28 @@ class LlamaTP:
         for decode-shaped token counts (<= 16) each pre-norm + residual add rides inside the skinny
         GEMM (``ops.gemm_rmsnorm``: 7 launches per layer); larger counts run a gain-free RMSNorm and
         the library / native GEMM (``ops.linear``).  Which kernels: :meth:`_route`."""
+        ops = self.ops
+        r, delta = self._fused_trunk(ids, positions, lens, B, S, decode, slot_ids, past, all_rows, max_ctx)
+        if not decode and not all_rows:  # each sequence's last valid token (one native gather of r and delta)
+            rows = lens if past is None else lens - past  # valid rows of this forward (on the device)
+            if delta is None:
+                r = ops.last_rows(r, rows, B, S)
+            else:
+                r, delta = ops.last_rows(r, rows, B, S, delta)
+        # the lm_head down the same ladder at its own row count (B, or every row of the step with all_rows):
+        # never int4; r + delta is not written back; above 16 rows -- 1 GB of weights -- the weight-streaming
+        # native tile up to 64 rows, the tile GEMM above (delta is None there when the residual adds rode
+        # in the o / down epilogues: int4 steps of 25-32 rows)
+        nb = r.shape[0]
+        head = proj_tiers(nb, bool(self.packed), False, bool(self.fp8), 0)
+        logits, _ = self._norm_proj(head, r, "lm_head", delta, resid_out=False, impl="native" if nb <= 64 else "auto")
+        return self._local_topk(logits, k)
+
+    def _fused_trunk(self, ids: torch.Tensor, positions: torch.Tensor, lens: torch.Tensor, B: int, S: int,
+                     decode: bool, slot_ids: Optional[torch.Tensor], past: Optional[torch.Tensor], all_rows: bool,
+                     max_ctx: Optional[int]):
+        """Embedding and layers of :meth:`_fused_forward`: the residual stream of every row and the last
+        row-parallel output not yet added to it (or None)."""
         ops, cfg = self.ops, self.cfg
         rt = self._route(B, S, decode, past is not None, all_rows)
         pos = positions.reshape(-1)
@@ -1407,21 +1434,7 @@ class LlamaTP:
                     self._lora_fused(i, qkv, st)
                 a, parts = self._fused_attention(i, qkv, st)
                 self._layer_tail(i, st, a, parts)
-        r, delta = st.r, st.delta
-        if not decode and not all_rows:  # each sequence's last valid token (one native gather of r and delta)
-            rows = lens if past is None else lens - past  # valid rows of this forward (on the device)
-            if delta is None:
-                r = ops.last_rows(r, rows, B, S)
-            else:
-                r, delta = ops.last_rows(r, rows, B, S, delta)
-        # the lm_head down the same ladder at its own row count (B, or every row of the step with all_rows):
-        # never int4; r + delta is not written back; above 16 rows -- 1 GB of weights -- the weight-streaming
-        # native tile up to 64 rows, the tile GEMM above (delta is None there when the residual adds rode
-        # in the o / down epilogues: int4 steps of 25-32 rows)
-        nb = r.shape[0]
-        head = proj_tiers(nb, bool(self.packed), False, bool(self.fp8), 0)
-        logits, _ = self._norm_proj(head, r, "lm_head", delta, resid_out=False, impl="native" if nb <= 64 else "auto")
-        return self._local_topk(logits, k)
+        return st.r, st.delta
 
     def _prefill_overlapped(self, rt: StepRoute, r, pos, lens, B: int, S: int, explicit_slots):
         """TP prefill as two batch halves (micro-batches) interleaved layer by layer so that every
@@ -1766,6 +1779,8 @@ class LlamaTP:
         if all_rows and past is None:
             raise ValueError("all_rows needs past (a verify step reads its context from the cache)")
         ids, positions, lens = ids.contiguous(), positions.contiguous(), lens.contiguous()
+        # score() repeats this preamble (past for kv_prefill="cache", check_prefill_chunk, the page table) in front
+        # of the same trunk: a change here belongs there too
         if past is None and not decode and self.kv_prefill == "cache":
             past = torch.zeros(B, dtype=torch.int32, device=self.device)  # one shot = the chunk at past 0
         if past is not None:
@@ -1828,6 +1843,64 @@ class LlamaTP:
         B, S = ids.shape
         pos = torch.arange(S, device=self.device, dtype=torch.int32).unsqueeze(0).expand(B, S).contiguous()
         return self.step(ids, pos, lens, decode=False, k=k)
+
+    @torch.no_grad()
+    def score(self, ids: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+        """Log-likelihood of given text: ids int ``[B, S]`` (right-padded), lens ``[B]`` -> fp32 ``[B, S]`` whose
+        position ``i >= 1`` of row ``b`` holds ``log p(ids[b, i] | ids[b, :i])`` for ``i < lens[b]``; position 0
+        and padding hold 0.  One prompt forward as :meth:`generate`'s one-shot prefill runs it (the rows land in
+        cache rows ``0 .. B - 1``), every row kept; the head is the gain-free final RMSNorm and
+        ``ops.linear_logprob`` (csrc/lm_logprob.hip) -- no ``[rows, vocab]`` logits exist -- then one all-gather of
+        the ranks' ``[B * S, 3]`` triples and ``ops.reference.logprob_merge``.  The reference backend takes the
+        same triples from its full fp32 logits.  Call it on every rank, as :meth:`generate`.  Whatever the model
+        was built with (int4 / w8a8 weights, an e4m3 cache, LoRA slots) applies.  ``ValueError`` for a batch or
+        sequence beyond the KV cache: nothing falls back."""
+        B, S = ids.shape
+        if B > self.max_batch or S > self.max_seq:
+            raise ValueError(f"batch / sequence ({B}, {S}) exceed the KV cache ({self.max_batch}, {self.max_seq})")
+        lens_host = lens.detach().to("cpu")
+        if lens_host.numel() != B or int(lens_host.min()) < 1 or int(lens_host.max()) > S:
+            raise ValueError(f"lens must be in [1, {S}] for each of the {B} sequences")
+        dev, sd = self.device, self.sd
+        ids = ids.to(dev).to(torch.int32).contiguous()
+        lens = lens.to(dev).to(torch.int32).contiguous()
+        pos = torch.arange(S, device=dev, dtype=torch.int32).unsqueeze(0).expand(B, S).contiguous()
+        # row (b, i) is scored against ids[b, i + 1] while i + 1 < lens[b]; -1: not scored
+        nxt = torch.cat([ids[:, 1:], ids.new_full((B, 1), -1)], dim=1)
+        targets = torch.where(pos + 1 < lens.unsqueeze(1), nxt, torch.full_like(nxt, -1)).reshape(-1)
+        # step()'s preamble for a one-shot prefill, and generate()'s page assignment around it (kept in step with both)
+        past = torch.zeros(B, dtype=torch.int32, device=dev) if self.kv_prefill == "cache" else None
+        if past is not None:
+            self.check_prefill_chunk()
+        valid = max(0, min(sd.vocab_shard, self.cfg.vocab - sd.vocab_lo))
+        assigned = 0
+        try:
+            if self.pages is not None:
+                for b in range(B):
+                    self.pages.assign(b, S)
+                    assigned = b + 1
+                self.pages.device_table()
+            with tracing.range("llama.score"):
+                if self.backend == "fused":
+                    ops = self.ops
+                    r, delta = self._fused_trunk(ids, pos, lens, B, S, False, None, past, False, None)
+                    if delta is None:
+                        xn = ops.rmsnorm(r, self.ones, eps=self.cfg.eps)
+                    else:
+                        xn = ops.rmsnorm(delta, self.ones, residual=r, eps=self.cfg.eps)
+                    part = ops.linear_logprob(xn, self.p["lm_head"], targets, lo=sd.vocab_lo, valid=valid,
+                                              vocab=self.cfg.vocab)
+                else:
+                    xn = self._ref_trunk(ids, pos, lens, B, S, False, None, past)
+                    part = R.linear_logprob(xn, self.p["lm_head"], targets, sd.vocab_lo, valid)
+        finally:
+            if self.pages is not None:
+                for b in range(assigned):
+                    self.pages.release(b)
+        lp = R.logprob_merge(self.comm.all_gather(part))
+        lp = torch.where(targets >= 0, lp, torch.zeros_like(lp)).view(B, S)
+        # row (b, i) scored token i + 1: shift so position i holds its own token's log-probability
+        return torch.cat([lp.new_zeros(B, 1), lp[:, :-1]], dim=1)
 
     def gather_candidates(self, vals: torch.Tensor, idx: torch.Tensor):
         """X4 all-gather of every rank's local top-k -> ``[B, tp*k]`` values / ids (host tensors)."""

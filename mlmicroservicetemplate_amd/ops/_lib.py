@@ -129,6 +129,8 @@ _SIGS = {
     "mls_quant_rows_fp8": [P, P, P, P, P, I, I, I, F, P],
     "mls_skinny_w8": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, I, P],
     "mls_skinny_w8_num_variants": [],
+    "mls_linear_logprob": [P, P, P, P, _c.c_longlong, I, I, I, I, I, I, I, P],
+    "mls_logprob_merge": [P, P, I, I, P],
     "mls_lora_split": [I, I, I, I],
     "mls_lora_shrink": [P, I, P, P, P, P, P, SZ, I, I, I, I, I, I, I, P],
     "mls_lora_expand": [P, I, P, P, P, P, P, P, SZ, I, I, I, F, I, I, I, I, I, I, I, I, P],
@@ -173,7 +175,7 @@ def _bind(lib: ctypes.CDLL) -> None:
 DEBUG = os.environ.get("MLS_DEBUG", "0") == "1"
 DEBUG_TUS = ("attention", "norm_ops", "stem_pool", "conv3x3_halo", "kv_fp8", "flash_ctx", "decode_verify",
              "decode_verify_fp8", "decode_pick", "spec_step", "lora",
-             "lora_linear")  # translation units with MLS_CHECK bounds
+             "lora_linear", "lm_logprob")  # translation units with MLS_CHECK bounds
 DEBUG_CODES = {
     101: "rope/KV append: cache slot beyond the cache",
     102: "rope/KV append: position beyond the RoPE table",
@@ -206,6 +208,7 @@ DEBUG_CODES = {
     512: "lora_linear: a tile names an adapter outside [0, max_adapters)",
     513: "lora_linear: a tile names a row outside [-1, rows)",
     514: "lora_linear: an adapter's rank table does not fit the pack (not written by LoraLinearPack.load)",
+    515: "linear_logprob: a target id outside [-1, vocab)",
 }
 
 

@@ -213,6 +213,39 @@ def gelu(x):
     return F.gelu(x)
 
 
+# ------------------------------------------------------------------ prompt scoring (log-likelihood of given tokens)
+def linear_logprob(xn: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, lo: int = 0,
+                   valid: Optional[int] = None) -> torch.Tensor:
+    """``ops.linear_logprob``'s ``[M, 3]`` triple ``(m, s, t)`` of one vocabulary shard, in the dtype the product
+    ``xn @ w.T`` has once promoted to at least fp32 (float64 inputs stay float64): the max over the shard's first
+    ``valid`` columns, the sum of ``exp(logit - m)`` over them, and the logit of column ``targets - lo`` (``-inf``
+    for a target of -1, outside the shard or in its padded tail)."""
+    dt = torch.float64 if xn.dtype == torch.float64 else torch.float32
+    logits = xn.to(dt) @ w.to(dt).T
+    N = logits.shape[1]
+    valid = N if valid is None else int(valid)
+    ninf = torch.full((), float("-inf"), dtype=dt, device=logits.device)
+    logits = torch.where(torch.arange(N, device=logits.device) < valid, logits, ninf)
+    m = logits.max(dim=1).values if N else ninf.expand(logits.shape[0])
+    ms = torch.where(torch.isinf(m), torch.zeros_like(m), m)  # a shard that is all padding: m = -inf, s = 0
+    s = torch.exp(logits - ms.unsqueeze(1)).sum(dim=1)
+    tl = targets.long() - int(lo)
+    ok = (targets.long() >= 0) & (tl >= 0) & (tl < valid)
+    t = torch.where(ok, logits.gather(1, tl.clamp(0, max(N - 1, 0)).unsqueeze(1)).squeeze(1), ninf)
+    return torch.stack([m, s, t], dim=1)
+
+
+def logprob_merge(parts: torch.Tensor) -> torch.Tensor:
+    """``[ranks, M, 3]`` shard triples of :func:`linear_logprob` -> ``[M]`` ``log p(target | row) = t - m - log s``
+    of the whole vocabulary: each shard's ``s`` rescaled by ``exp(m_i - m)``, the one finite ``t`` kept.  A row
+    whose target no shard holds (``-1``) gives ``-inf``."""
+    m_i, s_i, t_i = parts.unbind(dim=-1)
+    m = m_i.max(dim=0).values
+    ms = torch.where(torch.isinf(m), torch.zeros_like(m), m)
+    s = (s_i * torch.exp(m_i - ms)).sum(dim=0)
+    return t_i.max(dim=0).values - m - torch.log(s)
+
+
 # ------------------------------------------------------------------ LoRA on the q/k/v projection
 LORA_MODULES = ("q", "k", "v")
 LORA_MAX_RANK = 64

@@ -49,6 +49,55 @@ def softmax_rows(x: torch.Tensor, mask: Optional[torch.Tensor] = None, rows_per_
     return out
 
 
+LOGPROB_BN = 256  # csrc/lm_logprob.hip's column tile: one (m, s, t) triple per row and LOGPROB_BN columns
+
+
+def logprob_workspace_elems(M: int, N: int) -> int:
+    """fp32 elements of :func:`linear_logprob`'s tile slab for ``M`` rows against ``N`` columns."""
+    return -(-int(N) // LOGPROB_BN) * int(M) * 3
+
+
+def linear_logprob(xn: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, *, lo: int = 0,
+                   valid: Optional[int] = None, workspace: Optional[torch.Tensor] = None, vocab: Optional[int] = None,
+                   tile: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The log-likelihood pieces of ``xn @ w.T`` for one vocabulary shard, the logits never stored
+    (csrc/lm_logprob.hip): ``[M, 3]`` fp32 ``(m, s, t)`` per row -- the max over the shard's columns below
+    ``valid``, the sum of ``exp(logit - m)`` over them, and the logit of column ``targets[row] - lo`` (``-inf`` for
+    a target of -1, outside ``[lo, lo + valid)``).  ``log p = t - m - log s`` once the shards are folded
+    (``ops.reference.logprob_merge``).  ``xn [M, K]``, ``w [N, K]`` bf16, ``targets [M]`` int32 global ids;
+    ``K % 128 == 0``.  ``workspace``: fp32, at least :func:`logprob_workspace_elems` elements (allocated when
+    absent); ``vocab``: the bound a debug build holds the target ids to (default ``lo + N``); ``tile``: 0 picks
+    the row tile by ``M``, 1 / 2 force the 256- / 64-row kernel (A/B runs)."""
+    dev = xn.device
+    _need(xn, "xn", torch.bfloat16, dev)
+    _need(w, "w", torch.bfloat16, dev)
+    _need(targets, "targets", torch.int32, dev)
+    if xn.dim() != 2 or w.dim() != 2 or xn.shape[1] != w.shape[1] or targets.shape != (xn.shape[0],):
+        raise ValueError(f"linear_logprob: xn {tuple(xn.shape)}, w {tuple(w.shape)}, targets {tuple(targets.shape)}")
+    (M, K), N = xn.shape, w.shape[0]
+    valid = N if valid is None else int(valid)
+    need = logprob_workspace_elems(M, N)
+    if workspace is None:
+        workspace = torch.empty(need, device=dev, dtype=torch.float32)
+    else:
+        _need(workspace, "workspace", torch.float32, dev)
+        if workspace.numel() < need:
+            raise ValueError(f"linear_logprob: workspace holds {workspace.numel()} elements, {need} needed")
+    if out is None:
+        out = torch.empty(M, 3, device=dev, dtype=torch.float32)
+    else:
+        _need(out, "out", torch.float32, dev)
+        if tuple(out.shape) != (M, 3):
+            raise ValueError(f"linear_logprob: out must be [{M}, 3], got {tuple(out.shape)}")
+    st = stream_ptr(dev)
+    check(lib().mls_linear_logprob(xn.data_ptr(), w.data_ptr(), targets.data_ptr(), workspace.data_ptr(),
+                                   workspace.numel(), M, N, K, int(lo), valid,
+                                   int(lo) + N if vocab is None else int(vocab), int(tile), st), "mls_linear_logprob")
+    check(lib().mls_logprob_merge(workspace.data_ptr(), out.data_ptr(), M, -(-N // LOGPROB_BN), st),
+          "mls_logprob_merge")
+    return out
+
+
 def topk_large(x: torch.Tensor, k: int, max_chunk: int = 16384, *, lo: int = 0,
                valid: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Raw-logit top-k of rows longer than one LDS-resident row (LM heads): split each row into

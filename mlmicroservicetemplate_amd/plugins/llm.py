@@ -5,6 +5,8 @@ Request: ``{"prompt": str | "input_ids": [int], "max_new_tokens": int, "top_k": 
 leave the running decode batch at every step (``models/llama_serving.py``); otherwise
 concurrent requests are micro-batched (same batcher as ``/predict``), right-padded and generated
 together (batched prefill with per-sequence lengths, then lockstep decode steps).
+``"score": true`` asks for the prompt's own log-likelihood instead (``LlamaTP.score``: ``{"input_ids",
+"logprobs", "nll", "tokens"}``); it is served on the micro-batched path at TP = 1 and refused elsewhere.
 
 Multi-GPU: rank 0 owns HTTP.  For each batch it broadcasts a small command header and the
 token ids to the other ranks (X5); every rank then runs the same TP forward, and the
@@ -23,6 +25,13 @@ from ..models.llama_serving import OP_GENERATE, OP_ITER, OP_STOP
 from .base import ModelPlugin, PluginContext, register
 
 logger = logging.getLogger("mlsamd.plugin")
+
+
+class _Score:
+    """What a ``"score": true`` request carries through the batcher in place of its GenParams."""
+
+    def __init__(self, adapter: int = -1):
+        self.adapter = adapter
 
 
 @register("llama")
@@ -281,6 +290,19 @@ class LlamaPlugin(ModelPlugin):
             ids = [int(i) for i in req["input_ids"]]
         else:
             ids = self.tok.encode(str(req["prompt"]))
+        score = req.get("score", False)
+        if not isinstance(score, bool):
+            raise ValueError(f"score must be true or false, got {score!r}")
+        if score:  # the log-likelihood of the prompt itself (LlamaTP.score); max_new_tokens is ignored
+            if self.engine is not None or self.model.tp > 1:
+                raise ValueError("score: true is served by the lockstep batch path at TP = 1 only "
+                                 "(CONTINUOUS_BATCHING=0): the continuous engine admits no score requests and the "
+                                 "TP followers have no score command")
+            if not ids:
+                raise ValueError("empty prompt")
+            if len(ids) > self.model.max_seq:
+                raise ValueError(f"score: {len(ids)} tokens exceed max_seq {self.model.max_seq}")
+            return ids, _Score(self.adapter_index(req.get("adapter")))
         gp = GenParams(max_new_tokens=int(req.get("max_new_tokens", self.ctx.settings.MAX_NEW_TOKENS)),
                        top_k=int(req.get("top_k", 1)), temperature=float(req.get("temperature", 1.0)),
                        seed=int(req.get("seed", 0)), adapter=self.adapter_index(req.get("adapter")))
@@ -320,6 +342,8 @@ class LlamaPlugin(ModelPlugin):
         return out
 
     def finish_generate(self, out: Any) -> dict:
+        if isinstance(out, dict):  # a score request's result (_score_batch)
+            return out
         prompt_len, toks = out
         eos = set(self.cfg.eos_ids)
         cut = next((i + 1 for i, t in enumerate(toks) if t in eos), len(toks))
@@ -329,11 +353,18 @@ class LlamaPlugin(ModelPlugin):
     def replicas(self):
         def run_batch(samples):
             groups: Dict[tuple, List[int]] = {}
+            scored: Dict[int, List[int]] = {}  # adapter -> the batch's score requests
             for i, (_ids, gp) in enumerate(samples):
                 if not isinstance(gp.adapter, int):
                     raise ValueError(f"a request names one adapter index, got {gp.adapter!r}")
-                groups.setdefault((gp.top_k, gp.temperature, gp.seed, gp.adapter), []).append(i)
+                if isinstance(gp, _Score):
+                    scored.setdefault(gp.adapter, []).append(i)
+                else:
+                    groups.setdefault((gp.top_k, gp.temperature, gp.seed, gp.adapter), []).append(i)
             results: List[Any] = [None] * len(samples)
+            for adapter, members in scored.items():
+                for i, res in zip(members, self._score_batch([samples[i][0] for i in members], adapter)):
+                    results[i] = res
             for _key, members in groups.items():
                 ids_l = [samples[i][0] for i in members]
                 gp = samples[members[0]][1]
@@ -377,6 +408,24 @@ class LlamaPlugin(ModelPlugin):
             out = self.model.generate(ids, lens, gp, prefill_chunk=self.prefill_chunk, speculate=self.speculate,
                                       drafter=self._drafter(), **self._spec_device_kw())
         return out.cpu().tolist()
+
+    def _score_batch(self, ids_l: List[List[int]], adapter: int = -1) -> List[dict]:
+        """``"score": true`` requests of one lockstep batch: right-padded, one :meth:`LlamaTP.score`."""
+        S, B = max(len(t) for t in ids_l), len(ids_l)
+        ids = torch.zeros(B, S, dtype=torch.int32)
+        for i, t in enumerate(ids_l):
+            ids[i, : len(t)] = torch.tensor(t, dtype=torch.int32)
+        lens = torch.tensor([len(t) for t in ids_l], dtype=torch.int32)
+        with self._lock:
+            if self.model.lora_loaded or adapter != -1:
+                self.model.set_batch_adapters(B, adapter)
+            lp = self.model.score(ids, lens).double().cpu()
+        out = []
+        for i, t in enumerate(ids_l):
+            row = lp[i, : len(t)]
+            out.append({"input_ids": list(t), "logprobs": row.tolist(), "nll": float(-row.sum()),
+                        "tokens": len(t) - 1})
+        return out
 
     # ---- the continuous engine's TP control channel (models/llama_serving.py ContinuousLlama):
     # explicit headers only when no decode step carried one; admissions only when there are any
