@@ -533,7 +533,7 @@ class LlamaTP:
                  comm: Optional[TPComm] = None, backend: str = "reference", device="cpu", max_batch: int = 8,
                  max_seq: int = 1024, top_k_max: int = 50, kv_pages: int = 0, kv_dtype: str = "bf16",
                  weight_dtype: str = "bf16", kv_prefill: str = "rows", lora: Optional[dict] = None,
-                 w4_rows: str = "decode", w8_decode: str = "tile", verify_fp8: str = "ctx"):
+                 w4_rows: str = "decode", w8_decode: str = "tile", verify_fp8: str = "ctx", verify_cols: int = 16):
         """``lora={"max_adapters": n, "max_rank": r}``: room for n LoRA adapters of rank <= r on the q / k / v
         projections, chosen per cache slot (:meth:`load_adapter`, :meth:`set_slot_adapter`,
         ``GenParams.adapter``); until one is loaded neither backend computes anything new.
@@ -594,7 +594,12 @@ class LlamaTP:
         ``ops.flash_attention_ctx_fp8`` split-KV, wherever a bf16 cache would take ``ops.decode_attention_multi``
         (positions x Hq / Hkv <= 16, ``MLS_VERIFY_ATTN`` not ``ctx``).  Same cache bytes, same scales; P is
         rounded to bf16 with the V scale folded in, as the decode step does.  The reference backend accepts and
-        ignores it."""
+        ignores it.
+        ``verify_cols=64`` (16 or 64; default 16; bf16 cache only): the bound on a verify step's positions x
+        Hq / Hkv -- :meth:`check_speculate` admits ``(speculate + 1) * Hq / Hkv <= verify_cols``, and the fused
+        backend's verify steps above 16 columns attend through ``ops.decode_attention_wide``
+        (``csrc/decode_verify_wide.hip``); steps of <= 16 columns run as with 16.  The reference backend accepts
+        it and computes the same."""
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
         if weight_dtype not in ("bf16", "int4", "w8a8"):
@@ -617,6 +622,12 @@ class LlamaTP:
         if verify_fp8 != "ctx" and (kv_dtype != "fp8" or kv_prefill != "cache"):
             raise ValueError(f"verify_fp8={verify_fp8!r} is for kv_dtype='fp8' with kv_prefill='cache' only, got "
                              f"{kv_dtype!r} / {kv_prefill!r}")
+        if verify_cols not in (16, 64) or isinstance(verify_cols, bool):
+            raise ValueError(f"verify_cols must be 16 or 64, got {verify_cols!r}")
+        if verify_cols != 16 and kv_dtype == "fp8":
+            raise ValueError(f"verify_cols={verify_cols} is for kv_dtype='bf16' only: the e4m3 verify kernel stops at "
+                             "16 columns")
+        self.verify_cols = int(verify_cols)
         self.kv_dtype = kv_dtype
         self.kv_prefill = kv_prefill
         self.weight_dtype = weight_dtype
@@ -1079,7 +1090,7 @@ class LlamaTP:
             head_dim=cfg.head_dim, hidden=cfg.hidden, have_packed=bool(self.packed), have_w4=bool(self.w4),
             have_w8=bool(self.w8), w4_all=self.w4_rows == "all",
             w8_skinny=self.w8_decode == "skinny", w8_skinny_rows=self.w8_skinny_rows,
-            verify_fp8_multi=self.verify_fp8 == "multi",
+            verify_fp8_multi=self.verify_fp8 == "multi", verify_cols=self.verify_cols,
             have_fp8=bool(self.fp8), o_packed="l0.o" in self.packed, o_fp8="l0.o" in self.fp8, kv_fp8=self.kv_fp8,
             w4_max_rows=self.w4_max_rows, pk_fold=self.pk_fold, prefill_fold=self.prefill_fold,
             fuse_combine=self.fuse_combine, fuse_add_norm=self.fuse_add_norm, ar_fuse=self.ar_fuse,
@@ -1288,6 +1299,9 @@ class LlamaTP:
         if st.rt.multi and self.kv_fp8:
             return ops.decode_attention_multi_fp8(qkv, kc, vc, self.k_scale[i], self.v_scale[i], st.past, st.lens, st.B,
                                                   st.S, sd.hq, sd.hkv, D, **st.attn_kw), None
+        if st.rt.wide:  # verify_cols=64: more than 16 positions x Hq / Hkv columns
+            return ops.decode_attention_wide(qkv, kc, vc, st.past, st.lens, st.B, st.S, sd.hq, sd.hkv, D,
+                                             **st.attn_kw), None
         if st.rt.multi:
             return ops.decode_attention_multi(qkv, kc, vc, st.past, st.lens, st.B, st.S, sd.hq, sd.hkv, D,
                                               **st.attn_kw), None
@@ -1650,9 +1664,9 @@ class LlamaTP:
             raise ValueError(str(e).replace("chunked prefill", "speculative decoding")) from None
         if self.backend == "fused":
             G = self.sd.hq // max(self.sd.hkv, 1)
-            if G not in (1, 2, 4, 8) or (speculate + 1) * G > 16:
+            if G not in (1, 2, 4, 8) or (speculate + 1) * G > self.verify_cols:
                 raise ValueError(f"speculative decoding on the fused backend needs Hq / Hkv in 1, 2, 4, 8 and "
-                                 f"(speculate + 1) * Hq / Hkv <= 16 (got speculate {speculate}, "
+                                 f"(speculate + 1) * Hq / Hkv <= {self.verify_cols} (got speculate {speculate}, "
                                  f"{self.sd.hq} / {self.sd.hkv} heads on this rank)")
 
     def check_prefix_cache(self) -> None:
@@ -1699,7 +1713,7 @@ class LlamaTP:
         """Captured verify step for B sequences of T positions under the context bound ctx (static id /
         past / lens / slot buffers, as :meth:`_decode_graph`).  Warm-up and capture run with
         ``lens == past``: every row is padding, so no cache row is written."""
-        key = (B, T, k, ctx, self.verify_attn, self.verify_fp8)  # one graph per attention route (A/B arms)
+        key = (B, T, k, ctx, self.verify_attn, self.verify_fp8, self.verify_cols)  # one graph per attention route
         if key in self._ver_graphs:
             return self._ver_graphs[key]
         dev = self.device
@@ -2387,7 +2401,7 @@ class LlamaTP:
         (default the model's).  Warm-up runs the forward on scratch inputs with ``lens == past`` (every
         row is padding: no cache row is written, no slot state touched)."""
         eos = tuple(sorted(self.cfg.eos_ids if eos is None else eos))
-        key = ("serve_spec", Bv, T, k, ctx, self.verify_attn, self.verify_fp8, tuple(ngram), eos)
+        key = ("serve_spec", Bv, T, k, ctx, self.verify_attn, self.verify_fp8, self.verify_cols, tuple(ngram), eos)
         hit = self._dev_graphs.get(key)
         if hit is not None:
             return hit[0]

@@ -79,6 +79,7 @@ class StepRoute:
     overlap: bool       # TP prefill as two interleaved batch halves
     dec_chunk: int      # decode split rows
     lora_tail: bool = False  # a loaded adapter targets o / gate / up / down: the tail runs unfused around the deltas
+    wide: bool = False  # a multi step of more than 16 columns (verify_cols=64): ops.decode_attention_wide
 
     @property
     def fuse(self) -> bool:
@@ -103,7 +104,7 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
                fuse_add_norm: bool, ar_fuse: bool, tp_overlap: bool, verify_attn: str, spec_max_tokens: int,
                dec_chunk: int, ar_fusable: bool, capturing: bool, kv_fp8: bool = False,
                have_w8: bool = False, lora_tail: bool = False, w4_all: bool = False, w8_skinny: bool = False,
-               w8_skinny_rows: int = 16, verify_fp8_multi: bool = False) -> StepRoute:
+               w8_skinny_rows: int = 16, verify_fp8_multi: bool = False, verify_cols: int = 16) -> StepRoute:
     """``have_*``: the model holds such copies at all; ``o_packed`` / ``o_fp8``: of ``l0.o``;
     ``ar_fusable``: the comm's one-shot all-reduce can ride in a GEMM producing ``B * S * hidden``
     outputs; ``capturing``: the current stream is capturing a graph.  The rest are the model's
@@ -115,7 +116,9 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
     ``w4_all``: ``w4_rows="all"`` -- the int4 codes serve every row count (``ProjTiers.w4g``).
     ``w8_skinny`` / ``w8_skinny_rows``: ``w8_decode="skinny"`` and its row bound (``ProjTiers.w8s``); no other
     decision reads them.  ``verify_fp8_multi``: ``verify_fp8="multi"`` -- an e4m3 cache's verify steps may take
-    ``multi`` (``ops.decode_attention_multi_fp8``); off, or on a bf16 cache, nothing changes."""
+    ``multi`` (``ops.decode_attention_multi_fp8``); off, or on a bf16 cache, nothing changes.
+    ``verify_cols``: the bound on a multi step's S * Hq / Hkv columns, 16 or 64 (a bf16 cache only); above 16
+    columns the step is ``wide`` (``ops.decode_attention_wide``)."""
     T = B * S
     proj = proj_tiers(T, have_packed, have_w4, have_fp8, w4_max_rows, have_w8, w4_all, w8_skinny, w8_skinny_rows)
     # TP = 1: the residual add rides in the o / down epilogues (h = r + a Wo^T, r' = h + g Wd^T), so
@@ -148,7 +151,9 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
     # context kernel too (ops.flash_attention_ctx_fp8, split-KV) unless verify_fp8="multi" opts into the
     # verify kernel of that cache (ops.decode_attention_multi_fp8), under the same conditions.
     multi = (has_past and all_rows and verify_attn != "ctx" and S <= spec_max_tokens
-             and S * (hq // max(hkv, 1)) <= 16 and (not kv_fp8 or verify_fp8_multi))
+             and S * (hq // max(hkv, 1)) <= verify_cols and (not kv_fp8 or verify_fp8_multi))
+    # verify_cols=64: the columns past one MFMA's 16 lie on up to four column tiles of the same block
+    wide = multi and S * (hq // max(hkv, 1)) > 16
     # TP prefill: two batch halves interleaved so each o / down all-reduce overlaps the other half's
     # compute (LlamaTP._prefill_overlapped); MLS_TP_OVERLAP=0 runs the plain layer loop
     overlap = not decode and not has_past and tp > 1 and B >= 2 and T >= 64 and tp_overlap and not capturing
@@ -164,4 +169,5 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
     if w4_all:  # the two-half TP prefill was not run in this mode: the plain layer loop serves it
         overlap = False
     return StepRoute(proj=proj, fold=bool(fold), fuse_combine=bool(combine), ar_fuse=bool(ar), fuse_rn=bool(fuse_rn),
-                     multi=bool(multi), overlap=bool(overlap), dec_chunk=chunk, lora_tail=bool(lora_tail))
+                     multi=bool(multi), overlap=bool(overlap), dec_chunk=chunk, lora_tail=bool(lora_tail),
+                     wide=bool(wide))

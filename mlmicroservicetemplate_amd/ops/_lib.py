@@ -108,6 +108,7 @@ _SIGS = {
                                           P],
     "mls_decode_attention_multi": [P, P, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F, P],
     "mls_decode_attention_multi_fp8": [P, P, P, P, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F, P],
+    "mls_decode_attention_wide": [P, P, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F, P],
     "mls_decode_combine": [P, P, P, I, P, I, I, I, I, P],
     "mls_skinny_gemm": [P, P, P, P, P, P, SZ, I, I, I, I, I, P],
     "mls_mgemm": [P, P, P, P, P, P, SZ, I, I, I, I, I, I, P], "mls_mgemm_auto_split": [I, I, I],
@@ -175,7 +176,7 @@ def _bind(lib: ctypes.CDLL) -> None:
 DEBUG = os.environ.get("MLS_DEBUG", "0") == "1"
 DEBUG_TUS = ("attention", "norm_ops", "stem_pool", "conv3x3_halo", "kv_fp8", "flash_ctx", "decode_verify",
              "decode_verify_fp8", "decode_pick", "spec_step", "lora",
-             "lora_linear", "lm_logprob")  # translation units with MLS_CHECK bounds
+             "lora_linear", "lm_logprob", "decode_verify_wide")  # translation units with MLS_CHECK bounds
 DEBUG_CODES = {
     101: "rope/KV append: cache slot beyond the cache",
     102: "rope/KV append: position beyond the RoPE table",
@@ -194,6 +195,9 @@ DEBUG_CODES = {
          "(max_len)",
     325: "decode attention (multi, fp8 cache): slot outside the cache",
     326: "decode attention (multi, fp8 cache): page id outside the pool",
+    327: "decode attention (wide): not 0 <= past[b] <= lens[b] <= the rows of a slot / the split grid (max_len)",
+    328: "decode attention (wide): slot outside the cache",
+    329: "decode attention (wide): page id outside the pool",
     401: "decode pick: winning candidate index outside [0, tp * k) (a row of NaN candidates)",
     411: "spec draft: rows[r] is not a serving slot",
     412: "spec draft / accept: token count or history column outside the prompt / history arrays",

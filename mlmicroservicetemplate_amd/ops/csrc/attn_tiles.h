@@ -253,8 +253,10 @@ MLS_DEV void decode_v_fill_fp8(char* V, int krow, int cch, uint4 v) {
 // C = G (the single-token kernels): column = query head hh of the KV head, one output row per sequence.
 // C > G (decode_verify_kernel): nq queries per sequence, column = query * G + head; output / partial row
 // b * nq + query, so the partials of a sequence are those of nq * Hq heads of one row.
+// TILED (decode_verify_wide_kernel): the image holds the C columns c0 .. c0 + C - 1 of nq * G -- one call per
+// column tile, so the image stays C = 16 columns however many the block serves.  Off, c0 is not read.
 namespace {
-template <int G, int WAVES, int C = G>
+template <int G, int WAVES, int C = G, bool TILED = false>
 struct DecodeMerge {
   using T = DecodeTile<G, WAVES>;
   static constexpr int D = T::D;
@@ -271,13 +273,13 @@ struct DecodeMerge {
   const int& hk;
   const int& sp;
   const int& tid;
-  __device__ void operator()(bool direct, int nq = 1) const {
+  __device__ void operator()(bool direct, int nq = 1, int c0 = 0) const {
     __syncthreads();
-    const int cols = C == G ? G : nq * G;
+    const int cols = C == G ? G : TILED ? min(C, nq * G - c0) : nq * G;
     for (int idx = tid; idx < cols * D; idx += T::NT) {
       const int cc = idx / D, d = idx % D;
-      const int hh = C == G ? cc : cc % G;
-      const long row = C == G ? (long)b : (long)b * nq + cc / G;
+      const int hh = C == G ? cc : TILED ? (c0 + cc) % G : cc % G;
+      const long row = C == G ? (long)b : TILED ? (long)b * nq + (c0 + cc) / G : (long)b * nq + cc / G;
       float M = -INFINITY;
 #pragma unroll
       for (int p = 0; p < WAVES; ++p) M = fmaxf(M, sm_m[p][cc]);

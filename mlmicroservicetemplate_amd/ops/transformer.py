@@ -355,11 +355,12 @@ def _need_kv_multi(k_cache, v_cache, n_kv_heads: int, head_dim: int, dev) -> Non
 
 def _decode_attention_multi(op: str, cache_dtype, need_caches, qkv, caches, past, lens, batch: int, seq: int,
                             n_q_heads: int, n_kv_heads: int, head_dim: int, slot_ids, page_table, chunk, max_len, scale,
-                            workspace, out):
-    """The body of :func:`decode_attention_multi` and :func:`decode_attention_multi_fp8`: ``op`` names the
+                            workspace, out, cols: int = 16):
+    """The body of :func:`decode_attention_multi`, :func:`decode_attention_multi_fp8` and
+    :func:`decode_attention_wide`: ``op`` names the
     caller in the messages and the library's entry point ``mls_<op>``, ``caches`` = (k_cache, v_cache[,
     k_scale, v_scale]) of ``cache_dtype`` as the entry point takes them, ``need_caches(*caches, n_kv_heads,
-    head_dim, dev)`` checks their shapes."""
+    head_dim, dev)`` checks their shapes, ``cols`` is the entry point's limit on ``seq * Hq / Hkv``."""
     dev = qkv.device
     _need(qkv, "qkv", torch.bfloat16, dev)
     _need(caches[0], "k_cache", cache_dtype, dev)
@@ -371,8 +372,8 @@ def _decode_attention_multi(op: str, cache_dtype, need_caches, qkv, caches, past
     if head_dim != 128:
         raise ValueError(f"{op}: head_dim must be 128, got {head_dim}")
     G = n_q_heads // n_kv_heads
-    if G not in (1, 2, 4, 8) or seq * G > 16:
-        raise ValueError(f"{op}: Hq / Hkv in 1, 2, 4, 8 and seq * Hq / Hkv <= 16 "
+    if G not in (1, 2, 4, 8) or seq * G > cols or seq > 16:
+        raise ValueError(f"{op}: Hq / Hkv in 1, 2, 4, 8 and seq * Hq / Hkv <= {cols} "
                          f"(got seq {seq}, Hq / Hkv {n_q_heads} / {n_kv_heads})")
     W = (n_q_heads + 2 * n_kv_heads) * head_dim
     if qkv.dim() != 2 or tuple(qkv.shape) != (batch * seq, W):
@@ -441,6 +442,20 @@ def decode_attention_multi(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: to
     return _decode_attention_multi("decode_attention_multi", torch.bfloat16, _need_kv_multi, qkv, (k_cache, v_cache),
                                    past, lens, batch, seq, n_q_heads, n_kv_heads, head_dim, slot_ids, page_table, chunk,
                                    max_len, scale, workspace, out)
+
+
+def decode_attention_wide(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, past: torch.Tensor,
+                          lens: torch.Tensor, batch: int, seq: int, n_q_heads: int, n_kv_heads: int, head_dim: int, *,
+                          slot_ids: Optional[torch.Tensor] = None, page_table: Optional[torch.Tensor] = None,
+                          chunk: int = 64, max_len: Optional[int] = None, scale: Optional[float] = None,
+                          workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`decode_attention_multi` up to ``seq * Hq / Hkv <= 64`` (``seq <= 16``): the verify step of 4 to 15
+    drafts.  Same arguments, workspace and contract; the query columns lie on up to four 16-column tiles of one
+    block, which loads a split's K / V rows once for all of them (``csrc/decode_verify_wide.hip``).  At
+    ``seq * Hq / Hkv <= 16`` the call is :func:`decode_attention_multi`'s, bit for bit."""
+    return _decode_attention_multi("decode_attention_wide", torch.bfloat16, _need_kv_multi, qkv, (k_cache, v_cache),
+                                   past, lens, batch, seq, n_q_heads, n_kv_heads, head_dim, slot_ids, page_table, chunk,
+                                   max_len, scale, workspace, out, cols=64)
 
 
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, lens: torch.Tensor,

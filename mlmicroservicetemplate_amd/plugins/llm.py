@@ -90,6 +90,7 @@ class LlamaPlugin(ModelPlugin):
             raise ValueError("prefill_chunk is not available with kv_dtype: fp8 (a chunk would attend e4m3 context "
                              "rows where one-shot prefill attends unquantised ones)")
         verify_fp8 = self.parse_verify_fp8(extra, kv_dtype, kv_prefill)
+        verify_cols = self.parse_verify_cols(extra, kv_dtype)
         kv_pages = self._kv_pages(extra.get("kv_pages", 0), cfg, tp, max_batch, max_seq, dev, backend, kv_dtype)
         if tp > 1 and kv_pages:  # the scheduler replays rank 0's admissions: every pool must be equal
             from ..parallel import dist as mdist
@@ -98,7 +99,8 @@ class LlamaPlugin(ModelPlugin):
         self.model = llama.LlamaTP(params, cfg, tp=tp, rank=ctx.rank, comm=llama.TPComm(None, tp, device=dev), backend=backend,
                                    device=dev, max_batch=max_batch, max_seq=max_seq, kv_pages=kv_pages,
                                    kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_prefill=kv_prefill, lora=lora_kw,
-                                   w4_rows=w4_rows, w8_decode=w8_decode, verify_fp8=verify_fp8)
+                                   w4_rows=w4_rows, w8_decode=w8_decode, verify_fp8=verify_fp8,
+                                   verify_cols=verify_cols)
         for index, (name, path) in enumerate(lora_paths.items()):  # every rank reads the adapter and keeps its share (load_adapter)
             from ..utils.checkpoint import load_lora_adapter
 
@@ -127,9 +129,11 @@ class LlamaPlugin(ModelPlugin):
                 self.engine.start()
         self.kv_pages = kv_pages
         logger.info("llama ready: tp=%d rank=%d backend=%s device=%s kv_dtype=%s kv_prefill=%s kv_bytes_per_token=%d "
-                    "weight_dtype=%s w4_rows=%s w8_decode=%s layer_weight_bytes=%d prefix_cache=%s verify_fp8=%s", tp,
+                    "weight_dtype=%s w4_rows=%s w8_decode=%s layer_weight_bytes=%d prefix_cache=%s verify_fp8=%s "
+                    "verify_cols=%d", tp,
                     ctx.rank, backend, dev, kv_dtype, kv_prefill, self.kv_page_bytes(cfg, tp, backend, kv_dtype) // 64,
-                    weight_dtype, w4_rows, w8_decode, self.model.layer_weight_bytes(), self.prefix_cache, verify_fp8)
+                    weight_dtype, w4_rows, w8_decode, self.model.layer_weight_bytes(), self.prefix_cache, verify_fp8,
+                    verify_cols)
 
     @staticmethod
     def parse_weight_dtype(extra: dict) -> str:
@@ -177,6 +181,18 @@ class LlamaPlugin(ModelPlugin):
             raise ValueError(f"verify_fp8: {mode} is for kv_dtype: fp8 with kv_prefill: cache only, got "
                              f"{kv_dtype!r} / {kv_prefill!r}")
         return mode
+
+    @staticmethod
+    def parse_verify_cols(extra: dict, kv_dtype: str) -> int:
+        """MODEL_CONFIG ``verify_cols`` (with a bf16 KV cache only): ``16`` (default) | ``64`` -- the bound on
+        (speculate + 1) * Hq / Hkv; above 16 a speculation step's attention runs the wide verify kernel
+        ``decode_attention_wide`` (:class:`~..models.llama.LlamaTP`)."""
+        raw = extra.get("verify_cols", 16)
+        if isinstance(raw, bool) or str(raw) not in ("16", "64"):
+            raise ValueError(f"verify_cols must be 16 or 64, got {raw!r}")
+        if int(raw) != 16 and kv_dtype == "fp8":
+            raise ValueError(f"verify_cols: {raw} is for kv_dtype: bf16 only, got {kv_dtype!r}")
+        return int(raw)
 
     @staticmethod
     def parse_lora(extra: dict, prefix_cache: bool = False):

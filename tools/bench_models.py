@@ -123,17 +123,18 @@ def bench_verify_attn(args):
                 arms = {"decode_T1": lambda: ops.decode_attention(q1, kc, vc, lens, Hq, Hkv, D, chunk=64, head_major=True,
                                                                   workspace=ws1, out=o1, max_len=ctx, page_table=table,
                                                                   counters=cnt)}
-                for T in (2, 3, 4):
+                for T in (2, 3, 4, 5, 6, 8):  # T * Hq / Hkv > 16: the wide kernel (ops.decode_attention_wide)
                     past = torch.full((B,), ctx - T, dtype=torch.int32, device=dev)
                     qT = torch.randn(B * T, W, device=dev, generator=g).to(torch.bfloat16)
                     wsT = torch.empty(B * T * Hq * (rows // 64 + 1) * (D + 2), device=dev, dtype=torch.float32)
                     oT = torch.empty(B * T, Hq * D, device=dev, dtype=torch.bfloat16)
                     oC = torch.empty_like(oT)
-                    arms[f"multi_T{T}"] = (lambda T=T, past=past, qT=qT, wsT=wsT, oT=oT: ops.decode_attention_multi(
+                    name, op = ("multi", ops.decode_attention_multi) if T <= 4 else ("wide", ops.decode_attention_wide)
+                    arms[f"{name}_T{T}"] = (lambda T=T, past=past, qT=qT, wsT=wsT, oT=oT, op=op: op(
                         qT, kc, vc, past, lens, B, T, Hq, Hkv, D, page_table=table, max_len=ctx, workspace=wsT, out=oT))
                     arms[f"ctx_S{T}"] = (lambda T=T, past=past, qT=qT, oC=oC: ops.flash_attention_ctx(
                         qT, kc, vc, past, lens, B, T, Hq, Hkv, D, page_table=table, out=oC))
-                    if args.kv_dtype == "fp8":  # the e4m3 cache's two verify routes (LlamaTP.verify_fp8) on the same rows
+                    if args.kv_dtype == "fp8" and T <= 4:  # the e4m3 cache's two verify routes (LlamaTP.verify_fp8) on the same rows
                         o8, oC8 = torch.empty_like(oT), torch.empty_like(oT)
                         arms[f"multi_fp8_T{T}"] = (lambda T=T, past=past, qT=qT, wsT=wsT, o8=o8: ops.decode_attention_multi_fp8(
                             qT, *c8, past, lens, B, T, Hq, Hkv, D, page_table=table, max_len=ctx, workspace=wsT, out=o8))
@@ -294,7 +295,7 @@ def bench_llama(args):
     comm = ShardEmulationComm(tp) if tp > 1 else None
     m = LlamaTP(p, LLAMA3_8B, tp=tp, rank=0, comm=comm, backend="fused", device=dev, max_batch=max(args.batches),
                 max_seq=args.max_seq, kv_pages=args.kv_pages, kv_dtype=args.kv_dtype, weight_dtype=args.weight_dtype, w4_rows=args.w4_rows, w8_decode=args.w8_decode, verify_fp8=args.verify_fp8,
-                kv_prefill=args.kv_prefill)
+                kv_prefill=args.kv_prefill, verify_cols=args.verify_cols)
     if m.pages is not None and args.shuffle_pages:  # pages scattered as in a long-running server
         import random
 
@@ -621,6 +622,8 @@ def main():
     ap.add_argument("--verify-fp8", choices=["ctx", "multi"], default="ctx",
                     help="llama, --kv-dtype fp8 --kv-prefill cache: a verify step's attention on flash_attention_ctx_fp8, "
                          "or on the e4m3 verify kernel decode_attention_multi_fp8 (--speculate times both arms)")
+    ap.add_argument("--verify-cols", type=int, choices=[16, 64], default=16,
+                    help="llama: 64 admits --speculate 4 .. 7 at Hq / Hkv = 4 (the wide verify kernel decode_attention_wide)")
     ap.add_argument("--weight-dtype", choices=["bf16", "int4", "w8a8"], default="bf16",
                     help="llama: layer projections in bf16, W4A16 (4-bit codes, one bf16 scale per row and 128 k), or "
                          "W8A8 (e4m3 weights per channel, e4m3 activations per row, block-scaled MFMA)")
