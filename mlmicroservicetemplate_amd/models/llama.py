@@ -599,7 +599,12 @@ class LlamaTP:
         Hq / Hkv -- :meth:`check_speculate` admits ``(speculate + 1) * Hq / Hkv <= verify_cols``, and the fused
         backend's verify steps above 16 columns attend through ``ops.decode_attention_wide``
         (``csrc/decode_verify_wide.hip``); steps of <= 16 columns run as with 16.  The reference backend accepts
-        it and computes the same."""
+        it and computes the same.
+        ``verify_fp8="wide"`` (as ``"multi"``: fp8 cache with ``kv_prefill="cache"`` only): ``"multi"`` plus the
+        wide kernel of the e4m3 cache -- :meth:`check_speculate` admits ``(speculate + 1) * Hq / Hkv <= 64``,
+        verify steps of <= 16 columns run ``ops.decode_attention_multi_fp8`` as under ``"multi"``, steps of 17 to
+        64 columns ``ops.decode_attention_wide_fp8`` (``csrc/decode_verify_wide_fp8.hip``).  ``verify_cols`` stays
+        16.  The reference backend only admits the larger ``speculate``."""
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
         if weight_dtype not in ("bf16", "int4", "w8a8"):
@@ -617,8 +622,8 @@ class LlamaTP:
         if kv_prefill == "cache" and kv_dtype != "fp8":
             raise ValueError("kv_prefill='cache' is for kv_dtype='fp8' only: a bf16 cache already holds the very "
                              "rows prefill attends")
-        if verify_fp8 not in ("ctx", "multi"):
-            raise ValueError(f"verify_fp8 must be 'ctx' or 'multi', got {verify_fp8!r}")
+        if verify_fp8 not in ("ctx", "multi", "wide"):
+            raise ValueError(f"verify_fp8 must be 'ctx', 'multi' or 'wide', got {verify_fp8!r}")
         if verify_fp8 != "ctx" and (kv_dtype != "fp8" or kv_prefill != "cache"):
             raise ValueError(f"verify_fp8={verify_fp8!r} is for kv_dtype='fp8' with kv_prefill='cache' only, got "
                              f"{kv_dtype!r} / {kv_prefill!r}")
@@ -1090,7 +1095,8 @@ class LlamaTP:
             head_dim=cfg.head_dim, hidden=cfg.hidden, have_packed=bool(self.packed), have_w4=bool(self.w4),
             have_w8=bool(self.w8), w4_all=self.w4_rows == "all",
             w8_skinny=self.w8_decode == "skinny", w8_skinny_rows=self.w8_skinny_rows,
-            verify_fp8_multi=self.verify_fp8 == "multi", verify_cols=self.verify_cols,
+            verify_fp8_multi=self.verify_fp8 != "ctx", verify_cols=self.verify_cols,
+            verify_fp8_wide=self.verify_fp8 == "wide",
             have_fp8=bool(self.fp8), o_packed="l0.o" in self.packed, o_fp8="l0.o" in self.fp8, kv_fp8=self.kv_fp8,
             w4_max_rows=self.w4_max_rows, pk_fold=self.pk_fold, prefill_fold=self.prefill_fold,
             fuse_combine=self.fuse_combine, fuse_add_norm=self.fuse_add_norm, ar_fuse=self.ar_fuse,
@@ -1296,6 +1302,9 @@ class LlamaTP:
             a = attend(qkv, *caches, st.lens, sd.hq, sd.hkv, D, **st.attn_kw)
             return a if st.rt.fuse_combine else (a, None)
         self._rope_kv(i, qkv, st.pos, st.slots, st.lens, st.S)
+        if st.rt.wide and self.kv_fp8:  # verify_fp8="wide": more than 16 columns on the e4m3 cache
+            return ops.decode_attention_wide_fp8(qkv, kc, vc, self.k_scale[i], self.v_scale[i], st.past, st.lens, st.B,
+                                                 st.S, sd.hq, sd.hkv, D, **st.attn_kw), None
         if st.rt.multi and self.kv_fp8:
             return ops.decode_attention_multi_fp8(qkv, kc, vc, self.k_scale[i], self.v_scale[i], st.past, st.lens, st.B,
                                                   st.S, sd.hq, sd.hkv, D, **st.attn_kw), None
@@ -1664,9 +1673,10 @@ class LlamaTP:
             raise ValueError(str(e).replace("chunked prefill", "speculative decoding")) from None
         if self.backend == "fused":
             G = self.sd.hq // max(self.sd.hkv, 1)
-            if G not in (1, 2, 4, 8) or (speculate + 1) * G > self.verify_cols:
+            cols = 64 if self.verify_fp8 == "wide" else self.verify_cols
+            if G not in (1, 2, 4, 8) or (speculate + 1) * G > cols:
                 raise ValueError(f"speculative decoding on the fused backend needs Hq / Hkv in 1, 2, 4, 8 and "
-                                 f"(speculate + 1) * Hq / Hkv <= {self.verify_cols} (got speculate {speculate}, "
+                                 f"(speculate + 1) * Hq / Hkv <= {cols} (got speculate {speculate}, "
                                  f"{self.sd.hq} / {self.sd.hkv} heads on this rank)")
 
     def check_prefix_cache(self) -> None:

@@ -79,7 +79,8 @@ class StepRoute:
     overlap: bool       # TP prefill as two interleaved batch halves
     dec_chunk: int      # decode split rows
     lora_tail: bool = False  # a loaded adapter targets o / gate / up / down: the tail runs unfused around the deltas
-    wide: bool = False  # a multi step of more than 16 columns (verify_cols=64): ops.decode_attention_wide
+    wide: bool = False  # a multi step of more than 16 columns: ops.decode_attention_wide (verify_cols=64), on an
+                        # e4m3 cache ops.decode_attention_wide_fp8 (verify_fp8="wide")
 
     @property
     def fuse(self) -> bool:
@@ -104,7 +105,8 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
                fuse_add_norm: bool, ar_fuse: bool, tp_overlap: bool, verify_attn: str, spec_max_tokens: int,
                dec_chunk: int, ar_fusable: bool, capturing: bool, kv_fp8: bool = False,
                have_w8: bool = False, lora_tail: bool = False, w4_all: bool = False, w8_skinny: bool = False,
-               w8_skinny_rows: int = 16, verify_fp8_multi: bool = False, verify_cols: int = 16) -> StepRoute:
+               w8_skinny_rows: int = 16, verify_fp8_multi: bool = False, verify_cols: int = 16,
+               verify_fp8_wide: bool = False) -> StepRoute:
     """``have_*``: the model holds such copies at all; ``o_packed`` / ``o_fp8``: of ``l0.o``;
     ``ar_fusable``: the comm's one-shot all-reduce can ride in a GEMM producing ``B * S * hidden``
     outputs; ``capturing``: the current stream is capturing a graph.  The rest are the model's
@@ -118,7 +120,9 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
     decision reads them.  ``verify_fp8_multi``: ``verify_fp8="multi"`` -- an e4m3 cache's verify steps may take
     ``multi`` (``ops.decode_attention_multi_fp8``); off, or on a bf16 cache, nothing changes.
     ``verify_cols``: the bound on a multi step's S * Hq / Hkv columns, 16 or 64 (a bf16 cache only); above 16
-    columns the step is ``wide`` (``ops.decode_attention_wide``)."""
+    columns the step is ``wide`` (``ops.decode_attention_wide``).  ``verify_fp8_wide``: ``verify_fp8="wide"`` -- an
+    e4m3 cache's verify steps may take ``multi`` up to 64 columns, ``wide`` above 16
+    (``ops.decode_attention_wide_fp8``); off, or on a bf16 cache, nothing changes."""
     T = B * S
     proj = proj_tiers(T, have_packed, have_w4, have_fp8, w4_max_rows, have_w8, w4_all, w8_skinny, w8_skinny_rows)
     # TP = 1: the residual add rides in the o / down epilogues (h = r + a Wo^T, r' = h + g Wd^T), so
@@ -150,9 +154,11 @@ def step_route(*, B: int, S: int, decode: bool, has_past: bool, all_rows: bool, 
     # Chunked prefill (all_rows False) stays on flash_attention_ctx.  An e4m3 cache's verify steps take the
     # context kernel too (ops.flash_attention_ctx_fp8, split-KV) unless verify_fp8="multi" opts into the
     # verify kernel of that cache (ops.decode_attention_multi_fp8), under the same conditions.
+    # verify_fp8="wide" is "multi" with the e4m3 cache's own 64-column bound (verify_cols stays 16 there).
+    cols = 64 if kv_fp8 and verify_fp8_wide else verify_cols
     multi = (has_past and all_rows and verify_attn != "ctx" and S <= spec_max_tokens
-             and S * (hq // max(hkv, 1)) <= verify_cols and (not kv_fp8 or verify_fp8_multi))
-    # verify_cols=64: the columns past one MFMA's 16 lie on up to four column tiles of the same block
+             and S * (hq // max(hkv, 1)) <= cols and (not kv_fp8 or verify_fp8_multi or verify_fp8_wide))
+    # the columns past one MFMA's 16 lie on up to four column tiles of the same block
     wide = multi and S * (hq // max(hkv, 1)) > 16
     # TP prefill: two batch halves interleaved so each o / down all-reduce overlaps the other half's
     # compute (LlamaTP._prefill_overlapped); MLS_TP_OVERLAP=0 runs the plain layer loop

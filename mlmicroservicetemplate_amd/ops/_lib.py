@@ -109,6 +109,7 @@ _SIGS = {
     "mls_decode_attention_multi": [P, P, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F, P],
     "mls_decode_attention_multi_fp8": [P, P, P, P, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F, P],
     "mls_decode_attention_wide": [P, P, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F, P],
+    "mls_decode_attention_wide_fp8": [P, P, P, P, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, F, P],
     "mls_decode_combine": [P, P, P, I, P, I, I, I, I, P],
     "mls_skinny_gemm": [P, P, P, P, P, P, SZ, I, I, I, I, I, P],
     "mls_mgemm": [P, P, P, P, P, P, SZ, I, I, I, I, I, I, P], "mls_mgemm_auto_split": [I, I, I],
@@ -176,7 +177,8 @@ def _bind(lib: ctypes.CDLL) -> None:
 DEBUG = os.environ.get("MLS_DEBUG", "0") == "1"
 DEBUG_TUS = ("attention", "norm_ops", "stem_pool", "conv3x3_halo", "kv_fp8", "flash_ctx", "decode_verify",
              "decode_verify_fp8", "decode_pick", "spec_step", "lora",
-             "lora_linear", "lm_logprob", "decode_verify_wide")  # translation units with MLS_CHECK bounds
+             "lora_linear", "lm_logprob", "decode_verify_wide",
+             "decode_verify_wide_fp8")  # translation units with MLS_CHECK bounds
 DEBUG_CODES = {
     101: "rope/KV append: cache slot beyond the cache",
     102: "rope/KV append: position beyond the RoPE table",
@@ -198,6 +200,10 @@ DEBUG_CODES = {
     327: "decode attention (wide): not 0 <= past[b] <= lens[b] <= the rows of a slot / the split grid (max_len)",
     328: "decode attention (wide): slot outside the cache",
     329: "decode attention (wide): page id outside the pool",
+    330: "decode attention (wide, fp8 cache): not 0 <= past[b] <= lens[b] <= the rows of a slot / the split grid "
+         "(max_len)",
+    331: "decode attention (wide, fp8 cache): slot outside the cache",
+    332: "decode attention (wide, fp8 cache): page id outside the pool",
     401: "decode pick: winning candidate index outside [0, tp * k) (a row of NaN candidates)",
     411: "spec draft: rows[r] is not a serving slot",
     412: "spec draft / accept: token count or history column outside the prompt / history arrays",

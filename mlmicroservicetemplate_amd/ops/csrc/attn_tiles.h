@@ -244,6 +244,18 @@ MLS_DEV void decode_v_fill_fp8(char* V, int krow, int cch, uint4 v) {
   *reinterpret_cast<uint4*>(V + krow * DecodeDims::VST + cch * 32 + 16) =
       __builtin_bit_cast(uint4, fp8x8_to_bf16(v.z, v.w));
 }
+// The e4m3 verify kernels (decode_verify_fp8.hip, decode_verify_wide_fp8.hip): the scales of keys kf .. kf + 3
+// (kf % 4 == 0) of the block whose key 0 is row `rowbase`; keys >= end read 0
+MLS_DEV float4 scales4(const float* sc, long rowbase, int kf, int end) {
+  const float* p = sc + rowbase + kf;
+  if (kf + 4 <= end && ((rowbase + kf) & 3) == 0) return *reinterpret_cast<const float4*>(p);
+  float4 r;
+  r.x = kf < end ? p[0] : 0.f;
+  r.y = kf + 1 < end ? p[1] : 0.f;
+  r.z = kf + 2 < end ? p[2] : 0.f;
+  r.w = kf + 3 < end ? p[3] : 0.f;
+  return r;
+}
 
 // Merge the block's waves through LDS once each has stored (mt, ls) of column fr in sm_m / sm_l and its O
 // rows (columns 4g + j) in sm_o -- that store stays in the kernels: through this struct one instantiation

@@ -58,18 +58,6 @@ struct VerifyFp8Args {
   float scale_log2;
 };
 
-// the scales of keys kf .. kf + 3 (kf % 4 == 0) of the block whose key 0 is row `rowbase`; keys >= end read 0
-MLS_DEV float4 scales4(const float* sc, long rowbase, int kf, int end) {
-  const float* p = sc + rowbase + kf;
-  if (kf + 4 <= end && ((rowbase + kf) & 3) == 0) return *reinterpret_cast<const float4*>(p);
-  float4 r;
-  r.x = kf < end ? p[0] : 0.f;
-  r.y = kf + 1 < end ? p[1] : 0.f;
-  r.z = kf + 2 < end ? p[2] : 0.f;
-  r.w = kf + 3 < end ? p[3] : 0.f;
-  return r;
-}
-
 template <int G, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void decode_verify_fp8_kernel(const VerifyFp8Args a) {
   using TD = DecodeTile<G, WAVES>;

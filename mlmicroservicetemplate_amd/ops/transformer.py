@@ -356,8 +356,8 @@ def _need_kv_multi(k_cache, v_cache, n_kv_heads: int, head_dim: int, dev) -> Non
 def _decode_attention_multi(op: str, cache_dtype, need_caches, qkv, caches, past, lens, batch: int, seq: int,
                             n_q_heads: int, n_kv_heads: int, head_dim: int, slot_ids, page_table, chunk, max_len, scale,
                             workspace, out, cols: int = 16):
-    """The body of :func:`decode_attention_multi`, :func:`decode_attention_multi_fp8` and
-    :func:`decode_attention_wide`: ``op`` names the
+    """The body of :func:`decode_attention_multi`, :func:`decode_attention_multi_fp8`,
+    :func:`decode_attention_wide` and :func:`decode_attention_wide_fp8`: ``op`` names the
     caller in the messages and the library's entry point ``mls_<op>``, ``caches`` = (k_cache, v_cache[,
     k_scale, v_scale]) of ``cache_dtype`` as the entry point takes them, ``need_caches(*caches, n_kv_heads,
     head_dim, dev)`` checks their shapes, ``cols`` is the entry point's limit on ``seq * Hq / Hkv``."""
@@ -702,6 +702,24 @@ def decode_attention_multi_fp8(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache
     return _decode_attention_multi("decode_attention_multi_fp8", torch.uint8, _need_kv_fp8, qkv,
                                    (k_cache, v_cache, k_scale, v_scale), past, lens, batch, seq, n_q_heads,
                                    n_kv_heads, head_dim, slot_ids, page_table, chunk, max_len, scale, workspace, out)
+
+
+def decode_attention_wide_fp8(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: torch.Tensor,
+                              v_scale: torch.Tensor, past: torch.Tensor, lens: torch.Tensor, batch: int, seq: int,
+                              n_q_heads: int, n_kv_heads: int, head_dim: int, *,
+                              slot_ids: Optional[torch.Tensor] = None, page_table: Optional[torch.Tensor] = None,
+                              chunk: int = 64, max_len: Optional[int] = None, scale: Optional[float] = None,
+                              workspace: Optional[torch.Tensor] = None,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`decode_attention_multi_fp8` up to ``seq * Hq / Hkv <= 64`` (``seq <= 16``): the verify step of 4 to
+    15 drafts on an FP8 (e4m3) cache.  Same arguments, caches, scales, workspace and refusals; the query columns
+    lie on up to four 16-column tiles of one block, which loads a split's e4m3 K / V rows and their scales once
+    and converts them to bf16 once for all of them (``csrc/decode_verify_wide_fp8.hip``).  At
+    ``seq * Hq / Hkv <= 16`` the call is :func:`decode_attention_multi_fp8`'s, bit for bit."""
+    return _decode_attention_multi("decode_attention_wide_fp8", torch.uint8, _need_kv_fp8, qkv,
+                                   (k_cache, v_cache, k_scale, v_scale), past, lens, batch, seq, n_q_heads,
+                                   n_kv_heads, head_dim, slot_ids, page_table, chunk, max_len, scale, workspace, out,
+                                   cols=64)
 
 
 def skinny_packed_combine(attn_out: torch.Tensor, parts: DecodePartials, wp: torch.Tensor, N: int, *,

@@ -173,10 +173,11 @@ class LlamaPlugin(ModelPlugin):
     def parse_verify_fp8(extra: dict, kv_dtype: str, kv_prefill: str) -> str:
         """MODEL_CONFIG ``verify_fp8`` (with ``kv_dtype: fp8`` and ``kv_prefill: cache`` only): ``ctx`` (default: a
         speculation step's attention on ``flash_attention_ctx_fp8``) | ``multi`` (on the e4m3 verify kernel
-        ``decode_attention_multi_fp8``; :class:`~..models.llama.LlamaTP`)."""
+        ``decode_attention_multi_fp8``) | ``wide`` (``multi``, and (speculate + 1) * Hq / Hkv up to 64 with the
+        steps above 16 on ``decode_attention_wide_fp8``; :class:`~..models.llama.LlamaTP`)."""
         mode = str(extra.get("verify_fp8", "ctx"))
-        if mode not in ("ctx", "multi"):
-            raise ValueError(f"verify_fp8 must be 'ctx' or 'multi', got {mode!r}")
+        if mode not in ("ctx", "multi", "wide"):
+            raise ValueError(f"verify_fp8 must be 'ctx', 'multi' or 'wide', got {mode!r}")
         if mode != "ctx" and (kv_dtype != "fp8" or kv_prefill != "cache"):
             raise ValueError(f"verify_fp8: {mode} is for kv_dtype: fp8 with kv_prefill: cache only, got "
                              f"{kv_dtype!r} / {kv_prefill!r}")

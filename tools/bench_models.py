@@ -73,7 +73,7 @@ def bench_verify_attn(args):
     from events around one replay of a graph of ``--steps`` launches, median and minimum of 5 windows.  The same
     K / V are re-read by every launch, so the numbers are L2-warm.  ``--kv-dtype fp8`` adds the e4m3 cache's two verify
     routes on the same rows: ``ops.decode_attention_multi_fp8`` and ``ops.flash_attention_ctx_fp8`` with the
-    split count ``LlamaTP`` gives a verify step."""
+    split count ``LlamaTP`` gives a verify step (T = 5, 6, 8: ``ops.decode_attention_wide_fp8``)."""
     from mlmicroservicetemplate_amd import ops
     from mlmicroservicetemplate_amd.models.llama import LlamaTP
     from mlmicroservicetemplate_amd.ops import reference as R
@@ -134,9 +134,10 @@ def bench_verify_attn(args):
                         qT, kc, vc, past, lens, B, T, Hq, Hkv, D, page_table=table, max_len=ctx, workspace=wsT, out=oT))
                     arms[f"ctx_S{T}"] = (lambda T=T, past=past, qT=qT, oC=oC: ops.flash_attention_ctx(
                         qT, kc, vc, past, lens, B, T, Hq, Hkv, D, page_table=table, out=oC))
-                    if args.kv_dtype == "fp8" and T <= 4:  # the e4m3 cache's two verify routes (LlamaTP.verify_fp8) on the same rows
+                    if args.kv_dtype == "fp8":  # the e4m3 cache's verify routes (LlamaTP.verify_fp8) on the same rows
                         o8, oC8 = torch.empty_like(oT), torch.empty_like(oT)
-                        arms[f"multi_fp8_T{T}"] = (lambda T=T, past=past, qT=qT, wsT=wsT, o8=o8: ops.decode_attention_multi_fp8(
+                        op8 = ops.decode_attention_multi_fp8 if T <= 4 else ops.decode_attention_wide_fp8
+                        arms[f"{name}_fp8_T{T}"] = (lambda T=T, past=past, qT=qT, wsT=wsT, o8=o8, op8=op8: op8(
                             qT, *c8, past, lens, B, T, Hq, Hkv, D, page_table=table, max_len=ctx, workspace=wsT, out=o8))
                         ns = LlamaTP.ctx_split_rule(B, T, Hq, ctx)  # as LlamaTP._ctx_split_kw(verify=True) routes it
                         kw8 = {} if ns <= 1 else dict(splits=ns, max_ctx=ctx, workspace=torch.empty(
@@ -454,9 +455,15 @@ def _bench_speculate(m, args, K, B, S, ids, lens, tok, cur):
     n = torch.full((B,), T, device=dev, dtype=torch.int32)
     arms = {"decode": lambda: m.decode_step(tok, cur, 1, max_ctx=S + 1)}
     fp8_arms = m.kv_fp8 and m.kv_prefill == "cache"  # an e4m3 cache: the routes are LlamaTP.verify_fp8's
-    for route in ("multi", "ctx"):  # the verify step's two attention routes (LlamaTP.verify_attn; a graph per route)
+    # the verify step's two attention routes (LlamaTP.verify_attn; a graph per route); --verify-fp8 wide times its own
+    # route (past K = 3 "multi" would fall back to the context kernel) against ctx at the same K: verify_fp8="ctx"
+    # stops at K = 3, so that arm keeps "wide" for check_speculate and takes the context kernel by verify_attn="ctx"
+    wide = fp8_arms and args.verify_fp8 == "wide"
+    for route in ("wide" if wide else "multi", "ctx"):
         def step(route=route):
-            if fp8_arms:
+            if wide:
+                m.verify_attn = "ctx" if route == "ctx" else "multi"
+            elif fp8_arms:
                 m.verify_fp8 = route
             else:
                 m.verify_attn = route
@@ -619,9 +626,10 @@ def main():
     ap.add_argument("--w8-decode", choices=["tile", "skinny"], default="tile",
                     help="llama, --weight-dtype w8a8: steps of <= 16 rows on quant_rows_fp8 + gemm_w8a8, or on the "
                          "weight-streaming skinny_w8 kernel")
-    ap.add_argument("--verify-fp8", choices=["ctx", "multi"], default="ctx",
+    ap.add_argument("--verify-fp8", choices=["ctx", "multi", "wide"], default="ctx",
                     help="llama, --kv-dtype fp8 --kv-prefill cache: a verify step's attention on flash_attention_ctx_fp8, "
-                         "or on the e4m3 verify kernel decode_attention_multi_fp8 (--speculate times both arms)")
+                         "or on the e4m3 verify kernel decode_attention_multi_fp8 (--speculate times both arms); wide: "
+                         "multi, and --speculate 4 .. 7 at Hq / Hkv = 4 on decode_attention_wide_fp8")
     ap.add_argument("--verify-cols", type=int, choices=[16, 64], default=16,
                     help="llama: 64 admits --speculate 4 .. 7 at Hq / Hkv = 4 (the wide verify kernel decode_attention_wide)")
     ap.add_argument("--weight-dtype", choices=["bf16", "int4", "w8a8"], default="bf16",
